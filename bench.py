@@ -18,8 +18,8 @@ variants; each names itself in config.workload.  Genomes and reads are generated
 once and rotated over the steps (the mapper keeps no state between calls, so a repeated batch costs what a fresh one does).
 
 Rank 0 prints ONE JSON line.  `value` = read bases / wall time of the K timed steps fed from HOST buffers (the read H2D is
-inside the timed call: SURVEY 8d's wall time includes it); `resident_input_gbp_per_min` = a few more steps with the reads
-already in HBM, as a side figure.  `roofline` is for the kernel with the largest EXCLUSIVE device time: after the timed region
+inside the timed call: SURVEY 8d's wall time includes it); `resident_input_gbp_per_min` = as many more steps (--resident-steps) with
+the reads already in HBM, as a side figure.  `roofline` is for the kernel with the largest EXCLUSIVE device time: after the timed region
 a slice of a batch runs through ONE pipeline worker (nothing else on the GPU), which gives every candidate's launch duration
 alone (`alone_ms`) beside its HIP-event span inside the 12-worker pipeline (`in_pipeline_ms`); fractions are given on the HBM
 axis (8 TB/s) and on the VALU axis (1.229e12 wave-instructions/s = 1024 SIMDs x 2.4 GHz / 2 cycles, the guide's figure; the
@@ -38,8 +38,6 @@ import sys
 import time
 
 import numpy as np
-
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '20')  # before the HIP runtime starts: see megapath_nano_amd/__init__.py
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -492,6 +490,24 @@ def correctness_block(idx, opt, batch, args, members, twin_of, counts, sampled, 
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out):
+    """The arrays one step of the timed path returns (align_and_assign / human_decoy_step), as out_dir/<name>.npy in float64
+    (exact for these integer counters).  An array beyond its share of DUMP_BYTES is cut to a fixed seeded sample of its
+    elements, whose positions go beside it as <name>_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // 8 // (2 * len(out))   # elements per array, leaving room for a sample's positions
+    for name, v in out.items():
+        a = np.asarray(v, dtype=np.float64)
+        if a.size > cap:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            np.save(os.path.join(out_dir, f'{name}_index.npy'), pos.astype(np.float64))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -510,14 +526,21 @@ def main():
     ap.add_argument('--reads-per-step', type=int, default=None)
     ap.add_argument('--mean-len', type=int, default=8000)
     ap.add_argument('--distinct-batches', type=int, default=3)
-    ap.add_argument('--resident-steps', '--pcie-steps', dest='resident_steps', type=int, default=6,
-                    help='extra steps with the reads already resident in HBM (the side figure resident_input_gbp_per_min; `value` is fed from host buffers)')
+    ap.add_argument('--resident-steps', '--pcie-steps', dest='resident_steps', type=int, default=None,
+                    help='extra steps with the reads already resident in HBM (the side figure resident_input_gbp_per_min; `value` is fed from host buffers); '
+                         'default: --steps')
     ap.add_argument('--alone-reads', type=int, default=0, help='reads of the single-worker pass that times every kernel alone (0 = an eighth of a batch; -1 = skip)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-correctness', action='store_true')
     ap.add_argument('--mapping-only', action='store_true', help='diagnostic: no base-level extension (the reference\'s mapping_only mode); implies --no-correctness, not the metric')
     ap.add_argument('--cpu-index-genomes', type=int, default=250, help='genomes of the CPU baseline\'s index (250 x 4 Mbp = 1 Gbp)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (float64), for comparing two builds output for output')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.resident_steps is None:
+        args.resident_steps = args.steps
     if args.mapping_only:
         args.no_correctness = True
         args.no_cpu_baseline = True
@@ -645,6 +668,9 @@ def main():
             log(f'{args.resident_steps} resident-input steps done')
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+        log(f'outputs of the last timed step written to {args.dump_outputs}')
 
     K = max(1, args.steps)
     st = {k: v / K for k, v in stats_acc.items()}  # per step (rank 0), summed over the index parts a step maps

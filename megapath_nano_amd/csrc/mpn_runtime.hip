@@ -23,10 +23,4 @@ long long arena_test_budget() {
 }
 }  // namespace mpn
 
-// The pipelined mapper keeps 12 workers x 2 HIP streams in flight.  ROCm multiplexes streams onto GPU_MAX_HW_QUEUES
-// hardware queues (4 by default), and streams that share a queue serialise: measured on MI355X, 4 -> 16 queues raised
-// whole-job throughput by 15-30%, 16 -> 20 by another 2% (24, one queue per stream, loses 15%).  The variable is read when the HIP runtime initialises, so it is set when this
-// library is loaded, unless the caller already chose a value; a host that initialised HIP earlier should export it.
-__attribute__((constructor)) static void mpn_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "20", 0); }
-
 extern "C" const char *mpn_last_error(void) { return mpn::get_error(); }

@@ -1,6 +1,5 @@
 import os, sys, time, random
 sys.path.insert(0, os.getcwd())
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '20')
 import numpy as np, torch
 import bench
 from megapath_nano_amd import mapper, synth

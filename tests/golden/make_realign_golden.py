@@ -1,7 +1,8 @@
 """Generates tests/golden/realign_golden.json from the reference's own amplicon realigner: realigner.cpp + ssw_cpp.cpp + ssw.c
 compiled in place by oracle/Makefile (oracle/_ref/librealigner.so), called through its C entry points `realign_reads` /
 `free_memory` exactly as /root/reference/bin/realignment/realign_illumina_reads.py:596-629 does, on the seeded windows of
-tests/realign_cases.py.  Only inputs and outputs are stored.
+tests/realign_cases.py.  Only inputs and outputs are stored.  Also writes realign_random_golden.json: the outputs on the random windows of
+tests/test_realign_oracle.py.
 
     make -C oracle && python tests/golden/make_realign_golden.py
 """
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle.realign_bindings import have_ref, ref_realign  # noqa: E402
-from realign_cases import make_cases  # noqa: E402
+from realign_cases import make_cases, make_window, random_window_kwargs  # noqa: E402
 
 assert have_ref(), 'oracle/_ref/librealigner.so is missing: run make -C oracle in a container that has /root/reference'
 out = []
@@ -24,3 +25,9 @@ for c in make_cases():
 with open(os.path.join(HERE, 'realign_golden.json'), 'w') as f:
     json.dump(out, f, separators=(',', ':'))
 print('wrote', len(out), 'windows,', sum(len(c['seqs']) for c in out), 'reads')
+# outputs only on the random windows of tests/test_realign_oracle.py, which the test regenerates from the seeds
+rand = [[[p, cg] for p, cg in ref_realign(**make_window(5000 + k, **kw))] for k, kw in enumerate(random_window_kwargs())]
+with open(os.path.join(HERE, 'realign_random_golden.json'), 'w') as f:
+    json.dump(dict(source='reference realigner via oracle/_ref/librealigner.so', windows='realign_cases.random_window_kwargs()',
+                   expected=rand), f, separators=(',', ':'))
+print('wrote', len(rand), 'random windows')

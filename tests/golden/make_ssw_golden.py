@@ -43,6 +43,21 @@ if __name__ == '__main__':
     main()
 
 
+def seeded_golden():
+    """Outputs of the compiled reference ssw.c on the seeded cases make_cases(4242, 600) of tests/ssw_cases.py, which the
+    test regenerates from the seed: tests/golden/ssw_seeded_golden.json."""
+    out = []
+    for c in make_cases(4242, 600):
+        res = ref_align(read=c['read'], ref=c['ref'], mat=c['mat'], gap_open=c['gap_open'],
+                        gap_extend=c['gap_extend'], flag=c['flag'], filters=c['filters'], filterd=c['filterd'],
+                        mask=c['mask'], score_size=c['score_size'])
+        out.append(None if res is None else [int(x) for x in res[:7]] + [[int(x) for x in res[7]]])
+    with open(os.path.join(HERE, 'ssw_seeded_golden.json'), 'w') as f:
+        json.dump(dict(source='reference ssw.c via oracle/_ref/libssw.so', cases='make_cases(4242, 600)', expect=out), f,
+                  separators=(',', ':'))
+    print('wrote seeded golden', len(out))
+
+
 def pyssw_golden():
     """(score, cigar string, ref_begin) from the reference's own Python wrapper
     (/root/reference/bin/realignment/pyssw.py SSW.align) driving the compiled reference ssw.c."""
@@ -84,4 +99,5 @@ def pyssw_golden():
 
 
 if __name__ == '__main__':
+    seeded_golden()
     pyssw_golden()

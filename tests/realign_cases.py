@@ -93,3 +93,12 @@ def make_cases():
     cases.append(make_window(207, n_reads=40, n_haps=24, prefix=36, center=82, suffix=111, read_len=89, uncovered_hap=True))  # > 16: std::sort's quicksort phase
     cases.append(make_window(208, n_reads=35, n_haps=18, prefix=60, center=30, suffix=60, read_len=50, include_ref=False, repeat=True))
     return cases
+
+
+def random_window_kwargs(seed=11, n=40):
+    """make_window keyword sets of the random windows (window k is make_window(5000 + k, **kw))."""
+    rng = np.random.default_rng(seed)
+    return [dict(n_reads=int(rng.integers(1, 50)), n_haps=int(rng.integers(1, 30)), prefix=int(rng.integers(33, 200)),
+                 center=int(rng.integers(8, 100)), suffix=int(rng.integers(33, 200)), read_len=int(rng.integers(25, 151)),
+                 include_ref=bool(rng.integers(0, 2)), uncovered_hap=bool(rng.integers(0, 3) == 0),
+                 repeat=bool(rng.integers(0, 4) == 0)) for _ in range(n)]

@@ -281,6 +281,26 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert out.returncode != 0 and 'WORLD_SIZE=4' in out.stderr
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array a step returns as <name>.npy in float64, integer values exact; an array beyond its
+    share of the byte budget becomes the same seeded sample on every run, its positions stored beside it."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4096)
+    rng = np.random.default_rng(5)
+    out = dict(read_count=rng.integers(0, 2 ** 40, size=10), classes=rng.integers(0, 3, size=5000).astype(np.int8), n_rows=5000)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), out)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b')) == ['classes.npy', 'classes_index.npy', 'n_rows.npy', 'read_count.npy']
+    got = {n[:-4]: np.load(tmp_path / 'a' / n) for n in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert all(np.array_equal(v, np.load(tmp_path / 'b' / (k + '.npy'))) for k, v in got.items())
+    assert sum(v.nbytes for v in got.values()) <= 4096
+    assert np.array_equal(got['read_count'], out['read_count']) and got['n_rows'] == 5000
+    pos = got['classes_index'].astype(np.int64)
+    assert len(pos) == len(set(pos)) > 0 and np.array_equal(got['classes'], out['classes'][pos])
+
+
 def test_classify_codes_equals_the_dataframe_classification():
     """filters.classify_codes (integer columns, bench.py --config c2) against filters.human_and_decoy_classify (the mirror of
     megapath_nano.py:1135-1200) on random tables."""
