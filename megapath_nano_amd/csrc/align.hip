@@ -882,6 +882,7 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     g_stats[4] += nj; g_stats[5] += T.cells; g_stats[31] += T.strip_cells[0] + T.strip_cells[1] + T.strip_cells[2];
     for (int c = 0; c < 3; ++c) g_stats[41 + c] += T.strip_cells[c];
     g_stats[58] += T.xstrip_cells;
+    g_stats[64] += cnt[L_TILE];   // windows on the tiled strips (none under MPN_TILED=0)
     if (getenv("MPN_DEBUG_JOBS")) {
         static const char *const fam[] = {"lds", "wg", "strip", "band"};
         for (int l = 0; l < N_LISTS; ++l)
@@ -1413,6 +1414,10 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
         MPN_HIP_CHECK(stream_sync(st));
         h_hregs = dst;
         g_stats[63] += (int64_t)hit_counters[2];
+    } else if (!gpu_hits) {   // MPN_HOST_HITS=1: every read with chains takes the host path
+        int64_t with_chains = 0;
+        for (int i = 0; i < n; ++i) with_chains += h.n_chain[i] > 0;
+        g_stats[63] += with_chains;
     }
     // (every pool thread stages the segments of its reads in a list of its own: a shared cursor is a hot cache line)
     std::vector<std::vector<SqueezeSeg>> &stage = SL.seg_stage;

@@ -82,7 +82,7 @@ struct HostChains {
     void chain_order(int i, int32_t *order, int64_t *src) const;
 };
 
-constexpr int MPN_NSTATS = 64;
+constexpr int MPN_NSTATS = 65;
 extern thread_local int64_t g_stats[MPN_NSTATS];
 
 // 2-bit packing of 0..4 codes (N -> 0 + run list)
