@@ -730,7 +730,7 @@ struct Slot {
 static Slot g_slots[16];
 static thread_local Slot *tl_slot = &g_slots[0];
 
-static int g_force_kernel = 0;  // test hook: 0 auto, 1 single-wave LDS kernel, 3 workgroup kernel, 4 strip (else band), 5 band
+static int g_force_kernel = 0;  // test hook: 0 auto, 1 workgroup kernel with one wave, 3 with 256+ threads, 4 strip (else band), 5 band, 6 tiled
 
 static void parallel_chunks(int64_t n, int n_threads, const std::function<void(int64_t, int64_t, int)> &fn, int tag = 0) {
     if (n_threads <= 1 || n < 8192) { fn(0, n, 0); return; }
@@ -884,7 +884,7 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     g_stats[58] += T.xstrip_cells;
     g_stats[64] += cnt[L_TILE];   // windows on the tiled strips (none under MPN_TILED=0)
     if (getenv("MPN_DEBUG_JOBS")) {
-        static const char *const fam[] = {"lds", "wg", "strip", "band"};
+        static const char *const fam[] = {"wg64", "wg", "strip", "band"};
         for (int l = 0; l < N_LISTS; ++l)
             if (cnt[l]) fprintf(stderr, "[jobs] %s list %-2d n=%d\n", fam[l < L_WG ? 0 : l < L_STRIP ? 1 : l < L_BAND ? 2 : 3], l, cnt[l]);
     }
@@ -930,21 +930,16 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     // one launch of launch list `l` over ord[0..n)
     auto launch_list = [&](int l, const int32_t *ord, int n, hipStream_t s) -> int {
         if (n == 0) return 0;
-        if (l < L_WG) {
-            const size_t lds = std::max<size_t>((size_t)T.lds_need[l - L_LDS], 64);
-            if (lds > 64 * 1024) MPN_HIP_CHECK(hipFuncSetAttribute((const void *)ext_dp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(ext_dp_kernel, dim3(n), dim3(64), lds, s, d_jobs.p, ord, n, prm, d_reads, d_read_off, d_read_len, rv, P.p, OFF.p,
-                               gstate.p, d_res.p);
-        } else if (l < L_STRIP) {
-            const int ntc = (l - L_WG) / 5;
-            const size_t lds = std::max<size_t>((size_t)T.lds_need[(l - L_WG) % 5], 64);
+        if (l < L_STRIP) {   // width class (l - L_LDS) / 5: 64, 256, 512 or 1024 threads; LDS class (l - L_LDS) % 5
+            const int ntc = (l - L_LDS) / 5;
+            const size_t lds = std::max<size_t>((size_t)T.lds_need[(l - L_LDS) % 5], 64);
 #define MPN_WG_LAUNCH(NT)                                                                                                             \
             do {                                                                                                                      \
                 if (lds > 64 * 1024) MPN_HIP_CHECK(hipFuncSetAttribute((const void *)ext_dp_wg_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
                 hipLaunchKernelGGL(ext_dp_wg_kernel<NT>, dim3(n), dim3(NT), lds, s, d_jobs.p, ord, n, prm, d_reads, d_read_off, d_read_len, \
                                    rv, P.p, OFF.p, gstate.p, d_res.p);                                                                \
             } while (0)
-            if (ntc == 0) MPN_WG_LAUNCH(256); else if (ntc == 1) MPN_WG_LAUNCH(512); else MPN_WG_LAUNCH(1024);
+            if (ntc == 0) MPN_WG_LAUNCH(64); else if (ntc == 1) MPN_WG_LAUNCH(256); else if (ntc == 2) MPN_WG_LAUNCH(512); else MPN_WG_LAUNCH(1024);
 #undef MPN_WG_LAUNCH
         } else if (l < L_BAND) {  // called once per variant family (l = its first list): all its lane-group classes in ONE launch
             const int fam = (l - L_STRIP) / 48;   // 0: gap fills (approximate maximum); 1: exact (left- and right-aligned gaps)
@@ -953,16 +948,15 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
             int blocks = 0;
             size_t lds = 0;
             const int c_lo = fam == 0 ? 0 : 3, c_hi = fam == 0 ? 3 : N_STRIP_CLASS;
-            const int pair = fam == 0 ? 1 : 0;   // gap fills: two windows per lane group (ext_strip_pair)
             for (int glc = 2; glc >= 0; --glc)   // wide lane groups (the long windows) first
                 for (int sclass = c_lo + glc; sclass < c_hi; sclass += 3) {
-                    const int l0 = L_STRIP + 16 * sclass, nl = base[l0 + 16] - base[l0], per = (pair ? 8 : 4) >> glc;
+                    const int l0 = L_STRIP + 16 * sclass, nl = base[l0 + 16] - base[l0], per = strip_windows_per_wave(l0);
                     if (nl == 0) continue;
                     const int stride = (std::max(T.strip_lds[sclass], 16) + 3) & ~3;
                     // exact variants: a slot per anti-diagonal and the E4 table per window (+ 16: the rows that pad the last strip)
                     const int nr_stride = fam ? T.strip_nr[sclass] + 16 : 0;
                     lds = std::max(lds, (size_t)stride * per + STRIP_TAB_BYTES + (size_t)per * 8 * nr_stride);
-                    segs.s[segs.n++] = StripSeg{blocks, nl, base[l0], stride, nr_stride, glc, sclass >= 6 ? 1 : 0, pair};
+                    segs.s[segs.n++] = StripSeg{blocks, nl, base[l0], stride, nr_stride, glc, sclass >= 6 ? 1 : 0};
                     blocks += nl / per;
                 }
             if (blocks == 0) return 0;

@@ -5,8 +5,8 @@
 //                             all state in VGPRs, 1 B/cell of direction codes in a step-major matrix
 //   ext_dp_band_kernel<NW,T>  every other window whose band fits 1024 slots (end extensions with exact max + z-drop,
 //                             clipped fills, the exact second pass): band in registers, one barrier per anti-diagonal
-//   ext_dp_kernel, ext_dp_wg_kernel<NT>   fallbacks (wider bands, windows beyond LDS): Suzuki-Kasahara states u,v,x,y,x2,y2
-//                             and the H row in LDS or global scratch, one wave or one workgroup per window
+//   ext_dp_wg_kernel<NT>      fallback (wider bands, windows beyond LDS): Suzuki-Kasahara states u,v,x,y,x2,y2 and the
+//                             H row in LDS or global scratch, one workgroup of 64 (one wave), 256, 512 or 1024 threads per window
 //   ext_bt_kernel, ext_ztest_kernel        one LANE per window: traceback is a serial pointer chase, the z-drop test a CIGAR walk
 #pragma once
 #include "mpn_common.h"
@@ -73,177 +73,9 @@ __device__ __forceinline__ bool ext_apply_zdrop(ExtApply &ez, int32_t H, int r, 
     return false;
 }
 
-__global__ __launch_bounds__(64) void ext_dp_kernel(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, int n_jobs,
-                                                    ExtParams prm, const uint8_t *__restrict__ reads,
-                                                    const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
-                                                    RefView rv,
-                                                    uint8_t *__restrict__ P, int32_t *__restrict__ OFF, int8_t *__restrict__ gstate,
-                                                    ExtRes *__restrict__ res) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int lane = threadIdx.x;
-    const int jid = order[blockIdx.x];
-    const ExtJob jb = jobs[jid];
-    const int qlen = jb.qlen, tlen = jb.tlen;
-    int q = prm.q, e = prm.e, q2 = prm.q2, e2 = prm.e2;
-    if (q2 + e2 < q + e) { int t_ = q; q = q2; q2 = t_; t_ = e; e = e2; e2 = t_; }
-    const int qe = q + e, qe2 = q2 + e2;
-    ExtRes out;
-    out.max = 0; out.zdropped = 0; out.max_q = out.max_t = out.mqe_t = -1; out.mqe = NEG_INF; out.score = NEG_INF;
-    out.reach_end = 0; out.n_cigar = 0; out.r_done = -1; out.bt_i = out.bt_j = -1; out.do_bt = 0; out.zcode = 0;
-    if (qlen <= 0 || tlen <= 0 || -prm.sc_mis > 2 * (q + e)) { if (lane == 0) res[jid] = out; return; }
-    int w = jb.w;
-    if (w < 0) w = tlen > qlen ? tlen : qlen;
-    const int n_col = jb.n_col;
-    // LDS carve: qseq[qlen] tseq[tlen] (padded to 4) then state
-    uint8_t *qs_ = smem;
-    uint8_t *ts_ = smem + ((qlen + 3) & ~3);
-    int8_t *sbase = jb.state_mode ? gstate + jb.state_off : (int8_t *)(ts_ + ((tlen + 3) & ~3));
-    int8_t *u = sbase, *v = u + tlen, *x = v + tlen, *y = x + tlen, *x2 = y + tlen, *y2 = x2 + tlen;
-    int32_t *H = (int32_t *)(sbase + (((size_t)6 * tlen + 3) & ~(size_t)3));
-    const bool approx = (jb.flag & EZ_APPROX_MAX) != 0;
-    {
-        const int64_t roff = read_off[jb.read];
-        const int32_t rlen = read_len[jb.read];
-        for (int i = lane; i < qlen; i += 64) qs_[i] = ext_qbase(reads, roff, rlen, jb.rev, jb.qs + (jb.reversed ? qlen - 1 - i : i));
-        const int64_t g0 = rv.seq_off[jb.rid] + jb.ts;
-        for (int i = lane; i < tlen; i += 64) ts_[i] = (uint8_t)ref_code(rv, g0 + (jb.reversed ? tlen - 1 - i : i));
-        for (int i = lane; i < tlen; i += 64) {
-            u[i] = v[i] = x[i] = y[i] = (int8_t)-qe;
-            x2[i] = y2[i] = (int8_t)-qe2;
-            if (!approx) H[i] = NEG_INF;
-        }
-    }
-    __syncthreads();
-    int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-    if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-    const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
-    uint8_t *p = P + jb.p_off;
-    const int n_r = qlen + tlen - 1;
-    int32_t *off = OFF + 2 * jb.row_off;  // [r] band start, [n_r + r] band end
-    int32_t *off_end = off + n_r;
-    ExtApply ez; ez.max = 0; ez.max_t = ez.max_q = -1; ez.zdropped = 0;
-    int32_t mqe = NEG_INF, mqe_t = -1, score = NEG_INF, H0 = 0, last_H0_t = 0;
-    int last_st = -1, last_en = -1, r;
-    const bool right = (jb.flag & EZ_RIGHT) != 0;
-    for (r = 0; r < n_r; ++r) {
-        int st = 0, en = tlen - 1;
-        if (st < r - qlen + 1) st = r - qlen + 1;
-        if (en > r) en = r;
-        if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
-        if (en > (r + w) >> 1) en = (r + w) >> 1;
-        if (st > en) { ez.zdropped = 1; break; }
-        int cx1, cx21, cv1;
-        if (st > 0) {
-            if (st - 1 >= last_st && st - 1 <= last_en) { cx1 = x[st - 1]; cx21 = x2[st - 1]; cv1 = v[st - 1]; }
-            else { cx1 = -qe; cx21 = -qe2; cv1 = -qe; }
-        } else {
-            cx1 = -qe; cx21 = -qe2;
-            cv1 = r == 0 ? -qe : r < long_thres ? -e : r == long_thres ? long_diff : -e2;
-        }
-        if (en >= r) {
-            if (lane == 0) {
-                y[r] = (int8_t)-qe; y2[r] = (int8_t)-qe2;
-                u[r] = (int8_t)(r == 0 ? -qe : r < long_thres ? -e : r == long_thres ? long_diff : -e2);
-            }
-            __syncthreads();
-        }
-        if (lane == 0) { off[r] = st; off_end[r] = en; }
-        uint8_t *pr = p + (int64_t)r * n_col;
-        // exact-max bookkeeping needs OLD H[en-1]
-        int32_t Hen_new = 0;
-        if (!approx && r > 0) Hen_new = en > 0 ? H[en - 1] : H[en];
-        int32_t bestH = NEG_INF, bestKey = 0x7fffffff;
-        const int en1 = st + (en - st) / 4 * 4;
-        for (int c0 = st; c0 <= en; c0 += 64) {
-            const int t = c0 + lane;
-            const bool act = t <= en;
-            int ut = 0, vt = 0, xt = 0, x2t = 0, yt = 0, y2t = 0, sc = 0;
-            if (act) {
-                ut = u[t]; vt = v[t]; xt = x[t]; x2t = x2[t]; yt = y[t]; y2t = y2[t];
-                const int sq = ts_[t], sr = qs_[r - t];
-                sc = (sq == 4 || sr == 4) ? prm.sc_n : sq == sr ? prm.sc_mch : prm.sc_mis;
-            }
-            const int v1 = wave_shr1(vt, cv1), x1 = wave_shr1(xt, cx1), x21 = wave_shr1(x2t, cx21);
-            cv1 = __builtin_amdgcn_readlane(vt, 63); cx1 = __builtin_amdgcn_readlane(xt, 63); cx21 = __builtin_amdgcn_readlane(x2t, 63);
-            int z = sc, a = x1 + v1, b = yt + ut, a2 = x21 + v1, b2 = y2t + ut, d;
-            if (!right) {
-                d = a > z ? 1 : 0; z = max(z, a);
-                d = b > z ? 2 : d; z = max(z, b);
-                d = a2 > z ? 3 : d; z = max(z, a2);
-                d = b2 > z ? 4 : d; z = max(z, b2);
-            } else {
-                d = z > a ? 0 : 1; z = max(z, a);
-                d = z > b ? d : 2; z = max(z, b);
-                d = z > a2 ? d : 3; z = max(z, a2);
-                d = z > b2 ? d : 4; z = max(z, b2);
-            }
-            z = min(z, (int)prm.sc_mch);
-            const int nu = z - v1, nv = z - ut;
-            int tmp = z - q; a -= tmp; b -= tmp;
-            tmp = z - q2; a2 -= tmp; b2 -= tmp;
-            if (!right) {
-                d |= a > 0 ? 0x08 : 0; d |= b > 0 ? 0x10 : 0; d |= a2 > 0 ? 0x20 : 0; d |= b2 > 0 ? 0x40 : 0;
-            } else {
-                d |= a >= 0 ? 0x08 : 0; d |= b >= 0 ? 0x10 : 0; d |= a2 >= 0 ? 0x20 : 0; d |= b2 >= 0 ? 0x40 : 0;
-            }
-            if (act) {
-                u[t] = (int8_t)nu; v[t] = (int8_t)nv;
-                x[t] = (int8_t)(max(a, 0) - qe); y[t] = (int8_t)(max(b, 0) - qe);
-                x2[t] = (int8_t)(max(a2, 0) - qe2); y2[t] = (int8_t)(max(b2, 0) - qe2);
-                pr[t - st] = (uint8_t)d;
-                if (!approx && r > 0 && t < en) {
-                    const int32_t h = H[t] + nv;
-                    H[t] = h;
-                    const int key = (t < en1 ? 1 + ((t - st) & 3) : 5) << 24 | t;
-                    if (h > bestH || (h == bestH && key < bestKey)) { bestH = h; bestKey = key; }
-                }
-            }
-        }
-        __syncthreads();
-        if (!approx) {
-            int32_t max_H, max_t;
-            if (r > 0) {
-                const int32_t hen = Hen_new + (en > 0 ? (int)u[en] : (int)v[en]);
-                if (lane == 0) H[en] = hen;
-                // en wins every tie; then (t-st)&3 class order for t < en1; then the tail
-                const int32_t m = wave_reduce_max(bestH);
-                int kk = (bestH == m && m > NEG_INF) ? bestKey : 0x7fffffff;
-                kk = wave_reduce_min(kk);
-                if (m > hen) { max_H = m; max_t = kk & 0xffffff; }
-                else { max_H = hen; max_t = en; }
-            } else {
-                const int32_t h0 = (int)v[0] - qe;
-                if (lane == 0) H[0] = h0;
-                max_H = h0; max_t = 0;
-            }
-            __syncthreads();
-            if (r - st == qlen - 1) { const int32_t hs = H[st]; if (hs > mqe) { mqe = hs; mqe_t = st; } }
-            if (ext_apply_zdrop(ez, max_H, r, max_t, jb.zdrop, e2)) break;
-            if (r == n_r - 1 && en == tlen - 1) score = H[tlen - 1];
-        } else {
-            if (r > 0) {
-                if (last_H0_t >= st && last_H0_t <= en && last_H0_t + 1 >= st && last_H0_t + 1 <= en) {
-                    const int32_t d0 = v[last_H0_t], d1 = u[last_H0_t + 1];
-                    if (d0 > d1) H0 += d0; else { H0 += d1; ++last_H0_t; }
-                } else if (last_H0_t >= st && last_H0_t <= en) H0 += v[last_H0_t];
-                else { ++last_H0_t; H0 += u[last_H0_t]; }
-            } else { H0 = (int)v[0] - qe; last_H0_t = 0; }
-            if (r == n_r - 1 && en == tlen - 1) score = H0;
-        }
-        last_st = st; last_en = en;
-    }
-    out.max = ez.max; out.max_t = ez.max_t; out.max_q = ez.max_q; out.zdropped = ez.zdropped;
-    out.mqe = mqe; out.mqe_t = mqe_t; out.score = score;
-    out.r_done = r < n_r ? r : n_r - 1;
-    if (!ez.zdropped && !(jb.flag & EZ_EXTZ_ONLY)) { out.do_bt = 1; out.bt_i = tlen - 1; out.bt_j = qlen - 1; }
-    else if (!ez.zdropped && (jb.flag & EZ_EXTZ_ONLY) && mqe + jb.end_bonus > ez.max) { out.reach_end = 1; out.do_bt = 1; out.bt_i = mqe_t; out.bt_j = qlen - 1; }
-    else if (ez.max_t >= 0 && ez.max_q >= 0) { out.do_bt = 1; out.bt_i = ez.max_t; out.bt_j = ez.max_q; }
-    if (lane == 0) res[jid] = out;
-}
-
-// Workgroup-per-window variant for windows the band kernel below cannot take (band wider than 1024 cells, or
-// sequences that do not fit LDS): the band of one anti-diagonal is spread over NT threads instead of being walked by one
-// wave tile after tile.  States live in LDS (or the
+// Workgroup-per-window kernel for windows the band kernel below cannot take (band wider than 1024 cells, or
+// sequences that do not fit LDS): the band of one anti-diagonal is walked in tiles of NT = 64 (one wave), 256, 512 or 1024
+// cells, one per thread.  States live in LDS (or the
 // global scratch for huge windows).  Tiles are processed from the highest target position down: a tile reads its own
 // cells and its left neighbour (t-1, old values), a barrier follows, then it writes; lower tiles are still untouched.
 template <int NT>
@@ -632,8 +464,9 @@ __global__ __launch_bounds__(NW * 64) void ext_dp_band_kernel(const ExtJob *__re
     else ext_dp_band_body<NW, T, false>(jb, jid, prm, reads, read_off, read_len, rv, P, res, smem, bnd, red, pub);
 }
 
-// Systolic strip variant for gap-fill windows whose band never clips (w >= max(qlen, tlen), tlen <= 1024, gaps
-// left-aligned).  A window runs on a group of GL = 16, 32 or 64 lanes (see ext_dp_strip_kernel below): lane l owns the S consecutive target rows t = l*S .. l*S+S-1 and walks the query columns j = step - l,
+// Systolic strip cells for windows whose band never clips (w >= max(qlen, tlen), tlen <= 1024): the gap fills (left-aligned
+// gaps) two windows per lane group (ext_strip_pair), the end extensions and exact fills one (ext_strip_exact).
+// A window runs on a group of GL = 16, 32 or 64 lanes (see ext_dp_strip_kernel below): lane l owns the S consecutive target rows t = l*S .. l*S+S-1 and walks the query columns j = step - l,
 // so after a ramp of n_lanes-1 steps every lane computes S cells per step -- no partially filled anti-diagonal tiles.
 // The left neighbour (t, j-1) of a cell is the lane's own previous step (u, y, y2 kept per row in VGPRs), the upper
 // neighbour (t-1, j) is the previous row of the same step or, for the first row of a strip, the bottom row lane l-1
@@ -647,8 +480,8 @@ __global__ __launch_bounds__(NW * 64) void ext_dp_band_kernel(const ExtJob *__re
 //  * the direction is "first operand that equals the maximum": the states are pre-scaled by 8 and the candidates carry their rank in
 //    the low bits, so one max gives value and direction (stored as the rank, decoded by the traceback); the continuation flags come
 //    from the new gap states;
-//  * the corner score is summed along row 0 and then down the last column, which costs one add per step.
-// Same recurrences, boundary rules and direction codes as ext_dp_kernel.  Directions are stored step-major: cell
+//  * the corner score of a gap fill is summed along row 0 and then down the last column, which costs one add per step.
+// Same recurrences, boundary rules and direction codes as ext_dp_wg_kernel.  Directions are stored step-major: cell
 // (t, j) lives at [j + t/S][t], so the S bytes a lane produces in one step are contiguous and the whole wave writes one
 // contiguous row of n_lanes*S bytes per step (row-major dword stores cost 7x their bytes in HBM writes, measured).
 __host__ __device__ inline bool ext_strip_scores_ok(int mch, int mis, int amb, int qe, int qe2) {
@@ -656,16 +489,16 @@ __host__ __device__ inline bool ext_strip_scores_ok(int mch, int mis, int amb, i
     return mch >= -16 && mch <= 15 && mis >= -16 && mis <= 15 && amb >= -16 && amb <= 15 && qe >= 0 && qe <= 127 && qe2 >= 0 && qe2 <= 127;
 }
 constexpr int STRIP_TAB_BYTES = 32;   // the query score words, behind the groups' queries in LDS
-// EXACT windows (end extensions, exact global fills): is 8 H + 32768 a 16-bit number for every cell (see the H bookkeeping in
-// ext_strip_pack)?  -(gap of t+1) - (gap of j+1) <= H(t, j) <= match * min(t+1, j+1); the tie-break key holds t in 10 bits.
+// Exact windows (end extensions, exact global fills): is 8 H + 32768 a 16-bit number for every cell (see the H bookkeeping in
+// ext_strip_exact)?  -(gap of t+1) - (gap of j+1) <= H(t, j) <= match * min(t+1, j+1); the tie-break key holds t in 10 bits.
 __host__ __device__ inline bool ext_strip_exact_ok(int mch, int q, int e, int q2, int e2, int qlen, int tlen) {
     const int L = (qlen > tlen ? qlen : tlen) + 1;
     const int c1 = q + e * L, c2 = q2 + e2 * L;
     return tlen <= 1024 && 16 * (c1 < c2 ? c1 : c2) < 32000 && 8 * mch * L < 32000;
 }
 
-// EXACT = the ksw2 "exact" bookkeeping of the end extensions (and exact global fills): the maximum of every anti-diagonal with
-// ksw2's tie order, the z-drop rule over the anti-diagonals in order, the best score of the last query column.  The systolic
+// One window per lane group with the ksw2 "exact" bookkeeping of the end extensions (and exact global fills): the maximum
+// of every anti-diagonal with ksw2's tie order, the z-drop rule over the anti-diagonals in order, the best score of the last query column.  The systolic
 // array does not visit the cells in anti-diagonal order, so the rule is applied AFTER the matrix is done:
 //  * every cell carries its H (one packed add of the horizontal difference per cell; H(t, -1) is the closed form of the
 //    first-column boundary) and merges (H, tie-break key) into its anti-diagonal's slot in LDS with one ds_max_u32: the word is
@@ -677,12 +510,12 @@ __host__ __device__ inline bool ext_strip_exact_ok(int mch, int q, int e, int q2
 // RIGHT = right-aligned gaps (KSW_EZ_RIGHT, the left extension): the later operand wins a tie -- the ranks of the five
 // candidates are reversed (the traceback reads the operand index as the rank itself) -- and a gap continues when its state
 // is >= 0, not > 0: the new gap state is computed one unit (8) high, flagged, and brought down by a second saturating subtract.
-template <int S, int GL, bool EXACT, bool RIGHT>
-__device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, const int first,
-                                               const int n_list, const ExtParams &prm, const uint8_t *__restrict__ reads,
-                                               const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
-                                               const RefView &rv, uint8_t *__restrict__ P, ExtRes *__restrict__ res, uint8_t *smem,
-                                               const int lds_stride, const int nr_stride) {
+template <int S, int GL, bool RIGHT>
+__device__ __forceinline__ void ext_strip_exact(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, const int first,
+                                                const int n_list, const ExtParams &prm, const uint8_t *__restrict__ reads,
+                                                const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
+                                                const RefView &rv, uint8_t *__restrict__ P, ExtRes *__restrict__ res, uint8_t *smem,
+                                                const int lds_stride, const int nr_stride) {
     constexpr int NG = 64 / GL;  // windows per wave: each takes a group of GL lanes
     const int lane = threadIdx.x, g = lane / GL, gl = lane % GL;
     const int jid = first + g < n_list ? order[first + g] : -1;  // -1: padding at the end of a launch list
@@ -751,7 +584,7 @@ __device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, 
     const uint32_t CV = pk(cv_lo, cv_hi), CU = pk(cu_lo, cu_hi);
     uint32_t UL[S], YL[S];
     uint32_t TSEL[S];
-    uint32_t Hh[EXACT ? S : 1];   // EXACT: low half = 8 H(t, j) + (j + 1) CV.lo of the lane's current column (mod 2^16)
+    uint32_t Hh[S];   // low half = 8 H(t, j) + (j + 1) CV.lo of the lane's current column (mod 2^16)
     const int64_t g0 = ok ? rv.seq_off[rid] + ts : 0;
     const int t0 = gl * S;
     const uint32_t KONST = sb_n | 0x2000u;   // byte 0: the score against an ambiguous target base; byte 1: the high byte of every score
@@ -762,19 +595,16 @@ __device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, 
         TSEL[k] = 0x0c0c0100u | (sq < 4 ? 4u + (uint32_t)sq : 0u);   // v_perm(QT, KONST): byte 0 = QT[sq] or KONST[0], byte 1 = KONST[1]
         UL[k] = pk(MPN_BND(t), MPN_BND(t)) + CU;   // left of column 0: the first-column boundary (u of anti-diagonal r = t)
         YL[k] = 0;
-        if constexpr (EXACT) {
-            // H(t, -1): the sum of the boundary differences above
-            const int h = t < long_thres ? -(q + e * (t + 1)) : -(q2 + e2 * (t + 1));
-            Hh[k] = (uint32_t)(8 * h) & 0xffffu;
-        }
+        // H(t, -1): the sum of the boundary differences above
+        const int h = t < long_thres ? -(q + e * (t + 1)) : -(q2 + e2 * (t + 1));
+        Hh[k] = (uint32_t)(8 * h) & 0xffffu;
     }
-    // EXACT: per group, a slot per anti-diagonal (BEST) and the table E4[r] = (cells of anti-diagonal r - 1) & ~3, the part of the
+    // per group, a slot per anti-diagonal (BEST) and the table E4[r] = (cells of anti-diagonal r - 1) & ~3, the part of the
     // band ksw2 covers with whole 4-lane vectors; E4's space holds the last query column afterwards
-    uint32_t *BEST = nullptr, *E4T = nullptr;
+    uint32_t *const BEST = reinterpret_cast<uint32_t *>(smem + NG * lds_stride + STRIP_TAB_BYTES) + (size_t)g * 2 * nr_stride;
+    uint32_t *const E4T = BEST + nr_stride;
     const int n_r = ok ? qlen + tlen - 1 : 0;
-    if constexpr (EXACT) {
-        BEST = reinterpret_cast<uint32_t *>(smem + NG * lds_stride + STRIP_TAB_BYTES) + (size_t)g * 2 * nr_stride;
-        E4T = BEST + nr_stride;
+    {
         const int mn = (qlen < tlen ? qlen : tlen) - 1;
         for (int r = gl; r < nr_stride; r += GL) {
             const int c = min(min(r, n_r - 1 - r), mn);
@@ -789,7 +619,6 @@ __device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, 
     uint8_t *prow = P + p_off + t0;
     int out_v = 0, out_x = 0;
     uint32_t qt = 0;   // the score word of the query base this lane works on
-    int32_t row0 = 0;  // first lane of a group: sum of the horizontal differences of row 0
     // z + CU + CV (what the new u and v are subtracted from), and z + e + the offset of the candidate a gap state comes from
     // (right-aligned gaps: one unit lower, so that the flag sees state >= 0)
     constexpr int RU = RIGHT ? 8 : 0;
@@ -817,12 +646,11 @@ __device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, 
         uint32_t Vp = head ? pk(bj, bj) + CV : (uint32_t)v_s, Xp = head ? 0u : (uint32_t)x_s;
         if (j >= 0 && j < qlen && gl < n_lanes) {
             uint32_t dw[(S + 3) / 4], ecell[4] = {0, 0, 0, 0};
-            int nv0 = 0;
-            // EXACT: what turns a lane's H register into 8 H + 32768 in this column, t - st of the rows below the query's end,
+            // what turns a lane's H register into 8 H + 32768 in this column, t - st of the rows below the query's end,
             // the anti-diagonal slots of the lane's first row
             const uint32_t offj = (uint32_t)((j + 1) * cv_lo - 32768);
             const int qm1j = qlen - 1 - j;
-            uint32_t *bslot = EXACT ? BEST + (t0 + j) : nullptr;
+            uint32_t *bslot = BEST + (t0 + j);
 #pragma unroll
             for (int k = 0; k < S; ++k) {
                 const uint32_t sc16 = __builtin_amdgcn_perm(qt, KONST, TSEL[k]);   // 8 s + rank + BETA in the low half
@@ -865,14 +693,12 @@ __device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, 
                 asm("v_and_or_b32 %0, %1, 7, %2" : "=v"(ecell[k & 3]) : "v"(z16), "v"(Fw));
                 UL[k] = nu; YL[k] = __builtin_bit_cast(uint32_t, Bn);
                 Vp = nv; Xp = __builtin_bit_cast(uint32_t, An);
-                if constexpr (EXACT) {
-                    Hh[k] += nv;
-                    const uint32_t hb = (Hh[k] - offj) & 0xffffu;            // 8 H(t, j) + 32768
-                    const int t = t0 + k, m = min(t, qm1j);                  // m = t - (first cell of the anti-diagonal)
-                    uint32_t inv = (m < (int)E4T[t0 + j + k] ? ~((uint32_t)m << 10) & 0xc00u : (uint32_t)-1024) + (uint32_t)(4095 - t);
-                    inv = (j == 0 || t == tlm1) ? 8191u : inv;                // the band's last cell
-                    atomicMax(bslot + k, t <= tlm1 ? hb * 1024u + inv : 0u);  // (0: a row that pads the last strip)
-                }
+                Hh[k] += nv;
+                const uint32_t hb = (Hh[k] - offj) & 0xffffu;            // 8 H(t, j) + 32768
+                const int t = t0 + k, m = min(t, qm1j);                  // m = t - (first cell of the anti-diagonal)
+                uint32_t inv = (m < (int)E4T[t0 + j + k] ? ~((uint32_t)m << 10) & 0xc00u : (uint32_t)-1024) + (uint32_t)(4095 - t);
+                inv = (j == 0 || t == tlm1) ? 8191u : inv;                // the band's last cell
+                atomicMax(bslot + k, t <= tlm1 ? hb * 1024u + inv : 0u);  // (0: a row that pads the last strip)
                 if ((k & 3) == 3 || k == S - 1) {
                     // bytes 0 (rank, a, b) and bytes 2 (a2, b2) of up to four cells -> one word each, then hi << 2 joins lo
                     uint32_t e01 = ecell[0], e23 = (k & 3) >= 2 ? ecell[2] : 0u;
@@ -881,10 +707,8 @@ __device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, 
                     const uint32_t lo = __builtin_amdgcn_perm(e23, e01, 0x05040100u), hi = __builtin_amdgcn_perm(e23, e01, 0x07060302u);
                     asm("v_lshl_or_b32 %0, %1, 2, %2" : "=v"(dw[k >> 2]) : "v"(hi), "v"(lo));
                 }
-                if (k == 0) nv0 = (int)(nv & 0xffffu);
             }
             out_v = (int)Vp; out_x = (int)Xp;
-            row0 += nv0 - cv_lo;
             uint8_t *dst = prow + (int64_t)step * W;  // p_off is 16-aligned, W and t0 are multiples of S
             if constexpr (S == 4) *reinterpret_cast<uint32_t *>(dst) = dw[0];
             else if constexpr (S == 8) *reinterpret_cast<uint2 *>(dst) = make_uint2(dw[0], dw[1]);
@@ -898,95 +722,77 @@ __device__ __forceinline__ void ext_strip_pack(const ExtJob *__restrict__ jobs, 
         }
     }
 #undef MPN_BND
-    if constexpr (!EXACT) {
-        // H(tlen-1, qlen-1) = H(0,-1) + sum_j v(0,j) + sum_{t>0} u(t, qlen-1); a lane's UL froze at its last column
-        // (the sums are of pre-scaled differences, exact multiples of 8)
-        int32_t tot = head ? row0 - 8 * qe : 0;
+    // ---- the z-drop rule over the anti-diagonals, in order ----
+    __syncthreads();   // every slot has its maximum
+    // the last query column: a lane's H registers froze there.  HL[t] = H(t, qlen - 1) + 4096, over the E4 table
+    uint32_t *HL = E4T;
+    {
+        const uint32_t offl = (uint32_t)(qlen * cv_lo - 32768);
 #pragma unroll
-        for (int k = 0; k < S; ++k) tot += (t0 + k > 0 && t0 + k < tlen) ? (int)(UL[k] & 0xffffu) - cu_lo : 0;
+        for (int k = 0; k < S; ++k) if (t0 + k < tlen) HL[t0 + k] = ((Hh[k] - offl) & 0xffffu) >> 3;
+    }
+    __syncthreads();
+    struct Best { int m, t, r; };   // a maximum, its target position and its anti-diagonal (its place in walking order)
+    // first strict maximum in walking order over the lanes of the group: inclusive scan, the later lane wins only when greater
+    auto scan_first_max = [&](Best x) {
 #pragma unroll
-        for (int dlt = GL / 2; dlt; dlt >>= 1) tot += __shfl_xor(tot, dlt);
-        tot >>= 3;
-        if (head && jid >= 0) {
-            ExtRes out;
-            out.max = 0; out.zdropped = 0; out.max_q = out.max_t = out.mqe_t = -1; out.mqe = NEG_INF; out.score = ok ? tot : NEG_INF;
-            out.reach_end = 0; out.n_cigar = 0; out.r_done = ok ? qlen + tlen - 2 : -1; out.zcode = 0; out.cig_pos = 0;
-            out.do_bt = ok ? 1 : 0; out.bt_i = ok ? tlen - 1 : -1; out.bt_j = ok ? qlen - 1 : -1;
-            res[jid] = out;
+        for (int d = 1; d < GL; d <<= 1) {
+            const Best o{__shfl_up(x.m, d, GL), __shfl_up(x.t, d, GL), __shfl_up(x.r, d, GL)};
+            if (gl >= d && !(x.m > o.m)) x = o;
         }
-    } else {
-        // ---- the z-drop rule over the anti-diagonals, in order ----
-        __syncthreads();   // every slot has its maximum
-        // the last query column: a lane's H registers froze there.  HL[t] = H(t, qlen - 1) + 4096, over the E4 table
-        uint32_t *HL = E4T;
-        {
-            const uint32_t offl = (uint32_t)(qlen * cv_lo - 32768);
+        return x;
+    };
+    auto diag = [&](int r, int &H, int &mt) {
+        const uint32_t pv = BEST[r];
+        const uint32_t inv = pv & 8191u;
+        H = (int)(pv >> 13) - 4096;
+        mt = inv == 8191u ? min(tlm1, r) : (int)((8191u - inv) & 1023u);
+    };
+    const int C = (n_r + GL - 1) / GL, rlo = min(n_r, gl * C), rhi = min(n_r, rlo + C);
+    // (1) the running maximum that enters every lane's chunk
+    auto chunk_best = [&](int lim) {
+        Best b{NEG_INF, -1, -1};
+        for (int r = rlo; r < rhi && r <= lim; ++r) { int H, mt; diag(r, H, mt); if (H > b.m) b = Best{H, mt, r}; }
+        return b;
+    };
+    Best incl = scan_first_max(chunk_best(n_r));
+    Best in{__shfl_up(incl.m, 1, GL), __shfl_up(incl.t, 1, GL), __shfl_up(incl.r, 1, GL)};
+    ExtApply ez; ez.max = 0; ez.max_t = ez.max_q = -1; ez.zdropped = 0;
+    if (gl > 0 && in.m > 0) { ez.max = in.m; ez.max_t = in.t; ez.max_q = in.r - in.t; }
+    // (2) the first anti-diagonal that z-drops
+    int r_break = n_r;
+    for (int r = rlo; r < rhi; ++r) {
+        int H, mt; diag(r, H, mt);
+        if (ext_apply_zdrop(ez, H, r, mt, zdrop, e2)) { r_break = r; break; }
+    }
 #pragma unroll
-            for (int k = 0; k < S; ++k) if (t0 + k < tlen) HL[t0 + k] = ((Hh[k] - offl) & 0xffffu) >> 3;
+    for (int dlt = GL / 2; dlt; dlt >>= 1) r_break = min(r_break, __shfl_xor(r_break, dlt));
+    const bool dropped = r_break < n_r;
+    // (3) the state when the walk stops: maximum over the anti-diagonals up to there, best cell of the last query column
+    // (H(st, qlen - 1) of the anti-diagonals qlen - 1 .. r_break: target positions 0 .. r_break - qlen + 1)
+    Best fin = scan_first_max(chunk_best(r_break));
+    fin = Best{__shfl(fin.m, GL - 1, GL), __shfl(fin.t, GL - 1, GL), __shfl(fin.r, GL - 1, GL)};
+    const int t_lim = min(tlm1, r_break - (qlen - 1));
+    const int Ct = (tlen + GL - 1) / GL, tlo = min(tlen, gl * Ct), thi = min(tlen, tlo + Ct);
+    Best me{NEG_INF, -1, -1};
+    for (int t = tlo; t < thi && t <= t_lim; ++t) { const int h = (int)HL[t] - 4096; if (h > me.m) me = Best{h, t, t}; }
+    me = scan_first_max(me);
+    me = Best{__shfl(me.m, GL - 1, GL), __shfl(me.t, GL - 1, GL), 0};
+    if (head && jid >= 0) {
+        ExtRes out;
+        out.max = 0; out.zdropped = 0; out.max_q = out.max_t = out.mqe_t = -1; out.mqe = NEG_INF; out.score = NEG_INF;
+        out.reach_end = 0; out.n_cigar = 0; out.r_done = -1; out.bt_i = out.bt_j = -1; out.do_bt = 0; out.zcode = 0; out.cig_pos = 0;
+        if (ok) {
+            if (fin.m > 0) { out.max = fin.m; out.max_t = fin.t; out.max_q = fin.r - fin.t; }
+            out.zdropped = dropped ? 1 : 0;
+            if (me.m > NEG_INF) { out.mqe = me.m; out.mqe_t = me.t; }
+            if (!dropped) out.score = (int)HL[tlm1] - 4096;
+            out.r_done = dropped ? r_break : n_r - 1;
+            if (!dropped && !(jflag & EZ_EXTZ_ONLY)) { out.do_bt = 1; out.bt_i = tlen - 1; out.bt_j = qlen - 1; }
+            else if (!dropped && (jflag & EZ_EXTZ_ONLY) && out.mqe + end_bonus > out.max) { out.reach_end = 1; out.do_bt = 1; out.bt_i = out.mqe_t; out.bt_j = qlen - 1; }
+            else if (out.max_t >= 0 && out.max_q >= 0) { out.do_bt = 1; out.bt_i = out.max_t; out.bt_j = out.max_q; }
         }
-        __syncthreads();
-        struct Best { int m, t, r; };   // a maximum, its target position and its anti-diagonal (its place in walking order)
-        // first strict maximum in walking order over the lanes of the group: inclusive scan, the later lane wins only when greater
-        auto scan_first_max = [&](Best x) {
-#pragma unroll
-            for (int d = 1; d < GL; d <<= 1) {
-                const Best o{__shfl_up(x.m, d, GL), __shfl_up(x.t, d, GL), __shfl_up(x.r, d, GL)};
-                if (gl >= d && !(x.m > o.m)) x = o;
-            }
-            return x;
-        };
-        auto diag = [&](int r, int &H, int &mt) {
-            const uint32_t pv = BEST[r];
-            const uint32_t inv = pv & 8191u;
-            H = (int)(pv >> 13) - 4096;
-            mt = inv == 8191u ? min(tlm1, r) : (int)((8191u - inv) & 1023u);
-        };
-        const int C = (n_r + GL - 1) / GL, rlo = min(n_r, gl * C), rhi = min(n_r, rlo + C);
-        // (1) the running maximum that enters every lane's chunk
-        auto chunk_best = [&](int lim) {
-            Best b{NEG_INF, -1, -1};
-            for (int r = rlo; r < rhi && r <= lim; ++r) { int H, mt; diag(r, H, mt); if (H > b.m) b = Best{H, mt, r}; }
-            return b;
-        };
-        Best incl = scan_first_max(chunk_best(n_r));
-        Best in{__shfl_up(incl.m, 1, GL), __shfl_up(incl.t, 1, GL), __shfl_up(incl.r, 1, GL)};
-        ExtApply ez; ez.max = 0; ez.max_t = ez.max_q = -1; ez.zdropped = 0;
-        if (gl > 0 && in.m > 0) { ez.max = in.m; ez.max_t = in.t; ez.max_q = in.r - in.t; }
-        // (2) the first anti-diagonal that z-drops
-        int r_break = n_r;
-        for (int r = rlo; r < rhi; ++r) {
-            int H, mt; diag(r, H, mt);
-            if (ext_apply_zdrop(ez, H, r, mt, zdrop, e2)) { r_break = r; break; }
-        }
-#pragma unroll
-        for (int dlt = GL / 2; dlt; dlt >>= 1) r_break = min(r_break, __shfl_xor(r_break, dlt));
-        const bool dropped = r_break < n_r;
-        // (3) the state when the walk stops: maximum over the anti-diagonals up to there, best cell of the last query column
-        // (H(st, qlen - 1) of the anti-diagonals qlen - 1 .. r_break: target positions 0 .. r_break - qlen + 1)
-        Best fin = scan_first_max(chunk_best(r_break));
-        fin = Best{__shfl(fin.m, GL - 1, GL), __shfl(fin.t, GL - 1, GL), __shfl(fin.r, GL - 1, GL)};
-        const int t_lim = min(tlm1, r_break - (qlen - 1));
-        const int Ct = (tlen + GL - 1) / GL, tlo = min(tlen, gl * Ct), thi = min(tlen, tlo + Ct);
-        Best me{NEG_INF, -1, -1};
-        for (int t = tlo; t < thi && t <= t_lim; ++t) { const int h = (int)HL[t] - 4096; if (h > me.m) me = Best{h, t, t}; }
-        me = scan_first_max(me);
-        me = Best{__shfl(me.m, GL - 1, GL), __shfl(me.t, GL - 1, GL), 0};
-        if (head && jid >= 0) {
-            ExtRes out;
-            out.max = 0; out.zdropped = 0; out.max_q = out.max_t = out.mqe_t = -1; out.mqe = NEG_INF; out.score = NEG_INF;
-            out.reach_end = 0; out.n_cigar = 0; out.r_done = -1; out.bt_i = out.bt_j = -1; out.do_bt = 0; out.zcode = 0; out.cig_pos = 0;
-            if (ok) {
-                if (fin.m > 0) { out.max = fin.m; out.max_t = fin.t; out.max_q = fin.r - fin.t; }
-                out.zdropped = dropped ? 1 : 0;
-                if (me.m > NEG_INF) { out.mqe = me.m; out.mqe_t = me.t; }
-                if (!dropped) out.score = (int)HL[tlm1] - 4096;
-                out.r_done = dropped ? r_break : n_r - 1;
-                if (!dropped && !(jflag & EZ_EXTZ_ONLY)) { out.do_bt = 1; out.bt_i = tlen - 1; out.bt_j = qlen - 1; }
-                else if (!dropped && (jflag & EZ_EXTZ_ONLY) && out.mqe + end_bonus > out.max) { out.reach_end = 1; out.do_bt = 1; out.bt_i = out.mqe_t; out.bt_j = qlen - 1; }
-                else if (out.max_t >= 0 && out.max_q >= 0) { out.do_bt = 1; out.bt_i = out.max_t; out.bt_j = out.max_q; }
-            }
-            res[jid] = out;
-        }
+        res[jid] = out;
     }
 }
 
@@ -1222,20 +1028,20 @@ __device__ __forceinline__ void ext_strip_pair(const ExtJob *__restrict__ jobs, 
 // 256 / 512 / 1024 rows: the ramp of the systolic array costs n_lanes - 1 steps per window, so a window should use as few
 // lanes -- as tall a strip, S <= 16 -- as it can.  The launch list is grouped by S and every group is padded to whole
 // waves, so S is uniform per wave (read from its first window).
-template <int GL, bool EXACT, bool RIGHT>
-__device__ __forceinline__ void ext_strip_dispatch(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, const int first,
-                                                   const int n_list, const ExtParams &prm, const uint8_t *__restrict__ reads,
-                                                   const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
-                                                   const RefView &rv, uint8_t *__restrict__ P, ExtRes *__restrict__ res, uint8_t *smem,
-                                                   const int lds_stride, const int nr_stride) {
+template <int GL, bool RIGHT>
+__device__ __forceinline__ void ext_strip_exact_dispatch(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, const int first,
+                                                         const int n_list, const ExtParams &prm, const uint8_t *__restrict__ reads,
+                                                         const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
+                                                         const RefView &rv, uint8_t *__restrict__ P, ExtRes *__restrict__ res, uint8_t *smem,
+                                                         const int lds_stride, const int nr_stride) {
     const int j0 = first < n_list ? order[first] : -1;
     if (j0 < 0) return;   // (a wave of padding only: the lists are padded to whole waves at their ends)
     const int S = jobs[j0].strip_s;
-#define MPN_CASE(SS) case SS: ext_strip_pack<SS, GL, EXACT, RIGHT>(jobs, order, first, n_list, prm, reads, read_off, read_len, rv, P, res, smem, lds_stride, nr_stride); break
+#define MPN_CASE(SS) case SS: ext_strip_exact<SS, GL, RIGHT>(jobs, order, first, n_list, prm, reads, read_off, read_len, rv, P, res, smem, lds_stride, nr_stride); break
     switch (S) {
         MPN_CASE(1); MPN_CASE(2); MPN_CASE(3); MPN_CASE(4); MPN_CASE(5); MPN_CASE(6); MPN_CASE(7); MPN_CASE(8);
         MPN_CASE(9); MPN_CASE(10); MPN_CASE(11); MPN_CASE(12); MPN_CASE(13); MPN_CASE(14); MPN_CASE(15);
-        default: ext_strip_pack<16, GL, EXACT, RIGHT>(jobs, order, first, n_list, prm, reads, read_off, read_len, rv, P, res, smem, lds_stride, nr_stride); break;
+        default: ext_strip_exact<16, GL, RIGHT>(jobs, order, first, n_list, prm, reads, read_off, read_len, rv, P, res, smem, lds_stride, nr_stride); break;
     }
 #undef MPN_CASE
 }
@@ -1243,7 +1049,7 @@ __device__ __forceinline__ void ext_strip_dispatch(const ExtJob *__restrict__ jo
 // ONE launch for all the lane-group classes of a variant family (every launch ends in a tail of half-empty CUs: three launches
 // per round had three).  Segments are ordered from the widest lane group to the narrowest and, inside a class, from the tallest
 // strips and the longest queries down, so the waves with the most cells start first.
-struct StripSeg { int32_t first_block, n_list, ord_off, lds_stride, nr_stride, glc, right, pair; };   // pair: two windows per lane group (gap fills)
+struct StripSeg { int32_t first_block, n_list, ord_off, lds_stride, nr_stride, glc, right; };
 struct StripSegs { StripSeg s[6]; int32_t n; };
 
 // (the paired gap-fill cell keeps five registers per row -- u, y, y2 and the two windows' target selectors -- ~120 VGPRs at 16 rows:
@@ -1274,7 +1080,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         }
     } else {
         const int first = ((int)blockIdx.x - sg.first_block) * (4 >> sg.glc);
-#define MPN_GL(GLN, RT) ext_strip_dispatch<GLN, EXACT, RT>(jobs, ord, first, sg.n_list, prm, reads, read_off, read_len, rv, P, res, smem, sg.lds_stride, sg.nr_stride)
+#define MPN_GL(GLN, RT) ext_strip_exact_dispatch<GLN, RT>(jobs, ord, first, sg.n_list, prm, reads, read_off, read_len, rv, P, res, smem, sg.lds_stride, sg.nr_stride)
         if (sg.right) { if (sg.glc == 0) MPN_GL(16, true); else if (sg.glc == 1) MPN_GL(32, true); else MPN_GL(64, true); }
         else { if (sg.glc == 0) MPN_GL(16, false); else if (sg.glc == 1) MPN_GL(32, false); else MPN_GL(64, false); }
 #undef MPN_GL
@@ -1344,7 +1150,7 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
     out.max = 0; out.zdropped = 0; out.max_q = out.max_t = out.mqe_t = -1; out.mqe = NEG_INF; out.score = NEG_INF;
     out.reach_end = 0; out.n_cigar = 0; out.r_done = -1; out.bt_i = out.bt_j = -1; out.do_bt = 0; out.zcode = 0; out.cig_pos = 0;
     if (!(EXACT ? ext_tile_exact_ok(qlen, tlen, w) : ext_tile_ok(qlen, tlen, w)) || -prm.sc_mis > 2 * (q + e)) { if (lane == 0) res[jid] = out; return; }
-    // ---- the cell's constants (see ext_strip_pack) ----
+    // ---- the cell's constants (see ext_strip_exact) ----
     constexpr int RS = RIGHT ? 0 : 4, RA = RIGHT ? 1 : 3, RB = 2, RA2 = RIGHT ? 3 : 1, RB2 = RIGHT ? 4 : 0;
     const uint32_t sb_mch = (uint32_t)(8 * prm.sc_mch + RS + 128) & 0xff, sb_mis = (uint32_t)(8 * prm.sc_mis + RS + 128) & 0xff,
                    sb_n = (uint32_t)(8 * prm.sc_n + RS + 128) & 0xff;
@@ -1541,7 +1347,7 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
             res[jid] = out;
         }
     } else {
-        // ---- the z-drop rule over the anti-diagonals in order (as in ext_strip_pack's exact variants, 64 lanes wide) ----
+        // ---- the z-drop rule over the anti-diagonals in order (as in ext_strip_exact, 64 lanes wide) ----
         __syncthreads();
         const int tlm1 = tlen - 1;
         struct Best { int m, t, r; };

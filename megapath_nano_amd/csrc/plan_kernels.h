@@ -286,6 +286,7 @@ constexpr int TILE_EXACT_MAX_NR = 4096;
 // launch lists: every DP window belongs to exactly one
 // (strip lists: kernel variant (gap fill with approximate maximum / exact / exact with right-aligned gaps) x lane-group class
 // (16/32/64 lanes per window) x strip height 1..16; each is padded to whole waves)
+// (LDS-state lists L_LDS + 5 * width class + LDS class: ext_dp_wg_kernel with 64, 256, 512 or 1024 threads; L_WG = 256 threads)
 constexpr int N_STRIP_CLASS = 9;   // variant * 3 + lane-group class
 enum { L_LDS = 0, L_WG = 5, L_STRIP = 20, N_STRIP = 16 * N_STRIP_CLASS, L_BAND = L_STRIP + N_STRIP, L_TILE = L_BAND + 16, N_LISTS = L_TILE + 1 };
 constexpr int STRIP_QB = 64;                                  // query-length buckets inside a strip list (longest first)
@@ -375,9 +376,11 @@ __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ 
         int cls = 4;
         for (int c = 0; c < 4; ++c) if (seqb + stateb <= lds_cap[c]) { cls = c; break; }
         jb.state_mode = 0;
-        const bool use_wg = force_kernel == 3 || (force_kernel != 1 && n_col - 1 > 128);
-        const int wg_nt = n_col - 1 <= 256 ? 0 : n_col - 1 <= 512 ? 1 : 2;
-        const int redo_list = bv >= 0 ? L_BAND + bv * 4 + bc : use_wg ? L_WG + wg_nt * 5 + cls : L_LDS + cls;
+        // workgroup kernel: 64, 256, 512 or 1024 threads by band width (force_kernel 1: one wave, 3: at least 256)
+        int wgc = n_col - 1 <= 128 ? 0 : n_col - 1 <= 256 ? 1 : n_col - 1 <= 512 ? 2 : 3;
+        if (force_kernel == 1) wgc = 0;
+        else if (force_kernel == 3) wgc = max(wgc, 1);
+        const int redo_list = bv >= 0 ? L_BAND + bv * 4 + bc : L_LDS + wgc * 5 + cls;
         int lid;
         if (strip) {
             lid = L_STRIP + sclass * 16 + (16 - jb.strip_s);   // tall strips (the waves with the most cells) first: they must not start last

@@ -515,7 +515,11 @@ class Hits:
 
 
 def ext_dp_batch(opt, queries, targets, w, zdrop, end_bonus, flag, force_kernel=0):
-    """DP stage on (query, target) pairs of 0..4 codes -> list of dicts (max, zdropped, max_q, max_t, mqe, mqe_t, score, reach_end, n_cigar, cigar)."""
+    """DP stage on (query, target) pairs of 0..4 codes -> list of dicts (max, zdropped, max_q, max_t, mqe, mqe_t, score, reach_end, n_cigar, cigar).
+
+    force_kernel: 0 dispatch as the mapper does; 1 LDS-state workgroup kernel with one wave per window; 3 the same with 256, 512
+    or 1024 threads by band width; 4 systolic strip kernel where eligible, else as 5; 5 band-in-registers kernel where the band
+    fits 1024 slots; 6 tiled strips where eligible.  Other windows go to the workgroup kernel, sized as under 0."""
     lib = _bind()
     n = len(queries)
     qbuf, qoff, qlen = pack_seqs([np.asarray(q, dtype=np.uint8) for q in queries])

@@ -8,7 +8,7 @@ lst = cls & 0xff
 EXTZ, RIGHT, APPROX = 0x40, 0x02, 0x08   # printed for orientation only: see ext_kernels.h for the flag values
 L_BAND = 164   # plan_kernels.h: L_STRIP + 16 * N_STRIP_CLASS
 fam = np.where(lst < 5, 0, np.where(lst < 20, 1, np.where(lst < L_BAND, 2, 3)))
-names = ['lds', 'wg', 'strip', 'band']
+names = ['wg64', 'wg', 'strip', 'band']
 print('windows', len(r))
 for f in range(4):
     m = (fam == f) & (cls >= 0)

@@ -1,4 +1,4 @@
-"""GPU parity tests (-m gpu) of the extension-DP kernels (single-wave LDS, workgroup, strip, band) against
+"""GPU parity tests (-m gpu) of the extension-DP kernels (workgroup with one wave and with 256+ threads, strip, band) against
 the oracle's mmo_extd2 on seeded pairs: global / approximate-max / extension-only / right-aligned modes, band clipping,
 z-drop, ambiguous bases, small to large windows.  Bit-exact on scores, end points and CIGAR."""
 import numpy as np
@@ -157,7 +157,7 @@ def test_band_clipping_and_large_windows(opt):
 
 def test_band_kernel_slot_variants(opt):
     """Every slot count of the band kernel (128/256/512/1024), with the band sliding far enough to wrap the slots several
-    times, in approximate, exact and extension modes; the single-wave LDS kernel (1) must agree with the oracle too."""
+    times, in approximate, exact and extension modes; the one-wave workgroup kernel (1) must agree with the oracle too."""
     qs, ts = make_pairs(12, [900, 2500, 4100])
     for w in (10, 63, 126, 127, 128, 254, 255, 256, 400, 510, 511, 600, 1022, 1023):
         check(opt, qs, ts, w, 400, -1, APPROX, [5])
@@ -174,7 +174,7 @@ def test_band_kernel_slot_variants(opt):
 def test_lopsided_windows_dispatch(opt):
     """Windows far from square: long query x short target and the reverse, around the strip kernel's class limits
     (query 1024 / 2048 / 4096 bases per lane-group class, target 256 / 512 / 1024 rows): whatever kernel the dispatcher
-    picks (0) must agree with the oracle, like the LDS fallback (1)."""
+    picks (0) must agree with the oracle, like the one-wave workgroup kernel (1)."""
     rng = np.random.default_rng(31)
     qs, ts = [], []
     for qlen, tlen in ((5000, 300), (300, 5000), (1024, 256), (1025, 256), (2048, 512), (2049, 300), (4096, 1024), (4097, 1000),
