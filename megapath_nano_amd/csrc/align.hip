@@ -860,7 +860,7 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     prm.zdrop_inv = opt->zdrop_inv; prm.max_gap = opt->max_gap;
     const size_t order_cap = (size_t)nj + (size_t)N_STRIP * 8 + 16;   // (a strip list is padded to whole waves: at most 7 entries)
     if (SL.pool_sizes.ensure((size_t)nj * sizeof(JobSizes) + 16) || SL.pool_buckets.ensure((size_t)2 * N_BUCKETS * 4 + sizeof(LayoutTotals) + 16) ||
-        SL.pool_order.ensure(order_cap * 4) || SL.pin_res.ensure(sizeof(LayoutTotals) + 64) ||
+        SL.pool_order.ensure(order_cap * 4) || SL.pin_res.ensure(sizeof(LayoutTotals) + 96) ||
         SL.pool_redo_ids.ensure((size_t)nj * 4 + 16) || SL.pool_probes.ensure((size_t)nj * sizeof(InvProbe) + 16))
         return -1;
     struct { ExtJob *p; } d_jobs{dv.jobs};
@@ -876,13 +876,16 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
         zero_list_push(z, d_bcnt, (size_t)2 * N_BUCKETS * 4 + sizeof(LayoutTotals));
         zero_list_push(z, dv.used + 1, 8);
         zero_list_push(z, dv.used + 5, 8);
+        zero_list_push(z, dv.used + 7, 8);
         MPN_HIP_CHECK(zero_regions(z, st));
     }
     const int lay_grid = std::max(1, std::min((nj + 255) / 256, 256));   // (a block per CU: every block flushes its counters once)
     EvTimer evl(st);
     static const bool tiled_on = []() { const char *e = getenv("MPN_TILED"); return !e || atoi(e) != 0; }();
-    hipLaunchKernelGGL(job_classify_kernel, dim3(lay_grid), dim3(256), 0, st, d_jobs.p, d_nj, strip_scores, prm, g_force_kernel ? g_force_kernel : (tiled_on ? 0 : 7), d_sizes,
-                       d_bcnt, d_tot);
+    // (MPN_TILE_CLASS: the tiled class of eligible windows, for the sweep of profiles/r06_tile_pipeline; 0 = one wave)
+    static const int tile_pick = []() { const char *e = getenv("MPN_TILE_CLASS"); return e ? std::min(std::max(atoi(e), 0), N_TILE_CLASS - 1) : -1; }();
+    hipLaunchKernelGGL(job_classify_kernel, dim3(lay_grid), dim3(256), 0, st, d_jobs.p, d_nj, strip_scores, prm, g_force_kernel ? g_force_kernel : (tiled_on ? 0 : 7),
+                       tile_pick, d_sizes, d_bcnt, d_tot);
     hipLaunchKernelGGL(job_scan_kernel, dim3(1), dim3(1024), 0, st, d_sizes, d_nj, (const int32_t *)d_bcnt, d_bcur, d_tot, d_order.p);
     hipLaunchKernelGGL(job_layout_kernel, dim3(lay_grid), dim3(256), 0, st, d_jobs.p, d_nj, (const JobSizes *)d_sizes, d_bcur, d_order.p);
     MPN_HIP_CHECK(hipGetLastError());
@@ -907,11 +910,14 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     g_stats[4] += nj; g_stats[5] += T.cells; g_stats[31] += T.strip_cells[0] + T.strip_cells[1] + T.strip_cells[2];
     for (int c = 0; c < 3; ++c) g_stats[41 + c] += T.strip_cells[c];
     g_stats[58] += T.xstrip_cells;
-    g_stats[64] += cnt[L_TILE];   // windows on the tiled strips (none under MPN_TILED=0)
+    for (int c = 0; c < N_TILE_CLASS; ++c) {   // windows on the tiled strips (none under MPN_TILED=0), and per class
+        g_stats[64] += cnt[L_TILE + c];
+        g_stats[STAT_TILE_CLASS + c] += cnt[L_TILE + c];
+    }
     if (getenv("MPN_DEBUG_JOBS")) {
-        static const char *const fam[] = {"wg64", "wg", "strip", "band"};
+        static const char *const fam[] = {"wg64", "wg", "strip", "band", "tile"};
         for (int l = 0; l < N_LISTS; ++l)
-            if (cnt[l]) fprintf(stderr, "[jobs] %s list %-2d n=%d\n", fam[l < L_WG ? 0 : l < L_STRIP ? 1 : l < L_BAND ? 2 : 3], l, cnt[l]);
+            if (cnt[l]) fprintf(stderr, "[jobs] %s list %-2d n=%d\n", fam[l < L_WG ? 0 : l < L_STRIP ? 1 : l < L_BAND ? 2 : l < L_TILE ? 3 : 4], l, cnt[l]);
     }
     if (const char *dump = getenv("MPN_DUMP_STRIPS")) {   // debug: the geometry of the strip launch lists, in launch order
         const int n_ord = base[L_BAND] - base[L_STRIP];
@@ -993,10 +999,18 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
             } while (0)
             if (fam == 0) MPN_STRIP_LAUNCH(false); else MPN_STRIP_LAUNCH(true);
 #undef MPN_STRIP_LAUNCH
-        } else if (l == L_TILE) {
-            const size_t lds = (size_t)std::max(T.tile_lds, 64) + 64;   // (ext_tile_lds_bytes of the list's largest window)
-            if (lds > 64 * 1024) MPN_HIP_CHECK(hipFuncSetAttribute((const void *)ext_dp_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(ext_dp_tile_kernel, dim3(n), dim3(64), lds, s, d_jobs.p, ord, n, prm, d_reads, d_read_off, d_read_len, rv, P.p, gstate.p, d_res.p);
+        } else if (l >= L_TILE) {   // NW waves per window (tile_class_nw), the LDS of the list's largest window (ext_tile_lds_bytes)
+            const int c = l - L_TILE;
+            const size_t lds = (size_t)std::max(T.tile_lds[c], 64);
+#define MPN_TILE_LAUNCH(S, NW)                                                                                                        \
+            do {                                                                                                                      \
+                if (lds > 64 * 1024) MPN_HIP_CHECK(hipFuncSetAttribute((const void *)ext_dp_tile_kernel<S, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+                hipLaunchKernelGGL((ext_dp_tile_kernel<S, NW>), dim3(n), dim3(64 * NW), lds, s, d_jobs.p, ord, n, prm, d_reads, d_read_off, \
+                                   d_read_len, rv, P.p, gstate.p, d_res.p, d_used + 7);                                              \
+            } while (0)
+            static_assert(N_TILE_CLASS == 4, "tile classes");
+            if (c == 0) MPN_TILE_LAUNCH(16, 1); else if (c == 1) MPN_TILE_LAUNCH(4, 8); else if (c == 2) MPN_TILE_LAUNCH(8, 4); else MPN_TILE_LAUNCH(4, 16);
+#undef MPN_TILE_LAUNCH
         } else {
             const int bvar = (l - L_BAND) / 4;
             const size_t lds = std::max<size_t>((size_t)T.band_lds[(l - L_BAND) % 4], 64);
@@ -1022,7 +1036,8 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
         MPN_HIP_CHECK(hipEventCreateWithFlags(&SL.ev_c, hipEventDisableTiming));
     }
     auto on_side = [](int l) { return (l >= L_WG && l < L_STRIP) || l >= L_BAND + 8; };  // workgroup windows, 512- and 1024-slot bands, tiled strips
-    const bool have_tiles = cnt[L_TILE] > 0;
+    bool have_tiles = false;
+    for (int l = L_TILE; l < N_LISTS; ++l) have_tiles = have_tiles || cnt[l] > 0;
     bool have_side = false;
     for (int l = 0; l < L_TILE; ++l) have_side = have_side || (on_side(l) && cnt[l] > 0);
     hipStream_t extra[2] = {nullptr, nullptr};
@@ -1032,7 +1047,8 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     // (tiles: a wave per window for milliseconds; on a stream of their own they overlap the band kernels instead of preceding them)
     const hipStream_t side_st = have_side && n_extra > 0 ? extra[0] : main_st;
     const hipStream_t tile_st = have_tiles && n_extra > (int)have_side ? extra[(int)have_side] : main_st;
-    if (have_tiles && launch_list(L_TILE, d_order.p + base[L_TILE], cnt[L_TILE], tile_st)) return -1;
+    for (int l = L_TILE; l < N_LISTS && have_tiles; ++l)
+        if (launch_list(l, d_order.p + base[l], cnt[l], tile_st)) return -1;
     for (int l = L_TILE - 1; l >= 0; --l)
         if (on_side(l) && launch_list(l, d_order.p + base[l], cnt[l], side_st)) return -1;
     // The long windows are also the long pole of the two lane-per-window kernels (traceback, z-drop test): those of the side
@@ -1077,12 +1093,17 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     if (side_st != main_st) MPN_HIP_CHECK(hipStreamWaitEvent(main_st, SL.ev_b, 0));
     if (tile_st != main_st) MPN_HIP_CHECK(hipStreamWaitEvent(main_st, SL.ev_c, 0));
     unsigned long long *h_used = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(SL.pin_res.p) + ((sizeof(LayoutTotals) + 15) & ~(size_t)15));
-    MPN_HIP_CHECK(hipMemcpyAsync(h_used, d_used, 48, hipMemcpyDeviceToHost, st));
+    MPN_HIP_CHECK(hipMemcpyAsync(h_used, d_used, 64, hipMemcpyDeviceToHost, st));
     wt.stop_into(g_stats[28]);
     MPN_HIP_CHECK(stream_sync(st));
     wt.stop_into(g_stats[29]);
     // second pass: the windows whose CIGAR failed the z-drop test were listed by the test kernel (in no particular order), and
     // the windows whose largest drop may hide an inversion (mm_test_zdrop's probe: rare; decided here)
+    if (h_used[7]) {   // tiled windows whose hand-off wait gave up (never expected): counted, and the call fails
+        g_stats[STAT_TILE_GIVEUPS] += (int64_t)h_used[7];
+        set_error("%llu tiled DP windows gave up waiting for their hand-off", (unsigned long long)h_used[7]);
+        return -1;
+    }
     std::vector<int32_t> redo((size_t)h_used[1]);
     const int n_probe = (int)h_used[5];
     if (!redo.empty() || n_probe) {
@@ -1139,7 +1160,7 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
             const ExtJob &jb = jobs[(size_t)j];
             const int bv = band_of(j);
             pack[k] = j; pack[nr + k] = bv >= 0 ? 2 : 0; pack[2 * nr + k] = 128 << std::max(bv, 0); pack[3 * nr + k] = is_inv[(size_t)j];
-            if ((list_of(j) >= L_STRIP && list_of(j) < L_BAND) || list_of(j) == L_TILE) {   // (strip and tiled layouts are sized for themselves)
+            if ((list_of(j) >= L_STRIP && list_of(j) < L_BAND) || list_of(j) >= L_TILE) {   // (strip and tiled layouts are sized for themselves)
                 const int64_t n_r = (int64_t)jb.qlen + jb.tlen - 1;
                 pack_off[k] = -1 - p2_tot;  // resolved below, once the pool address is known
                 p2_tot += ((bv >= 0 ? n_r * (128 << bv) : n_r * jb.n_col) + 15) & ~(int64_t)15;

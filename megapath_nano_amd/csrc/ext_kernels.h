@@ -33,7 +33,7 @@ struct ExtJob {
     int32_t layout;      // direction matrix: 0 = [anti-diagonal][t - band start]; 1 = strip kernel: cell (t, j) at [j + t/S][t];
                          // 2 = band kernel: [anti-diagonal][t mod SL]; 3 = tiled strips (tile_geom)
     int32_t qstride;     // layout 1: row width W = n_lanes * S bytes; layout 2: SL
-    int32_t strip_s;     // layout 1: S
+    int32_t strip_s;     // layout 1: S; layout 3: rows per lane of a tile (R / 64)
     int32_t cls;         // launch list | second-pass list << 8 | (band variant + 1) << 16 (job_classify_kernel); -1: placeholder without DP
 };
 
@@ -1089,32 +1089,49 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Tiled, banded strips: the gap fills the strip kernel above cannot take -- targets longer than 1024 rows, or a band that clips
-// (the 1.6-kb fills between the sparse anchors of a divergent assembly; w = 750) -- on the SAME cell instead of the band kernel's
-// generic 32-bit one (~33 instead of ~120 instructions per cell).  One wave per window.  The target is cut into tiles of 1024 rows
-// (64 lanes x 16); a tile is a systolic strip over the query columns its rows have in the band, [T0 - w, T0 + rows - 1 + w]; the
-// v / x states and H of a tile's last row go through a 12-byte-per-column boundary in HBM to the next tile's first row.
+// (the 1.6-kb fills between the sparse anchors of a divergent assembly; w = 750) -- and the end extensions beyond the exact strip
+// variants, on the SAME cell instead of the band kernel's generic 32-bit one (~33 instead of ~120 instructions per cell).  The
+// target is cut into tiles of R = 64 S rows (64 lanes x S); a tile is a systolic strip over the query columns its rows have in the
+// band, [T0 - w, T0 + R - 1 + w], and hands the v / x states and H of its last row (12 bytes per column) to the next tile's first row.
+//   ext_dp_tile_kernel<16, 1>  one wave walks the tiles one after another; the hand-off goes through HBM (any band width)
+//   ext_dp_tile_kernel<S, NW>  NW waves, wave k mod NW takes tile k: tile k + 1 starts R + 63 steps after tile k, its first row
+//                              read from an LDS ring the wave before fills (pipelined; bands with 2 w + 128 < NW (C + R))
 // ksw2's band in (t, j) terms: a cell is computed iff t - w <= j <= t + w (st = (r - w + 1) >> 1, en = (r + w) >> 1, r = t + j).
 // What lies outside is never read: the first in-band cell of a row (j == t - w) takes freshly opened gaps on its left, the last
 // one (j == t + w) freshly opened gaps above -- two selects each -- exactly what ksw2's SSE code and the band kernel read there.
 // Cells outside the band are computed on whatever flows in and ignored.  H is carried as a 32-bit number (8 H): from the left,
 // or from above at a row's entry into the band; the corner's H is the score (ksw2's approximate-maximum walk ends there too).
-// Directions: per tile a step-major block like the strip kernel's; layout 3 in the traceback.
-constexpr int TILE_ROWS = 1024, TILE_S = 16;
+// Directions: per tile a step-major block like the strip kernel's; layout 3 in the traceback (ExtJob::strip_s = S).
 struct TileGeom { int T0, rows, n_lanes, W, jlo, jhi; int64_t base; };
-// geometry of tile `tile` of a tlen x qlen window with band w; base = bytes of the tiles before it
-__host__ __device__ inline TileGeom tile_geom(int tile, int qlen, int tlen, int w) {
+// geometry of tile `tile` (S rows per lane) of a tlen x qlen window with band w, a tile with a column in the band; base = bytes of
+// the tiles before it, which are all full (R rows, 64 lanes) and have columns in the band too: sum over k < tile of (jhi_k - jlo_k + 64) R, jlo_k = max(0, k R - w), jhi_k = min(qlen - 1, k R + R - 1 + w)
+__host__ __device__ inline TileGeom tile_geom(int tile, int qlen, int tlen, int w, int S) {
+    const int R = 64 * S;
     TileGeom g{};
-    int64_t base = 0;
-    for (int k = 0;; ++k) {
-        const int T0 = k * TILE_ROWS, rows = tlen - T0 < TILE_ROWS ? tlen - T0 : TILE_ROWS, nl = (rows + TILE_S - 1) / TILE_S;
-        const int jlo = T0 - w > 0 ? T0 - w : 0, jhi = T0 + rows - 1 + w < qlen - 1 ? T0 + rows - 1 + w : qlen - 1;
-        if (k == tile) { g.T0 = T0; g.rows = rows; g.n_lanes = nl; g.W = nl * TILE_S; g.jlo = jlo; g.jhi = jhi; g.base = base; return g; }
-        base += (int64_t)((jhi >= jlo ? jhi - jlo + 1 : 0) + nl - 1) * (nl * TILE_S);
-    }
+    g.T0 = tile * R;
+    g.rows = tlen - g.T0 < R ? tlen - g.T0 : R;
+    g.n_lanes = (g.rows + S - 1) / S;
+    g.W = g.n_lanes * S;
+    g.jlo = g.T0 - w > 0 ? g.T0 - w : 0;
+    g.jhi = g.T0 + g.rows - 1 + w < qlen - 1 ? g.T0 + g.rows - 1 + w : qlen - 1;
+    const int64_t m = tile;
+    // sum of jlo_k: the k with k R > w, i.e. k >= k0 = w / R + 1
+    const int64_t k0 = (int64_t)w / R + 1;
+    const int64_t n0 = m > k0 ? m - k0 : 0;
+    const int64_t s_lo = (int64_t)R * (n0 * (k0 + m - 1) / 2) - n0 * (int64_t)w;   // R (k0 + ... + m - 1) - n0 w
+    // sum of jhi_k: k R + R - 1 + w below qlen - 1 for k < k1 = ceil((qlen - R - w) / R) (clamped to [0, m])
+    const int64_t num = (int64_t)qlen - R - w;
+    int64_t k1 = num <= 0 ? 0 : (num + R - 1) / R;
+    if (k1 > m) k1 = m;
+    const int64_t s_hi = (int64_t)R * (k1 * (k1 - 1) / 2) + k1 * (int64_t)(R - 1 + w) + (m - k1) * (int64_t)(qlen - 1);
+    g.base = (s_hi - s_lo + 64 * m) * R;
+    return g;
 }
-__host__ __device__ inline int64_t tile_matrix_bytes(int qlen, int tlen, int w) {
-    const int nt = (tlen + TILE_ROWS - 1) / TILE_ROWS;
-    const TileGeom g = tile_geom(nt - 1, qlen, tlen, w);
+__host__ __device__ inline int64_t tile_matrix_bytes(int qlen, int tlen, int w, int S) {
+    // (the tiles with a column in the band: k R - w <= qlen - 1; past them an end extension's band has left the matrix, and
+    // tile_geom, which assumes its tiles non-empty, does not apply)
+    const int R = 64 * S, nt_all = (tlen + R - 1) / R, nt_band = (int)(((int64_t)qlen - 1 + w) / R) + 1, nt = nt_all < nt_band ? nt_all : nt_band;
+    const TileGeom g = tile_geom(nt - 1, qlen, tlen, w, S);
     return g.base + (int64_t)((g.jhi >= g.jlo ? g.jhi - g.jlo + 1 : 0) + g.n_lanes - 1) * g.W;
 }
 // eligible: a global alignment whose corner the band reaches, on scores the packed cell holds
@@ -1126,20 +1143,32 @@ __host__ __device__ inline bool ext_tile_ok(int qlen, int tlen, int w) {
 // EXACT: an end extension (ksw2's exact maximum per anti-diagonal with its tie order, the z-drop rule, the best cell of the last query
 // column): every in-band cell merges (H, tie key) into its anti-diagonal's slot of an LDS table with one ds_max_u32 -- the slot's
 // band limits come from a second table -- and the rule is applied over the anti-diagonals in order after the last tile, like the
-// exact strip variants do.  RIGHT: right-aligned gaps (the left extension).  LDS: query | score table | BEST[n_r] | (st, en)[n_r].
+// exact strip variants do.  RIGHT: right-aligned gaps (the left extension).
+// LDS: query | score table | [NW > 1: hand-off counters | rings] | BEST[n_r] | (st, en)[n_r].
 __host__ __device__ inline bool ext_tile_exact_ok(int qlen, int tlen, int w) {
     return qlen > 0 && tlen > 0 && w >= 1 && tlen <= 8191 && qlen <= 16384 && qlen + tlen - 1 <= 14000;
 }
-__host__ __device__ inline int ext_tile_lds_bytes(int qlen, int tlen, bool exact) {
-    return ((qlen + 3) & ~3) + 64 + (exact ? 8 * ((qlen + tlen + 2) & ~3) : 0);
+// The pipelined variant's hand-off: wave k's ring feeds wave k + 1 (mod NW), C = TILE_RING_COLS / NW columns of (v, x, H) each, with
+// two monotonic item counters per ring (produced, consumed).  Waiting cannot close a cycle while the rings together hold more than
+// the columns a tile hands on that the tile NW later has not yet been reached: NW (C + R) > 2 w (+ margin; ext_tile_pipe_ok).
+constexpr int TILE_RING_COLS = 2048, TILE_CTRL_BYTES = 4 * (2 * 16 + 4);   // (produced[NW], consumed[NW], failed, pad; NW <= 16)
+__host__ __device__ inline int ext_tile_ring_off(int qlen) { return ((qlen + 3) & ~3) + 64 + TILE_CTRL_BYTES; }
+__host__ __device__ inline int ext_tile_lds_bytes(int qlen, int tlen, bool exact, int NW) {
+    return ext_tile_ring_off(qlen) + (NW > 1 ? 12 * TILE_RING_COLS : 0) + (exact ? 8 * ((qlen + tlen + 2) & ~3) : 0);
 }
+__host__ __device__ inline bool ext_tile_pipe_ok(int w, int S, int NW) {
+    return 2 * w + 128 < NW * (TILE_RING_COLS / NW + 64 * S);
+}
+constexpr int TILE_SPIN_MAX = 1 << 21;   // polls (each after an s_sleep) before a wait gives up: ~0.1 s, far beyond any real wait
 
-template <bool EXACT, bool RIGHT>
+template <int S, int NW, bool EXACT, bool RIGHT>
 __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, const ExtParams &prm, const uint8_t *__restrict__ reads,
                                               const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len, const RefView &rv,
-                                              uint8_t *__restrict__ P, int8_t *__restrict__ gstate, ExtRes *__restrict__ res, uint8_t *smem) {
-    constexpr int S = TILE_S;
-    const int lane = threadIdx.x;
+                                              uint8_t *__restrict__ P, int8_t *__restrict__ gstate, ExtRes *__restrict__ res, uint8_t *smem,
+                                              unsigned long long *__restrict__ n_failed) {
+    static_assert(S % 4 == 0 && S <= 16 && NW >= 1 && NW <= 16, "rows per lane: 4, 8, 12 or 16");
+    constexpr int R = 64 * S, NT = 64 * NW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qlen = jb.qlen, tlen = jb.tlen;
     int q = prm.q, e = prm.e, q2 = prm.q2, e2 = prm.e2;
     if (q2 + e2 < q + e) { int t_ = q; q = q2; q2 = t_; t_ = e; e = e2; e2 = t_; }
@@ -1149,18 +1178,19 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
     ExtRes out;
     out.max = 0; out.zdropped = 0; out.max_q = out.max_t = out.mqe_t = -1; out.mqe = NEG_INF; out.score = NEG_INF;
     out.reach_end = 0; out.n_cigar = 0; out.r_done = -1; out.bt_i = out.bt_j = -1; out.do_bt = 0; out.zcode = 0; out.cig_pos = 0;
-    if (!(EXACT ? ext_tile_exact_ok(qlen, tlen, w) : ext_tile_ok(qlen, tlen, w)) || -prm.sc_mis > 2 * (q + e)) { if (lane == 0) res[jid] = out; return; }
+    if (!(EXACT ? ext_tile_exact_ok(qlen, tlen, w) : ext_tile_ok(qlen, tlen, w)) || -prm.sc_mis > 2 * (q + e) ||
+        (NW > 1 && !ext_tile_pipe_ok(w, S, NW))) { if (tid == 0) res[jid] = out; return; }
     // ---- the cell's constants (see ext_strip_exact) ----
     constexpr int RS = RIGHT ? 0 : 4, RA = RIGHT ? 1 : 3, RB = 2, RA2 = RIGHT ? 3 : 1, RB2 = RIGHT ? 4 : 0;
     const uint32_t sb_mch = (uint32_t)(8 * prm.sc_mch + RS + 128) & 0xff, sb_mis = (uint32_t)(8 * prm.sc_mis + RS + 128) & 0xff,
                    sb_n = (uint32_t)(8 * prm.sc_n + RS + 128) & 0xff;
     const int q_pad = (qlen + 3) & ~3;
     uint32_t *tab = reinterpret_cast<uint32_t *>(smem + q_pad);
-    if (lane < 5) tab[lane] = lane == 4 ? sb_n * 0x01010101u : (sb_mis * 0x01010101u) ^ ((sb_mch ^ sb_mis) << (8 * lane));
+    if (tid < 5) tab[tid] = lane == 4 ? sb_n * 0x01010101u : (sb_mis * 0x01010101u) ^ ((sb_mch ^ sb_mis) << (8 * lane));
     {
         const int64_t roff = read_off[jb.read];
         const int32_t rlen = read_len[jb.read];
-        for (int i = lane; i < qlen; i += 64) smem[i] = (uint8_t)(4 * ext_qbase(reads, roff, rlen, jb.rev, jb.qs + (jb.reversed ? qlen - 1 - i : i)));
+        for (int i = tid; i < qlen; i += NT) smem[i] = (uint8_t)(4 * ext_qbase(reads, roff, rlen, jb.rev, jb.qs + (jb.reversed ? qlen - 1 - i : i)));
     }
     int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
     if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
@@ -1180,38 +1210,61 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
     const uint32_t EIGHT = 0x00080008u, RANK_CLR = 0xfff8fff8u;
     const uint32_t MCH7 = (uint32_t)(8 * prm.sc_mch + 7 + BETA) * 0x00010001u;
     const int64_t g0 = rv.seq_off[jb.rid] + jb.ts;
-    // boundary between tiles: two buffers of qlen x 3 words in the window's global scratch (a tile reads what the one before wrote
-    // while it writes for the next)
+    // one wave: the boundary between tiles is two buffers of qlen x 3 words in the window's global scratch (a tile reads what the
+    // one before wrote while it writes for the next), H of the last query column follows them.  NW waves: an LDS ring per wave
+    // (see ext_tile_pipe_ok), H of the last query column at the start of the scratch.
     uint32_t *bnd_base = reinterpret_cast<uint32_t *>(gstate + jb.state_off);
-    const int n_tiles = (tlen + TILE_ROWS - 1) / TILE_ROWS;
+    const int n_tiles = (tlen + R - 1) / R;
+    uint32_t *ctrl = reinterpret_cast<uint32_t *>(smem + ext_tile_ring_off(qlen) - TILE_CTRL_BYTES);   // produced[NW] | consumed[NW] | failed
+    uint32_t *ring = ctrl + TILE_CTRL_BYTES / 4;
+    constexpr int C = TILE_RING_COLS / NW;   // columns per ring: (v, x, H) as three planes of C words
     // EXACT: per anti-diagonal the running (H, tie key) maximum and the band limits; per target row H in the last query column
     const int n_r = qlen + tlen - 1;
-    uint32_t *BEST = reinterpret_cast<uint32_t *>(smem + q_pad + 64), *SE = BEST + ((n_r + 3) & ~3);
-    int32_t *HL = reinterpret_cast<int32_t *>(bnd_base + 6 * (size_t)qlen);
-    int r_lim = n_r;   // first anti-diagonal whose band lies outside the matrix (ksw2 stops there as z-dropped)
+    uint32_t *BEST = reinterpret_cast<uint32_t *>(smem + ext_tile_ring_off(qlen) + (NW > 1 ? 12 * TILE_RING_COLS : 0)), *SE = BEST + ((n_r + 3) & ~3);
+    int32_t *HL = reinterpret_cast<int32_t *>(NW > 1 ? bnd_base : bnd_base + 6 * (size_t)qlen);
+    if (tid < 2 * NW + 1) ctrl[tid] = 0;
     if constexpr (EXACT) {
-        for (int r = lane; r < n_r; r += 64) {
+        for (int r = tid; r < n_r; r += NT) {
             int st = 0, en = tlen - 1;
             if (st < r - qlen + 1) st = r - qlen + 1;
             if (en > r) en = r;
             if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
             if (en > (r + w) >> 1) en = (r + w) >> 1;
-            if (st > en) { r_lim = r_lim < r ? r_lim : r; st = 1; en = 0; }
+            if (st > en) { st = 1; en = 0; }   // (the band has left the matrix: r_lim below)
             BEST[r] = 0;
             SE[r] = (uint32_t)st | (uint32_t)en << 16;
         }
-        for (int t = lane; t < tlen; t += 64) HL[t] = NEG_INF;
-        r_lim = wave_reduce_min(r_lim);
+        for (int t = tid; t < tlen; t += NT) HL[t] = NEG_INF;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     }
     __syncthreads();
     const bool head = lane == 0;
     int32_t score8 = 0;
-    int prev_jhi = -1;
-    for (int tile = 0; tile < n_tiles; ++tile) {
-        const TileGeom G = tile_geom(tile, qlen, tlen, w);
+    // NW waves: this wave reads the ring of wave - 1 and fills its own; item n of a ring is its n-th column handed on (each tile
+    // hands on its columns from the next tile's jlo up, the next tile reads exactly those, in order)
+    uint32_t *const prod_in = &ctrl[(wave + NW - 1) % NW], *const cons_in = &ctrl[NW + (wave + NW - 1) % NW];
+    uint32_t *const prod_out = &ctrl[wave], *const cons_out = &ctrl[NW + wave];
+    uint32_t *const ring_in = ring + 3 * C * ((wave + NW - 1) % NW), *const ring_out = ring + 3 * C * wave;
+    uint32_t n_in = 0, n_out = 0, seen_prod = 0, seen_cons = 0;
+    bool failed = false;
+    // a bounded wait for `*ctr - lim > 0` (counters are monotonic); false: it gave up, or another wave did (the window is marked failed)
+    auto wait_gt = [&](uint32_t *ctr, uint32_t lim, uint32_t &seen) -> bool {
+        if ((int)(seen - lim) > 0) return true;
+        for (int k = 0; k < TILE_SPIN_MAX; ++k) {
+            seen = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if ((int)(seen - lim) > 0) return true;
+            if (__hip_atomic_load(&ctrl[2 * NW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return false;
+            __builtin_amdgcn_s_sleep(1);
+        }
+        __hip_atomic_store(&ctrl[2 * NW], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return false;
+    };
+    for (int tile = NW > 1 ? wave : 0; tile < n_tiles; tile += NW) {
+        const TileGeom G = tile_geom(tile, qlen, tlen, w, S);
         const int T0 = G.T0, n_lanes = G.n_lanes, W = G.W, jlo = G.jlo, jhi = G.jhi;
-        if (jhi < jlo) break;   // (cannot happen for an eligible window: |qlen - tlen| <= w)
+        if (jhi < jlo) break;   // (an end extension whose band has left the matrix: so have the tiles after it)
+        const int prev_jhi = tile > 0 ? min(qlen - 1, T0 - 1 + w) : -1;   // jhi of the tile before
+        const int jlo_next = T0 + R - w > 0 ? T0 + R - w : 0;            // jlo of the tile after
         uint32_t *bnd_in = bnd_base + (size_t)(tile & 1) * 3 * (size_t)qlen, *bnd_out = bnd_base + (size_t)((tile + 1) & 1) * 3 * (size_t)qlen;
         const bool write_bnd = tile + 1 < n_tiles;
         const int t0 = T0 + lane * S;
@@ -1237,7 +1290,17 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
         // the head lane's boundary words, requested two steps ahead
         uint32_t bv_n = 0, bx_n = 0, bh_n = 0, bv_n2 = 0, bx_n2 = 0, bh_n2 = 0;
         auto load_bnd = [&](int col, uint32_t &a, uint32_t &b, uint32_t &c) {
-            if (tile > 0 && head && col <= prev_jhi && col < qlen) { a = bnd_in[3 * (size_t)col]; b = bnd_in[3 * (size_t)col + 1]; c = bnd_in[3 * (size_t)col + 2]; }
+            if (tile > 0 && head && col <= prev_jhi && col < qlen) {
+                if constexpr (NW == 1) { a = bnd_in[3 * (size_t)col]; b = bnd_in[3 * (size_t)col + 1]; c = bnd_in[3 * (size_t)col + 2]; }
+                else {
+                    const uint32_t n = n_in + (uint32_t)(col - jlo), slot = n % C;
+                    if (!failed && !wait_gt(prod_in, n, seen_prod)) failed = true;
+                    __atomic_signal_fence(__ATOMIC_SEQ_CST);   // (the counter's load before the data's: LDS serves a wave in order)
+                    a = ring_in[slot]; b = ring_in[C + slot]; c = ring_in[2 * C + slot];
+                    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+                    __hip_atomic_store(cons_in, n + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
         };
         load_bnd(jlo, bv_n, bx_n, bh_n);
         load_bnd(jlo + 1, bv_n2, bx_n2, bh_n2);
@@ -1259,7 +1322,7 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
                 else { Vp = bv; Xp = bx; Hup = (int32_t)bh; }
             } else { Vp = (uint32_t)v_s; Xp = (uint32_t)x_s; Hup = h_s; }
             if (j >= jlo && j <= jhi && lane < n_lanes) {
-                uint32_t dw[(S + 3) / 4], ecell[4] = {0, 0, 0, 0};
+                uint32_t dw[S / 4], ecell[4] = {0, 0, 0, 0};
                 const int d_in = j - t0 + w;    // row k enters the band at this column iff d_in == k
                 const int d_out = j - t0 - w;   // row k is the band's last row of this column iff d_out == k
 #pragma unroll
@@ -1319,9 +1382,21 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
                     }
                 }
                 out_v = (int)Vp; out_x = (int)Xp; out_h = Hup;
-                *reinterpret_cast<uint4 *>(prow + (int64_t)step * W) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+                if constexpr (S == 16) *reinterpret_cast<uint4 *>(prow + (int64_t)step * W) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+                else if constexpr (S == 8) *reinterpret_cast<uint2 *>(prow + (int64_t)step * W) = make_uint2(dw[0], dw[1]);
+                else if constexpr (S == 4) *reinterpret_cast<uint32_t *>(prow + (int64_t)step * W) = dw[0];
                 // a full tile's last lane hands its last row to the next tile
-                if (write_bnd && lane == 63) { bnd_out[3 * (size_t)j] = (uint32_t)out_v; bnd_out[3 * (size_t)j + 1] = (uint32_t)out_x; bnd_out[3 * (size_t)j + 2] = (uint32_t)out_h; }
+                if constexpr (NW == 1) {
+                    if (write_bnd && lane == 63) { bnd_out[3 * (size_t)j] = (uint32_t)out_v; bnd_out[3 * (size_t)j + 1] = (uint32_t)out_x; bnd_out[3 * (size_t)j + 2] = (uint32_t)out_h; }
+                } else if (write_bnd && lane == 63 && j >= jlo_next) {
+                    // (the slot is free once the consumer has taken item n - C)
+                    const uint32_t n = n_out + (uint32_t)(j - jlo_next), slot = n % C;
+                    if (!failed && !wait_gt(cons_out, n - C, seen_cons)) failed = true;
+                    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+                    ring_out[slot] = (uint32_t)out_v; ring_out[C + slot] = (uint32_t)out_x; ring_out[2 * C + slot] = (uint32_t)out_h;
+                    __atomic_signal_fence(__ATOMIC_SEQ_CST);   // (the data's stores before the counter's: LDS serves a wave in order)
+                    __hip_atomic_store(prod_out, n + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
             }
         }
         // the corner: H of row tlen - 1 after its last column (qlen - 1 = jhi of the last tile)
@@ -1332,13 +1407,27 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
             for (int k = 0; k < S; ++k) hv = k == kk ? H8[k] : hv;
             score8 = __shfl(hv, ll);
         }
-        prev_jhi = jhi;
-        // the boundary the next tile reads was written by lane 63, its first lane reads it: order them
+        if constexpr (NW == 1) {
+            // the boundary the next tile reads was written by lane 63, its first lane reads it: order them
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        } else {
+            if (tile > 0 && prev_jhi >= jlo) n_in += (uint32_t)(prev_jhi - jlo + 1);
+            if (write_bnd && jhi >= jlo_next) n_out += (uint32_t)(jhi - jlo_next + 1);
+        }
+    }
+#undef MPN_BND
+    if constexpr (NW > 1) {   // every wave's last-column H (EXACT) and the failure flag, then one wave finishes the window
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        if (wave != (EXACT ? 0 : (n_tiles - 1) % NW)) return;
+        if (__hip_atomic_load(&ctrl[2 * NW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {   // a wait gave up: no result
+            if (lane == 0) { res[jid] = out; atomicAdd(n_failed, 1ull); }
+            return;
+        }
     }
-#undef MPN_BND
     if constexpr (!EXACT) {
         if (lane == 0) {
             out.score = score8 >> 3;
@@ -1348,7 +1437,7 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
         }
     } else {
         // ---- the z-drop rule over the anti-diagonals in order (as in ext_strip_exact, 64 lanes wide) ----
-        __syncthreads();
+        if constexpr (NW == 1) __syncthreads();
         const int tlm1 = tlen - 1;
         struct Best { int m, t, r; };
         auto scan_first_max = [&](Best x) {
@@ -1364,6 +1453,10 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
             H = pv ? (int)(pv >> 16) - 32768 : NEG_INF;
             mt = (int)((0xffffu - (pv & 0xffffu)) & 8191u);
         };
+        // first anti-diagonal whose band lies outside the matrix (ksw2 stops there as z-dropped)
+        int r_lim = n_r;
+        for (int r = lane; r < n_r; r += 64) { const uint32_t se = SE[r]; if ((int)(se & 0xffffu) > (int)(se >> 16)) { r_lim = r; break; } }
+        r_lim = wave_reduce_min(r_lim);
         const int n_eff = r_lim < n_r ? r_lim : n_r;   // anti-diagonals ksw2 computes
         const int C = (n_eff + 63) / 64, rlo = min(n_eff, lane * C), rhi = min(n_eff, rlo + C);
         auto chunk_best = [&](int lim) {
@@ -1408,17 +1501,21 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
     }
 }
 
-__global__ __launch_bounds__(64) void ext_dp_tile_kernel(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, int n_jobs,
-                                                         ExtParams prm, const uint8_t *__restrict__ reads,
-                                                         const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
-                                                         RefView rv, uint8_t *__restrict__ P, int8_t *__restrict__ gstate, ExtRes *__restrict__ res) {
+template <int S, int NW>
+__global__ __launch_bounds__(64 * NW) void ext_dp_tile_kernel(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, int n_jobs,
+                                                              ExtParams prm, const uint8_t *__restrict__ reads,
+                                                              const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
+                                                              RefView rv, uint8_t *__restrict__ P, int8_t *__restrict__ gstate, ExtRes *__restrict__ res,
+                                                              unsigned long long *__restrict__ n_failed) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int jid = order[blockIdx.x];
     const ExtJob jb = jobs[jid];
     // (a workgroup is one window: one branch per window into the instantiation that carries only its own bookkeeping)
-    if (jb.flag & EZ_APPROX_MAX) ext_tile_body<false, false>(jb, jid, prm, reads, read_off, read_len, rv, P, gstate, res, smem);
-    else if (jb.flag & EZ_RIGHT) ext_tile_body<true, true>(jb, jid, prm, reads, read_off, read_len, rv, P, gstate, res, smem);
-    else ext_tile_body<true, false>(jb, jid, prm, reads, read_off, read_len, rv, P, gstate, res, smem);
+#define MPN_TB(EX, RT) ext_tile_body<S, NW, EX, RT>(jb, jid, prm, reads, read_off, read_len, rv, P, gstate, res, smem, n_failed)
+    if (jb.flag & EZ_APPROX_MAX) MPN_TB(false, false);
+    else if (jb.flag & EZ_RIGHT) MPN_TB(true, true);
+    else MPN_TB(true, false);
+#undef MPN_TB
 }
 
 
@@ -1444,7 +1541,7 @@ __global__ __launch_bounds__(64) void ext_bt_kernel(const ExtJob *__restrict__ j
     const bool rowmajor = jb.layout == 1;  // strip kernel: cell (t, j) at [j + t/S][t], band never clips
     const bool rank_is_op = (jb.flag & EZ_RIGHT) != 0;
     const bool byslot = jb.layout == 2;    // band kernel: cell (t, r) at [r][t mod SL], band limits recomputed here
-    const bool tiled = jb.layout == 3;     // tiled strips: per 1024-row tile a step-major block over the tile's band columns
+    const bool tiled = jb.layout == 3;     // tiled strips: per tile of 64 strip_s rows a step-major block over the tile's band columns
     TileGeom tg{};
     int tg_tile = -1;
     const int bw = jb.w < 0 ? (jb.tlen > jb.qlen ? jb.tlen : jb.qlen) : jb.w;
@@ -1501,10 +1598,10 @@ __global__ __launch_bounds__(64) void ext_bt_kernel(const ExtJob *__restrict__ j
             if (i > en) force_state = 1;
             tmp = 0;
             if (force_state < 0) {
-                const int tile = i / TILE_ROWS;
-                if (tile != tg_tile) { tg = tile_geom(tile, jb.qlen, jb.tlen, bw); tg_tile = tile; }   // (the walk only descends: a few times per window)
+                const int tile = i / (64 * jb.strip_s);
+                if (tile != tg_tile) { tg = tile_geom(tile, jb.qlen, jb.tlen, bw, jb.strip_s); tg_tile = tile; }   // (the walk only descends)
                 const int lt = i - tg.T0;
-                tmp = p[tg.base + (int64_t)((j - tg.jlo) + lt / TILE_S) * tg.W + lt];
+                tmp = p[tg.base + (int64_t)((j - tg.jlo) + lt / jb.strip_s) * tg.W + lt];
                 if (!rank_is_op) tmp = (tmp & ~7) | (4 - (tmp & 7));
             }
         }

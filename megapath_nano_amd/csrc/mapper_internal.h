@@ -83,10 +83,12 @@ struct HostChains {
     void chain_order(int i, int32_t *order, int64_t *src) const;
 };
 
-constexpr int MPN_NSTATS = 68;
+constexpr int MPN_NSTATS = 73;
 constexpr int STAT_LEASE_WAIT = 65;   // wall time the workers waited for a free submission stream (StreamLease)
 // extension groups with side work (long windows, tiles): [66] it got leased side streams, [67] it ran on the worker's own stream
 constexpr int STAT_SIDE_LEASED = 66, STAT_SIDE_OWN = 67;
+// tiled DP windows per tiled class ([68] one wave, [69..71] pipelined, plan_kernels.h tile_class_*), [72] hand-off waits given up (must be 0)
+constexpr int STAT_TILE_CLASS = 68, STAT_TILE_GIVEUPS = 72;
 extern thread_local int64_t g_stats[MPN_NSTATS];
 
 // 2-bit packing of 0..4 codes (N -> 0 + run list)

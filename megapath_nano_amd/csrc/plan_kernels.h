@@ -277,10 +277,16 @@ __global__ __launch_bounds__(64) void plan_kernel(PlanOpt o, const PlanReg *__re
     }
 }
 
-// An exact tiled window runs on ONE wave at ~50 instructions per cell: 4 ms for 3000 anti-diagonals, 26 ms for a 5000 x 5000
-// extension -- twice the band kernel's eight waves.  The pipeline is sensitive to that pole (-17 % on the strain-rich headline with
-// every extension tiled), so the longest extensions stay on the band kernel.
+// Tiled lists L_TILE + c: c = 0 runs a window's tiles one after another on ONE wave (S = 16, any band width); c >= 1 pipelines
+// them over the waves of a workgroup (ext_dp_tile_kernel<S, NW>).  An exact window on one wave runs at ~50 instructions per cell:
+// 26 ms for a 5000 x 5000 extension, twice the band kernel's eight waves, so the one-wave list keeps only exact windows of up to
+// TILE_EXACT_MAX_NR anti-diagonals; the pipelined lists take every eligible window (profiles/r06_tile_pipeline).
 constexpr int TILE_EXACT_MAX_NR = 4096;
+constexpr int N_TILE_CLASS = 4;
+__host__ __device__ inline int tile_class_s(int c) { return c == 0 ? 16 : c == 2 ? 8 : 4; }
+__host__ __device__ inline int tile_class_nw(int c) { return c == 0 ? 1 : c == 1 ? 8 : c == 2 ? 4 : 16; }
+constexpr int TILE_AUTO_CLASS = 1;        // the pipelined class of the automatic choice (the sweep in profiles/r06_tile_pipeline)
+constexpr int TILE_LDS_CAP = 160 << 10;   // LDS of one workgroup
 
 // ---- kernel choice and direction-matrix layout of every window --------------------------------------------------------------
 // launch lists: every DP window belongs to exactly one
@@ -288,7 +294,7 @@ constexpr int TILE_EXACT_MAX_NR = 4096;
 // (16/32/64 lanes per window) x strip height 1..16; each is padded to whole waves)
 // (LDS-state lists L_LDS + 5 * width class + LDS class: ext_dp_wg_kernel with 64, 256, 512 or 1024 threads; L_WG = 256 threads)
 constexpr int N_STRIP_CLASS = 9;   // variant * 3 + lane-group class
-enum { L_LDS = 0, L_WG = 5, L_STRIP = 20, N_STRIP = 16 * N_STRIP_CLASS, L_BAND = L_STRIP + N_STRIP, L_TILE = L_BAND + 16, N_LISTS = L_TILE + 1 };
+enum { L_LDS = 0, L_WG = 5, L_STRIP = 20, N_STRIP = 16 * N_STRIP_CLASS, L_BAND = L_STRIP + N_STRIP, L_TILE = L_BAND + 16, N_LISTS = L_TILE + N_TILE_CLASS };
 constexpr int STRIP_QB = 64;                                  // query-length buckets inside a strip list (longest first)
 constexpr int N_BUCKETS = N_LISTS + N_STRIP * (STRIP_QB - 1);  // scatter buckets: a strip list is STRIP_QB consecutive buckets
 __host__ __device__ inline int strip_glc_of_list(int l) { return ((l - L_STRIP) / 16) % 3; }
@@ -301,16 +307,17 @@ __host__ __device__ inline int bucket_of_list(int l) {       // first bucket of 
 struct LayoutTotals {          // read back by the host after job_layout_kernel
     long long p_tot, row_tot, cig_tot, state_tot, cells, strip_cells[3], xstrip_cells;
     int lds_need[5], strip_lds[N_STRIP_CLASS], band_lds[4], strip_nr[N_STRIP_CLASS];   // (strip_nr: anti-diagonals of the longest exact window)
-    int tile_lds, pad_;                                                                  // longest query of the tiled-strip list
+    int tile_lds[N_TILE_CLASS];                                                          // LDS of the largest window of each tiled list
     int too_large, tl_q, tl_t, n_jobs;
     int cnt[N_LISTS], base[N_LISTS + 1];   // launch lists in the flat order array (strip lists padded to whole waves)
 };
 
 struct JobSizes { long long p, row, cig, st; };   // scratch needs of a window (scanned into offsets)
 
+// tile_pick: the tiled class a window eligible for it takes (-1: TILE_AUTO_CLASS; 0: the one-wave class only)
 __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ jobs, const unsigned long long *__restrict__ nj_p, int strip_scores,
-                                                           ExtParams prm, int force_kernel, JobSizes *__restrict__ sizes, int32_t *__restrict__ bucket_cnt,
-                                                           LayoutTotals *__restrict__ tot) {
+                                                           ExtParams prm, int force_kernel, int tile_pick, JobSizes *__restrict__ sizes,
+                                                           int32_t *__restrict__ bucket_cnt, LayoutTotals *__restrict__ tot) {
     const int nj = (int)*nj_p;   // (written by plan_kernel, or by the host for the stage test)
     const bool no_tile = force_kernel == 7;   // 7: automatic choice without the tiled strips (MPN_TILED=0)
     if (no_tile) force_kernel = 0;
@@ -318,8 +325,8 @@ __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ 
     // counters and maxima are gathered per block in LDS and leave with one atomic per block and slot: a hundred thousand
     // windows adding to ONE global address serialise at the memory side (DESIGN.md lesson 4)
     __shared__ int s_bucket[N_BUCKETS];
-    constexpr int M_STRIP = 5, M_BAND = M_STRIP + N_STRIP_CLASS, M_NR = M_BAND + 4, M_TILE = M_NR + N_STRIP_CLASS, M_END = M_TILE + 1;
-    __shared__ int s_max[M_END];   // lds_need[5] | strip_lds[9] | band_lds[4] | strip_nr[9] | tile_lds
+    constexpr int M_STRIP = 5, M_BAND = M_STRIP + N_STRIP_CLASS, M_NR = M_BAND + 4, M_TILE = M_NR + N_STRIP_CLASS, M_END = M_TILE + N_TILE_CLASS;
+    __shared__ int s_max[M_END];   // lds_need[5] | strip_lds[9] | band_lds[4] | strip_nr[9] | tile_lds[4]
     for (int k = threadIdx.x; k < N_BUCKETS; k += blockDim.x) s_bucket[k] = 0;
     if (threadIdx.x < M_END) s_max[threadIdx.x] = 0;
     __syncthreads();
@@ -351,9 +358,16 @@ __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ 
         // tiled strips: the gap fills the strip kernel cannot take (target beyond 1024 rows, or a band that clips)
         // ... and the end extensions (exact maximum, z-drop) beyond the exact strip variants' reach
         const bool tile_exact = !(jb.flag & EZ_APPROX_MAX);
-        const bool tiled = !strip && strip_scores && !no_tile && (force_kernel == 0 || force_kernel == 6) &&
-                           (tile_exact ? (ext_tile_exact_ok(jb.qlen, jb.tlen, w) && (force_kernel == 6 || jb.qlen + jb.tlen <= TILE_EXACT_MAX_NR))
-                                       : (!(jb.flag & (EZ_EXTZ_ONLY | EZ_RIGHT)) && !jb.reversed && ext_tile_ok(jb.qlen, jb.tlen, w)));
+        int tcls = -1;   // tiled class
+        if (!strip && strip_scores && !no_tile && (force_kernel == 0 || force_kernel == 6) &&
+            (tile_exact ? ext_tile_exact_ok(jb.qlen, jb.tlen, w)
+                        : (!(jb.flag & (EZ_EXTZ_ONLY | EZ_RIGHT)) && !jb.reversed && ext_tile_ok(jb.qlen, jb.tlen, w)))) {
+            const int c = tile_pick < 0 ? TILE_AUTO_CLASS : tile_pick;
+            if (c > 0 && ext_tile_pipe_ok(w, tile_class_s(c), tile_class_nw(c)) &&
+                ext_tile_lds_bytes(jb.qlen, jb.tlen, tile_exact, tile_class_nw(c)) <= TILE_LDS_CAP) tcls = c;
+            else if (!tile_exact || force_kernel == 6 || jb.qlen + jb.tlen <= TILE_EXACT_MAX_NR) tcls = 0;
+        }
+        const bool tiled = tcls >= 0;
         const int sclass = variant * 3 + max(glc, 0);
         const int seqb = ((jb.qlen + 3) & ~3) + ((jb.tlen + 3) & ~3);
         // band kernel: the band (n_col - 1 cells at most) plus the stale left neighbour must fit the slots
@@ -365,11 +379,12 @@ __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ 
         jb.layout = strip ? 1 : tiled ? 3 : bv >= 0 ? 2 : 0;
         const int strip_gl = 16 << max(glc, 0);
         jb.strip_s = max(1, min(16, (jb.tlen + strip_gl - 1) / strip_gl));   // strip height: the window's rows over its lane group
+        if (tiled) jb.strip_s = tile_class_s(tcls);                           // ... or a tile's rows per lane
         const int strip_lanes = (jb.tlen + jb.strip_s - 1) / jb.strip_s;
         jb.qstride = strip ? strip_lanes * jb.strip_s : 128 << max(bv, 0);   // row width of the direction matrix (layouts 1, 2)
         const long long strip_bytes = (long long)(jb.qlen + strip_lanes - 1) * (strip_lanes * jb.strip_s);
         // (the rare exact second pass of a strip window gets its direction matrix from a pool of its own)
-        sz.p = ((strip ? strip_bytes : tiled ? (long long)tile_matrix_bytes(jb.qlen, jb.tlen, w) : bv >= 0 ? n_r * (128 << bv) : n_r * n_col) + 15) & ~15LL;
+        sz.p = ((strip ? strip_bytes : tiled ? (long long)tile_matrix_bytes(jb.qlen, jb.tlen, w, jb.strip_s) : bv >= 0 ? n_r * (128 << bv) : n_r * n_col) + 15) & ~15LL;
         cells += n_r * n_col;
         if (strip) { if (variant == 0) scells[glc] += (long long)jb.qlen * jb.tlen; else xcells += (long long)jb.qlen * jb.tlen; }
         const int stateb = ((6 * jb.tlen + 3) & ~3) + 4 * jb.tlen;
@@ -388,10 +403,11 @@ __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ 
             if (variant) atomicMax(&s_max[M_NR + sclass], (int)n_r);
         }
         else if (tiled) {
-            lid = L_TILE;
-            atomicMax(&s_max[M_TILE], ext_tile_lds_bytes(jb.qlen, jb.tlen, tile_exact));
-            // the boundary between tiles: two buffers of 12 bytes per query column; exact: + H of the last query column per target row
-            sz.st = ((long long)24 * jb.qlen + (tile_exact ? (long long)4 * jb.tlen : 0) + 15) & ~15LL;
+            lid = L_TILE + tcls;
+            atomicMax(&s_max[M_TILE + tcls], ext_tile_lds_bytes(jb.qlen, jb.tlen, tile_exact, tile_class_nw(tcls)));
+            // one wave: the boundary between tiles, two buffers of 12 bytes per query column (pipelined: LDS rings); exact: + H of the
+            // last query column per target row
+            sz.st = ((tcls == 0 ? (long long)24 * jb.qlen : 0) + (tile_exact ? (long long)4 * jb.tlen : 0) + 15) & ~15LL;
         }
         else if (bv >= 0) lid = L_BAND + bv * 4 + bc;
         else lid = redo_list;
@@ -417,7 +433,7 @@ __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ 
     if (threadIdx.x < M_END && s_max[threadIdx.x]) {
         const int k = threadIdx.x;
         atomicMax(k < M_STRIP ? &tot->lds_need[k] : k < M_BAND ? &tot->strip_lds[k - M_STRIP] : k < M_NR ? &tot->band_lds[k - M_BAND] :
-                  k < M_TILE ? &tot->strip_nr[k - M_NR] : &tot->tile_lds, s_max[k]);
+                  k < M_TILE ? &tot->strip_nr[k - M_NR] : &tot->tile_lds[k - M_TILE], s_max[k]);
     }
     // (per-block reduction of the cell counters, one atomic per block)
     __shared__ long long red[5];

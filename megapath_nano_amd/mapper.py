@@ -554,7 +554,9 @@ STAT_NAMES = {0: 'bases', 1: 'minimizers', 2: 'anchors', 3: 'chains', 4: 'dp_job
               37: 'k_chain_dp_ns', 38: 'k_strip16_ns', 39: 'k_strip32_ns', 40: 'k_strip64_ns', 41: 'strip16_cells',
               42: 'strip32_cells', 43: 'strip64_cells', 44: 'sort_records_moved', 45: 'anchors_kept', 46: 'k_compact_ns', 47: 'k_sort_msd_ns', 48: 'k_sort_chunk_ns', 49: 'k_sort_radix_ns',
               50: 'k_seed_filter_ns', 51: 'anchors_emitted', 52: 'k_finish_ns', 53: 'cigar_ops', 54: 'k_stitch_ns', 55: 'k_plan_ns', 56: 'k_layout_ns', 57: 'k_xstrip_ns', 58: 'xstrip_cells', 59: 'anchors_squeezed', 60: 'workers_shed', 61: 'workers', 62: 'k_hit_select_ns', 63: 'reads_hits_on_host',
-              64: 'tile_windows', 65: 'wall_lease_wait_ns', 66: 'ext_groups_side_leased', 67: 'ext_groups_side_own'}
+              64: 'tile_windows', 65: 'wall_lease_wait_ns', 66: 'ext_groups_side_leased', 67: 'ext_groups_side_own',
+              68: 'tile_windows_1w_s16', 69: 'tile_windows_s4_nw8', 70: 'tile_windows_s8_nw4', 71: 'tile_windows_s4_nw16',
+              72: 'tile_wait_giveups'}
 
 
 def last_stats():
