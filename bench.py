@@ -18,12 +18,14 @@ variants; each names itself in config.workload.  Genomes and reads are generated
 once and rotated over the steps (the mapper keeps no state between calls, so a repeated batch costs what a fresh one does).
 
 Rank 0 prints ONE JSON line.  `value` = read bases / wall time of the K timed steps fed from HOST buffers (the read H2D is
-inside the timed call: SURVEY 8d's wall time includes it); `resident_input_gbp_per_min` = as many more steps (--resident-steps) with
-the reads already in HBM, as a side figure.  `roofline` is for the kernel with the largest EXCLUSIVE device time: after the timed region
-a slice of a batch runs through ONE pipeline worker (nothing else on the GPU), which gives every candidate's launch duration
-alone (`alone_ms`) beside its HIP-event span inside the 12-worker pipeline (`in_pipeline_ms`); fractions are given on the HBM
+inside the timed call: SURVEY 8d's wall time includes it).  A plain run does only what `value` needs: it builds the workload, runs the
+W warm-up and K timed steps, writes --dump-outputs and prints the line, whose `roofline` then picks the kernel with the largest
+HIP-event span inside the pipeline.  --full adds, after the timed region: `resident_input_gbp_per_min` = as many more steps
+(--resident-steps) with the reads already in HBM, as a side figure; the single-worker pass, so that `roofline` is for the kernel with the
+largest EXCLUSIVE device time: a slice of a batch runs through ONE pipeline worker (nothing else on the GPU), which gives every candidate's
+launch duration alone (`alone_ms`) beside its HIP-event span inside the 12-worker pipeline (`in_pipeline_ms`); fractions are given on the HBM
 axis (8 TB/s) and on the VALU axis (1.229e12 wave-instructions/s = 1024 SIMDs x 2.4 GHz / 2 cycles, the guide's figure; the
-instruction-mix ceiling is a side note).  `cpu_baseline` times the CPU oracle (oracle/mm2_oracle.c, a port)
+instruction-mix ceiling is a side note); `cpu_baseline` times the CPU oracle (oracle/mm2_oracle.c, a port)
 on a bounded sample of the same reads on this host's cores against an index of >= 1 Gbp; `correctness` checks the output of
 THIS run at the full index size (outside the timed region): truth hit rate from the generator's read origins, the
 independent PAF checker (tests/paf_check.py) over target slices fetched from the index in HBM, per-name counts against the
@@ -508,7 +510,7 @@ def dump_outputs(out_dir, out):
         np.save(os.path.join(out_dir, f'{name}.npy'), a)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=8)
@@ -526,19 +528,26 @@ def main():
     ap.add_argument('--reads-per-step', type=int, default=None)
     ap.add_argument('--mean-len', type=int, default=8000)
     ap.add_argument('--distinct-batches', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run the resident-input steps, the single-worker pass of the roofline, the checks of this '
+                         'run\'s output (correctness) and the CPU baseline; a plain run does none of them')
     ap.add_argument('--resident-steps', '--pcie-steps', dest='resident_steps', type=int, default=None,
-                    help='extra steps with the reads already resident in HBM (the side figure resident_input_gbp_per_min; `value` is fed from host buffers); '
-                         'default: --steps')
-    ap.add_argument('--alone-reads', type=int, default=0, help='reads of the single-worker pass that times every kernel alone (0 = an eighth of a batch; -1 = skip)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-correctness', action='store_true')
+                    help='--full: extra steps with the reads already resident in HBM (the side figure resident_input_gbp_per_min; `value` is fed from '
+                         'host buffers); default: --steps')
+    ap.add_argument('--alone-reads', type=int, default=0,
+                    help='--full: reads of the single-worker pass that times every kernel alone (0 = an eighth of a batch; -1 = skip)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-correctness', action='store_true', help='--full without the checks of this run\'s output')
     ap.add_argument('--mapping-only', action='store_true', help='diagnostic: no base-level extension (the reference\'s mapping_only mode); implies --no-correctness, not the metric')
     ap.add_argument('--cpu-index-genomes', type=int, default=250, help='genomes of the CPU baseline\'s index (250 x 4 Mbp = 1 Gbp)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step returned as DIR/<name>.npy (float64), for comparing two builds output for output')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:
+        args.resident_steps, args.alone_reads = 0, -1
+        args.no_correctness = args.no_cpu_baseline = True
     if args.resident_steps is None:
         args.resident_steps = args.steps
     if args.mapping_only:
@@ -549,7 +558,11 @@ def main():
         args.genomes = cfg_defaults[args.config][0]
     if args.reads_per_step is None:
         args.reads_per_step = cfg_defaults[args.config][1]
+    return args
 
+
+def main():
+    args = parse_args()
     env_world = os.environ.get('WORLD_SIZE')
     if args.gpus > 1 and env_world is None:
         launch_ranks(args.gpus)       # does not return
@@ -635,7 +648,8 @@ def main():
             log(f'  thread {tid} {name!r}{" (main)" if is_main else ""}: {sec / max(1, args.steps):.3f} CPU-s per step '
                 f'(user {(u1 - u0) / max(1, args.steps):.3f}, system {(s1 - s0) / max(1, args.steps):.3f}; context switches per step: '
                 f'{(v1 - v0) / max(1, args.steps):.0f} voluntary, {(n1 - n0) / max(1, args.steps):.0f} involuntary)')
-    if args.config != 'c2':
+    check_counts = args.config != 'c2' and not args.no_correctness   # the composition only the correctness block compares against
+    if check_counts:
         for s in range(args.steps):
             sampled += np.bincount(batches[(args.warmup + s) % n_distinct].truth['genome'], minlength=n)
     host_cpu_max = host_cpu_s
@@ -648,7 +662,7 @@ def main():
         bt = torch.tensor([bases], dtype=torch.int64, device=rd)
         dist.all_reduce(bt, op=dist.ReduceOp.SUM)
         bases = int(bt.item())
-        if args.config != 'c2':
+        if check_counts:
             allreduce(sampled)   # counts are already global (align_and_assign all-reduces them)
     # side figure: the same steps with the reads already resident in HBM (no H2D in the call)
     resident = None

@@ -3,7 +3,7 @@ set -e
 export TMPDIR=/tmp
 T=${1:-r03}; O=gpurun_out/prof_$T
 rm -rf $O; mkdir -p $O
-CMD="python3 bench.py --gpus 1 --steps 20 --warmup 5"
+CMD="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full"
 timeout -k 10 600 $CMD > gpurun_out/${T}_bench_driver_cmd.log 2> gpurun_out/${T}_bench_driver_cmd.err
 echo bench done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $CMD --no-cpu-baseline > $O/stats.log 2>&1

@@ -3,7 +3,7 @@ set -e
 export TMPDIR=/tmp
 T=${1:-r04}; O=gpurun_out/prof_$T
 rm -rf $O; mkdir -p $O
-CMD="python3 bench.py --gpus 1 --steps 20 --warmup 5"
+CMD="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full"
 if [ "${2:-all}" != "stats-only" ]; then
   timeout -k 10 900 $CMD > gpurun_out/${T}_bench_driver_cmd.log 2> gpurun_out/${T}_bench_driver_cmd.err
   echo bench done
@@ -19,7 +19,7 @@ rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE GRBM_GUI_ACTIVE -d
 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $O/pmc3 -- $P > $O/pmc3.log 2>&1
 MPN_PMC_CONFIG=refseq python scripts/pmc_summary.py gpurun_out/${T}_pmc_summary.json 5 $(ls $O/pmc*/*/*counter_collection.csv)
 rm -rf $O/pmc1 $O/pmc2 $O/pmc3; echo pmc done
-C3="python3 bench.py --config c3 --gpus 1 --steps 20 --warmup 5"
+C3="python3 bench.py --config c3 --gpus 1 --steps 20 --warmup 5 --full"
 timeout -k 10 600 $C3 > gpurun_out/${T}_variant_c3.json 2> gpurun_out/${T}_variant_c3.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $C3 --no-cpu-baseline --no-correctness > $O/stats_c3.log 2>&1
 cp $(ls $O/stats/*/*kernel_stats.csv | head -1) gpurun_out/${T}_c3_kernel_stats.csv

@@ -301,6 +301,18 @@ def test_bench_dump_outputs(tmp_path, monkeypatch):
     assert len(pos) == len(set(pos)) > 0 and np.array_equal(got['classes'], out['classes'][pos])
 
 
+def test_bench_plain_run_skips_what_only_full_runs():
+    """A plain bench.py run times its steps and nothing more; --full adds the resident-input steps, the single-worker pass, the
+    output checks and the CPU baseline, each of which its own option still turns off."""
+    import bench
+    plain = bench.parse_args(['--steps', '3', '--resident-steps', '2', '--alone-reads', '512'])
+    assert (plain.full, plain.resident_steps, plain.alone_reads, plain.no_correctness, plain.no_cpu_baseline) == (False, 0, -1, True, True)
+    full = bench.parse_args(['--steps', '3', '--full'])
+    assert (full.resident_steps, full.alone_reads, full.no_correctness, full.no_cpu_baseline) == (3, 0, False, False)
+    full = bench.parse_args(['--steps', '3', '--full', '--resident-steps', '0', '--alone-reads', '-1', '--no-correctness', '--no-cpu-baseline'])
+    assert (full.resident_steps, full.alone_reads, full.no_correctness, full.no_cpu_baseline) == (0, -1, True, True)
+
+
 def test_classify_codes_equals_the_dataframe_classification():
     """filters.classify_codes (integer columns, bench.py --config c2) against filters.human_and_decoy_classify (the mirror of
     megapath_nano.py:1135-1200) on random tables."""
