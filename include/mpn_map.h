@@ -79,6 +79,8 @@ mpn_index *mpn_index_load(const char *path);
  * *next_offset where the next one starts, or -1 after the last (next_offset may be NULL). */
 int mpn_index_save_append(const mpn_index *idx, const char *path);
 mpn_index *mpn_index_load_at(const char *path, int64_t offset, int64_t *next_offset);
+/* The part at `offset` without loading it: returns its number of targets (*bases: their total length; *next_offset as above), or -1 */
+int32_t mpn_index_part_info(const char *path, int64_t offset, int64_t *bases, int64_t *next_offset);
 /* names and lengths of the targets of an index (for a loaded one): name i is copied into buf (cap bytes incl. NUL) */
 int32_t mpn_index_n_seq(const mpn_index *idx);
 int32_t mpn_index_seq_len(const mpn_index *idx, int32_t i);
@@ -186,6 +188,21 @@ int32_t mpn_hits_n_seq(const mpn_hits *h);
 int32_t mpn_hits_seq_len(const mpn_hits *h, int32_t i);
 int32_t mpn_hits_seq_name(const mpn_hits *h, int32_t i, char *buf, int32_t cap);
 int64_t mpn_hits_sam_header(const mpn_hits *h, const char *cmdline, char *buf, int64_t cap);
+
+/* ---- index parts sharded over ranks: the hits of a range of reads move from the rank that holds some parts to the rank that owns
+ * the reads ----------------------------------------------------------------------------------------------
+ * mpn_hits_export: the accumulated (not yet finished) hits of reads [lo, hi) of h as one self-contained byte block: a header (magic,
+ * version, k, want_text, n_reads, the exporter's n_seq and n_parts, payload size, checksum), then per read rep_len, the number of hits
+ * and each hit's fields, with its CIGAR when want_text.  Only what the merge and the text / column writers read travels.
+ * buf == NULL: returns the size needed.  Returns the bytes written, -3 if cap is too small, -1 + mpn_last_error() on bad arguments.
+ * mpn_hits_import: append a block to h, which was created for exactly the block's n_reads reads, the way mpn_map_batch_parts would
+ * have appended the exporter's parts: every target id shifted by the number of targets h already holds, rep_len = the larger, then the
+ * exporter's n_seq targets (names, lens) and n_parts parts added to h.  Blocks of contiguous part blocks imported in part order give
+ * what one accumulator over all parts gives.  A block whose k (once h holds a part) or want_text differs from h's, whose read count,
+ * target count or part count differs, or that is truncated or corrupted is refused (-1 + mpn_last_error()) and h is left unchanged. */
+int64_t mpn_hits_export(const mpn_hits *h, int32_t lo, int32_t hi, void *buf, int64_t cap);
+int mpn_hits_import(mpn_hits *h, const void *buf, int64_t len, int32_t n_parts, int32_t n_seq, const char *const *names,
+                    const int32_t *lens);
 
 /* After mpn_map_batch(_ex) returned -3 the results of that call are kept by the library (process-wide, until the next
  * mapping call): fetch them with larger buffers instead of mapping the batch again.

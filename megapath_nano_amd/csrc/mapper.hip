@@ -821,6 +821,43 @@ static int index_save(const mpn_index *idx, const char *path, bool append) {
 
 mpn_index *mpn_index_load(const char *path) { return mpn_index_load_at(path, 0, nullptr); }
 
+// The header and name table of the part at `offset`, nothing else: what a rank needs to place every part of a saved target set
+// before it loads only its own (index parts sharded over ranks).  Returns n_seq, or -1 + mpn_last_error().
+int32_t mpn_index_part_info(const char *path, int64_t offset, int64_t *bases, int64_t *next_offset) {
+    if (next_offset) *next_offset = -1;
+    if (bases) *bases = 0;
+    if (!path || offset < 0) { set_error("mpn_index_part_info: null path or negative offset"); return -1; }
+    FILE *f = fopen(path, "rb");
+    if (!f) { set_error("mpn_index_part_info: cannot open %s", path); return -1; }
+    auto fail = [&](const char *why) { set_error("mpn_index_part_info: %s (%s)", why, path); fclose(f); return -1; };
+    struct stat sb;
+    if (fstat(fileno(f), &sb) != 0) return fail("cannot stat");
+    if (offset && fseeko(f, (off_t)offset, SEEK_SET) != 0) return fail("cannot seek");
+    char magic[8];
+    int32_t h32[4];
+    int64_t h64[4];
+    if (fread(magic, 1, 8, f) != 8 || fread(h32, 1, sizeof(h32), f) != sizeof(h32) || fread(h64, 1, sizeof(h64), f) != sizeof(h64) ||
+        memcmp(magic, MPN_IDX_MAGIC, 8) != 0)
+        return fail("not an mpn index file");
+    const int32_t n_seq = h32[2], n_nruns = h32[3];
+    const int64_t n_keys = h64[0], n_mz = h64[1], total = h64[2], n_words = h64[3];
+    if (n_seq <= 0 || n_nruns < 0 || n_keys < 0 || n_mz < n_keys || total < 0 || n_words < 0) return fail("corrupt header");
+    int64_t names = 0;
+    if (fseeko(f, (off_t)n_seq * 4, SEEK_CUR) != 0) return fail("truncated file");
+    for (int32_t i = 0; i < n_seq; ++i) {
+        uint32_t l = 0;
+        if (fread(&l, 1, 4, f) != 4 || l > (1u << 20) || fseeko(f, (off_t)l, SEEK_CUR) != 0) return fail("corrupt name table");
+        names += 4 + (int64_t)l;
+    }
+    const int64_t end = offset + 8 + 16 + 32 + (int64_t)n_seq * 4 + names + (int64_t)n_nruns * 16 + n_words * 4 + n_keys * 8 + (n_keys + 1) * 8 +
+                        n_mz * 8;
+    if (end > (int64_t)sb.st_size) return fail("truncated file");
+    fclose(f);
+    if (bases) *bases = total;
+    if (next_offset && end < (int64_t)sb.st_size) *next_offset = end;
+    return n_seq;
+}
+
 // One part of a saved index: the part that starts at byte `offset` of the file; *next_offset = where the next part starts, or
 // -1 after the last one (a file written by mpn_index_save holds one part, one extended by mpn_index_save_append several).
 mpn_index *mpn_index_load_at(const char *path, int64_t offset, int64_t *next_offset) {

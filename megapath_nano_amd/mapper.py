@@ -102,6 +102,12 @@ def _bind():
         lib.mpn_map_batch_parts.restype = ct.c_int
         lib.mpn_hits_set_text.argtypes = [P, ct.c_int32]
         lib.mpn_hits_set_text.restype = None
+        lib.mpn_hits_export.argtypes = [P, ct.c_int32, ct.c_int32, P, ct.c_int64]
+        lib.mpn_hits_export.restype = ct.c_int64
+        lib.mpn_hits_import.argtypes = [P, P, ct.c_int64, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_char_p), P]
+        lib.mpn_hits_import.restype = ct.c_int
+        lib.mpn_index_part_info.argtypes = [ct.c_char_p, ct.c_int64, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]
+        lib.mpn_index_part_info.restype = ct.c_int32
         lib.mpn_hits_finish.argtypes = [P, ct.POINTER(MapOpt), ct.c_int32, ct.POINTER(ct.c_char_p), P, P, P, P, P, ct.c_int64,
                                         ct.POINTER(AlnCols)]
         lib.mpn_hits_finish.restype = ct.c_int64
@@ -216,6 +222,20 @@ class Index:
             raise _ffi.MpnError('mpn_index_load failed: ' + _ffi.last_error())
         self = cls._from_handle(h)
         return self, int(nxt.value)
+
+    @classmethod
+    def part_info(cls, path):
+        """Every part of a saved file without loading any: -> list of (offset, n_seq, bases), in file (= target) order."""
+        lib = _bind()
+        out, off = [], 0
+        while off >= 0:
+            bases, nxt = ct.c_int64(0), ct.c_int64(-1)
+            n = lib.mpn_index_part_info(os.fsencode(path), int(off), ct.byref(bases), ct.byref(nxt))
+            if n < 0:
+                raise _ffi.MpnError('mpn_index_part_info failed: ' + _ffi.last_error())
+            out.append((off, int(n), int(bases.value)))
+            off = int(nxt.value)
+        return out
 
     @classmethod
     def _from_handle(cls, h):
@@ -366,6 +386,27 @@ class PackedReads:
     def seq(self, i):
         return self.buf[self.off[i]:self.off[i] + self.lens[i]]
 
+    def sub(self, lo, hi):
+        """Reads [lo, hi) as a PackedReads of their own: names, bases, qualities and (when this batch has one) the device copy,
+        repacked from offset 0 like a batch of just these reads."""
+        lo, hi = int(lo), int(hi)
+        assert 0 <= lo <= hi <= self.n, (lo, hi, self.n)
+        a = int(self.off[lo]) if hi > lo else 0
+        b = int(self.off[hi - 1] + self.lens[hi - 1]) if hi > lo else 0
+        out = self.__class__.__new__(self.__class__)
+        out.n = hi - lo
+        out.names = self.names[lo:hi]
+        out.buf = np.zeros(b - a + 16, dtype=np.uint8)
+        out.buf[:b - a] = self.buf[a:b]
+        out.off = (self.off[lo:hi] - a).astype(np.int64)
+        out.lens = self.lens[lo:hi].copy()
+        out.qbuf = None
+        if getattr(self, 'qbuf', None) is not None:
+            out.qbuf = np.zeros(b - a + 16, dtype=np.uint8)
+            out.qbuf[:b - a] = self.qbuf[a:b]
+        out._finish(self.dev[0].device if self.dev is not None else None)
+        return out
+
 
 _rows_per_read = 2.0  # running estimate used to size the column arrays (a short guess costs a copy, not a second mapping)
 
@@ -480,6 +521,29 @@ class Hits:
             return lib.mpn_hits_finish(self.h, ct.byref(opt), p.n, p.cnames, p.buf.ctypes.data, q, p.off.ctypes.data, p.lens.ctypes.data,
                                        out, cap, cols)
         return _emit(call, opt, p, want_paf, want_cols)
+
+    def export(self, lo, hi):
+        """The accumulated hits of reads [lo, hi) (before finish()) as one byte block for import_block() -> np.ndarray[uint8]"""
+        lib = _bind()
+        need = lib.mpn_hits_export(self.h, int(lo), int(hi), None, 0)
+        if need < 0:
+            raise _ffi.MpnError('mpn_hits_export: ' + _ffi.last_error())
+        buf = np.empty(need, dtype=np.uint8)
+        r = lib.mpn_hits_export(self.h, int(lo), int(hi), buf.ctypes.data, need)
+        if r != need:
+            raise _ffi.MpnError(f'mpn_hits_export rc={r}: {_ffi.last_error()}')
+        return buf
+
+    def import_block(self, buf, n_parts, names, lens):
+        """Append a block of export() the way add_parts() would have appended the exporter's n_parts parts, whose targets are
+        (names, lens).  Blocks are imported in part order."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        n = len(names)
+        if len(lens) != n:
+            raise ValueError(f'{n} target names but {len(lens)} lengths')
+        cn = (ct.c_char_p * n)(*[x.encode() for x in names])
+        _ffi.check(_bind().mpn_hits_import(self.h, buf.ctypes.data, len(buf), int(n_parts), n, cn, lens.ctypes.data), 'mpn_hits_import')
 
     def targets(self):
         lib = _bind()

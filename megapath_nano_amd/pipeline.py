@@ -4,10 +4,13 @@
 The DataFrame-level mirrors (aligner.Align, reassignment.Reassign) call the same C-ABI entry points; this module is
 what bench.py times and what a multi-GPU run executes per rank.
 """
+import pickle
 import random
+import time
 
 import numpy as np
 
+from . import dist as mdist
 from . import mapper
 from .reassignment import ReassignPlan
 
@@ -53,11 +56,115 @@ class Taxonomy:
         self.n_names, self.n_species = int(n_names), int(n_species)
 
 
+class ShardedIndex:
+    """This rank's share of a target set whose index parts are sharded over the ranks of each read group.
+
+    World W = R x S; rank r is shard s = r % S of read group g = r // S and holds the parts of block s of
+    dist.assign_parts (contiguous, in target order).  Every rank of a group maps the group's whole batch against its own parts;
+    the hits of owner sub-range t go to shard t of the group (mpn_hits_export, dist.exchange_bytes), which imports the blocks
+    in shard order and merges them (mpn_hits_import, mpn_hits_finish).  Because the blocks are contiguous and imported in
+    shard order, the merged accumulator is the one a single process holding every part would have built: same part order,
+    same target ids, the largest rep_len.  The per-shard target lists and part counts are gathered once, here."""
+
+    def __init__(self, parts, rank, world, n_shards, groups=None):
+        """parts: this rank's resident mapper.Index parts, in target order.  groups: dist.shard_groups(world, n_shards), created
+        by every rank (a collective); made here when not given."""
+        self.group_id, self.shard = mdist.index_shard_layout(rank, world, n_shards)
+        self.rank, self.world, self.n_shards = rank, world, n_shards
+        self.parts = list(parts)
+        if groups is None:
+            groups = mdist.shard_groups(world, n_shards)
+        self.group = groups[self.group_id]
+        mine = ([n for p in self.parts for n in p.names], [int(x) for p in self.parts for x in p.lens], len(self.parts))
+        if n_shards == 1:
+            got = [mine]
+        else:
+            blob = np.frombuffer(pickle.dumps(mine), dtype=np.uint8)
+            got = [pickle.loads(b.tobytes()) for b in mdist.exchange_bytes([blob] * n_shards, self.group)]
+        self.targets = [(names, np.asarray(lens, dtype=np.int32)) for names, lens, _ in got]
+        self.n_parts = [int(k) for _, _, k in got]
+        self.times = {}
+
+    def all_targets(self):
+        """(names, lens) of the whole target set: the shards' lists in shard order, = the single-process target order"""
+        return [n for names, _ in self.targets for n in names], np.concatenate([lens for _, lens in self.targets])
+
+    def owner_ranges(self, lens):
+        """The S owner sub-ranges of a group batch with read lengths `lens` (batch indices)."""
+        return mdist.shard_bounds(lens, self.n_shards)
+
+    def map_owned(self, opt, packed, use_device=True):
+        """packed: the whole batch of this rank's read group (the same on every shard of the group).  -> the finished columns of
+        the reads this rank owns (sub-range `shard` of the batch), read_idx relative to the sub-range.  Every rank takes part
+        in the exchange, also with an empty sub-range.  self.times: seconds of map / export / exchange / import / finish, and
+        the bytes this rank sent."""
+        t = {}
+        t0 = time.perf_counter()
+        subs = self.owner_ranges(packed.lens)
+        hits = mapper.Hits(packed, want_text=False)
+        try:
+            hits.add_parts(self.parts, opt, use_device=use_device)
+            t1 = time.perf_counter()
+            blocks = [hits.export(lo, hi) for lo, hi in subs]
+        finally:
+            hits.close()
+        t2 = time.perf_counter()
+        got = blocks if self.n_shards == 1 else mdist.exchange_bytes(blocks, self.group)
+        t3 = time.perf_counter()
+        lo, hi = subs[self.shard]
+        acc = mapper.Hits(packed.sub(lo, hi), want_text=False)
+        try:
+            for s, blk in enumerate(got):
+                acc.import_block(blk, self.n_parts[s], *self.targets[s])
+            t4 = time.perf_counter()
+            _, _, c = acc.finish(opt, want_paf=False, want_cols=True)
+        finally:
+            acc.close()
+        t5 = time.perf_counter()
+        self.times = dict(map_s=t1 - t0, export_s=t2 - t1, exchange_s=t3 - t2, import_s=t4 - t3, finish_s=t5 - t4,
+                          sent_bytes=sum(len(b) for s, b in enumerate(blocks) if s != self.shard), owned=(lo, hi))
+        return c
+
+    def close(self):
+        for p in self.parts:
+            p.close()
+        self.parts = []
+
+
+def own_saved_parts(path, rank, world, n_shards):
+    """The parts of a saved multi-part index (Index.save(append=True), minimap2 -d) that shard `rank` holds: every part is
+    placed from its header alone (Index.part_info), only this shard's block is loaded.  -> list of mapper.Index"""
+    info = mapper.Index.part_info(path)
+    _, shard = mdist.index_shard_layout(rank, world, n_shards)
+    a, b = mdist.assign_parts([bases for _, _, bases in info], n_shards)[shard]
+    return [mapper.Index.load_at(path, info[p][0])[0] for p in range(a, b)]
+
+
+def own_target_parts(make_parts, rank, world, n_shards, k=15, w=10):
+    """The parts cut from a target stream (aligner.iter_target_parts) that shard `rank` holds.  make_parts() starts the stream
+    anew: a first pass only counts the bases of every part, the second builds this shard's block and skips the rest.
+    -> list of mapper.Index"""
+    bases = [sum(len(s) for _, s in part) for part in make_parts()]
+    _, shard = mdist.index_shard_layout(rank, world, n_shards)
+    a, b = mdist.assign_parts(bases, n_shards)[shard]
+    out = []
+    for p, part in enumerate(make_parts()):
+        if a <= p < b:
+            out.append(mapper.Index(part, k=k, w=w))
+        elif p >= b:
+            break
+    return out
+
+
 def align_and_assign(idx, opt, packed, tax, error_rate=0.05, ratio=0.05, as_threshold=0.0, min_alignment_score=0,
                      allreduce=None, rng=None, reassign=True, shard=(0, 1), use_device=True):
     """One step of the hot path for one batch of reads.  Returns dict(read_count, aligned_bp, n_rows, n_relations).
-    With shard=(rank, world) and an all-reduce, `rng` must be seeded identically on every rank (see sharded_tiebreak)."""
-    if isinstance(idx, (list, tuple)):
+    With shard=(rank, world) and an all-reduce, `rng` must be seeded identically on every rank (see sharded_tiebreak).
+    idx: one Index, a list of resident parts, or a ShardedIndex; with the latter, `packed` is the whole batch of this rank's
+    read group and the rows that follow are those of the reads this rank owns."""
+    if isinstance(idx, ShardedIndex):
+        c = idx.map_owned(opt, packed, use_device=use_device)   # columns of this rank's owned reads, merged over every shard
+    elif isinstance(idx, (list, tuple)):
         # a target set held as several index parts (minimap2 -I): every part is mapped, the hits are merged per read like
         # minimap2 --split-prefix merges them (mapper.Hits); column `rid` indexes the concatenated target list
         hits = mapper.Hits(packed, want_text=False)
