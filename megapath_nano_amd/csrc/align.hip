@@ -876,6 +876,7 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
         zero_list_push(z, d_bcnt, (size_t)2 * N_BUCKETS * 4 + sizeof(LayoutTotals));
         zero_list_push(z, dv.used + 1, 8);
         zero_list_push(z, dv.used + 5, 8);
+        zero_list_push(z, dv.used + 8, 16);  // [8] windows walked by ext_bt_wave_kernel, [9] fills failed by ext_ztest_wave_kernel (this group)
         zero_list_push(z, dv.used + 7, 8);
         MPN_HIP_CHECK(zero_regions(z, st));
     }
@@ -1056,29 +1057,46 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
     const int side_lo[2] = {base[L_WG], base[L_BAND + 8]}, side_hi[2] = {base[L_STRIP], base[L_TILE]};
     const int tile_lo[2] = {base[L_TILE], 0}, tile_hi[2] = {base[N_LISTS], 0};
     const int main_lo[2] = {0, base[L_STRIP]}, main_hi[2] = {base[L_WG], base[L_BAND + 8]};
-    auto bt_ztest = [&](const int *lo, const int *hi, hipStream_t s, bool timed) -> int {
-        for (int k = 0; k < 2; ++k) {
-            const int n = hi[k] - lo[k];
-            if (n > 0) hipLaunchKernelGGL(ext_bt_kernel, dim3((n + 63) / 64), dim3(64), 0, s, d_jobs.p, d_order.p + lo[k], n, P.p, OFF.p, CIG.p, d_compact, d_used, d_res.p);
-        }
+    // The walks of the few long windows (tile and side lists) take a wave per window: a launch of two or three waves of lanes
+    // that each chase thousands of dependent loads holds its queue for the longest of them.  The main lists (tens of thousands of
+    // windows that hide each other's latency) and the second pass keep a lane per window.
+    // MPN_EXT_WALK = auto (this) | lane (a lane per window everywhere) | wave (a wave per window everywhere): tests, measurements
+    static const int walk_mode = []() {
+        const char *e = getenv("MPN_EXT_WALK");
+        return !e || !strcmp(e, "auto") ? 0 : !strcmp(e, "lane") ? 1 : !strcmp(e, "wave") ? 2 : 0;
+    }();
+    auto launch_bt = [&](const int32_t *ord, int n, hipStream_t s, bool wave) {
+        if (n <= 0) return;
+        if (wave) hipLaunchKernelGGL(ext_bt_wave_kernel, dim3(n), dim3(64), 0, s, d_jobs.p, ord, n, P.p, OFF.p, CIG.p, d_compact, d_used, d_res.p, d_used + 8);
+        else hipLaunchKernelGGL(ext_bt_kernel, dim3((n + 63) / 64), dim3(64), 0, s, d_jobs.p, ord, n, P.p, OFF.p, CIG.p, d_compact, d_used, d_res.p);
+    };
+    auto bt_ztest = [&](const int *lo, const int *hi, hipStream_t s, bool timed, bool wave) -> int {
+        for (int k = 0; k < 2; ++k) launch_bt(d_order.p + lo[k], hi[k] - lo[k], s, wave);
         MPN_HIP_CHECK(hipGetLastError());
         if (timed) ev.mark(25);
         // z-drop test of the gap-fill CIGARs (the kernel skips the other windows); flagged ones are recomputed with the exact maximum
         for (int k = 0; k < 2; ++k) {
             const int n = hi[k] - lo[k];
-            if (n > 0) hipLaunchKernelGGL(ext_ztest_kernel, dim3((n + 63) / 64), dim3(64), 0, s, d_jobs.p, d_order.p + lo[k], n, prm, d_reads, d_read_off, d_read_len, rv, CIG.p, d_res.p,
-                                          d_redo_ids, d_used + 1, d_probes, d_used + 5);
+            if (n <= 0) continue;
+            if (wave) hipLaunchKernelGGL(ext_ztest_wave_kernel, dim3(n), dim3(64), 0, s, d_jobs.p, d_order.p + lo[k], n, prm, d_reads, d_read_off, d_read_len, rv, CIG.p, d_res.p,
+                                         d_redo_ids, d_used + 1, d_probes, d_used + 5, d_used + 9);
+            else hipLaunchKernelGGL(ext_ztest_kernel, dim3((n + 63) / 64), dim3(64), 0, s, d_jobs.p, d_order.p + lo[k], n, prm, d_reads, d_read_off, d_read_len, rv, CIG.p, d_res.p,
+                                    d_redo_ids, d_used + 1, d_probes, d_used + 5);
         }
         MPN_HIP_CHECK(hipGetLastError());
         if (timed) ev.mark(26);
         return 0;
     };
+    // (the long lists' walks are timed on their own where they run on the worker's own stream, the usual case on few queues:
+    // [STAT_EV_WALK_LONG], and no longer inside [15])
+    if (have_side || have_tiles) ev.mark(15);
     if (have_tiles) {
-        if (bt_ztest(tile_lo, tile_hi, tile_st, false)) return -1;
+        if (bt_ztest(tile_lo, tile_hi, tile_st, false, walk_mode != 1)) return -1;
         if (tile_st != main_st) MPN_HIP_CHECK(hipEventRecord(SL.ev_c, tile_st));
     }
-    if (bt_ztest(side_lo, side_hi, side_st, false)) return -1;
+    if (bt_ztest(side_lo, side_hi, side_st, false, walk_mode != 1)) return -1;
     if (side_st != main_st) MPN_HIP_CHECK(hipEventRecord(SL.ev_b, side_st));
+    if (have_side || have_tiles) ev.mark(STAT_EV_WALK_LONG);
     for (int l = N_LISTS - 1; l >= 0; --l) {  // wide before narrow, strips (the bulk) in the middle
         if (on_side(l)) continue;
         if (l == L_BAND - 1) ev.mark(15);  // the strip launches are timed on their own ([9]): the roofline kernel of bench.py
@@ -1088,17 +1106,19 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
         } else if (launch_list(l, d_order.p + base[l], cnt[l], main_st)) return -1;
     }
     ev.mark(15);
-    if (bt_ztest(main_lo, main_hi, main_st, true)) return -1;
+    if (bt_ztest(main_lo, main_hi, main_st, true, walk_mode == 2)) return -1;
     // (waits between streams this worker holds; the sync below waits for all of them and gives them back)
     if (side_st != main_st) MPN_HIP_CHECK(hipStreamWaitEvent(main_st, SL.ev_b, 0));
     if (tile_st != main_st) MPN_HIP_CHECK(hipStreamWaitEvent(main_st, SL.ev_c, 0));
     unsigned long long *h_used = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(SL.pin_res.p) + ((sizeof(LayoutTotals) + 15) & ~(size_t)15));
-    MPN_HIP_CHECK(hipMemcpyAsync(h_used, d_used, 64, hipMemcpyDeviceToHost, st));
+    MPN_HIP_CHECK(hipMemcpyAsync(h_used, d_used, 80, hipMemcpyDeviceToHost, st));   // ([8], [9]: the wave walk kernels' counters)
     wt.stop_into(g_stats[28]);
     MPN_HIP_CHECK(stream_sync(st));
     wt.stop_into(g_stats[29]);
     // second pass: the windows whose CIGAR failed the z-drop test were listed by the test kernel (in no particular order), and
     // the windows whose largest drop may hide an inversion (mm_test_zdrop's probe: rare; decided here)
+    g_stats[STAT_WALK_WAVE] += (int64_t)h_used[8];
+    g_stats[STAT_WALK_WAVE_FAILED] += (int64_t)h_used[9];
     if (h_used[7]) {   // tiled windows whose hand-off wait gave up (never expected): counted, and the call fails
         g_stats[STAT_TILE_GIVEUPS] += (int64_t)h_used[7];
         set_error("%llu tiled DP windows gave up waiting for their hand-off", (unsigned long long)h_used[7]);
@@ -1184,7 +1204,8 @@ static int run_job_group(const RefView &rv, const mpn_map_opt *opt, int nj_cap, 
                 lo = hi;
             }
             ev.mark(15);
-            hipLaunchKernelGGL(ext_bt_kernel, dim3((nr + 63) / 64), dim3(64), 0, st, d_jobs.p, d_redo.p, nr, P.p, OFF.p, CIG.p, d_compact, d_used, d_res.p);
+            launch_bt(d_redo.p, nr, st, walk_mode == 2);
+            if (walk_mode == 2) g_stats[STAT_WALK_WAVE] += nr;   // (the counter was read back before the second pass; its list has no padding)
             MPN_HIP_CHECK(hipGetLastError());
             ev.mark(25);
             MPN_HIP_CHECK(stream_sync(st));
@@ -2453,7 +2474,7 @@ extern "C" int mpn_ext_dp_batch(const mpn_map_opt *opt, int32_t n, const uint8_t
     MPN_HIP_CHECK(hipMemcpy(tl_slot->pool_jobs.p, jobs.data(), (size_t)n * sizeof(ExtJob), hipMemcpyHostToDevice));
     {
         const unsigned long long cnt = (unsigned long long)n;
-        if (tl_slot->pool_used.ensure(64)) return -1;
+        if (tl_slot->pool_used.ensure(128)) return -1;
         MPN_HIP_CHECK(hipMemcpy(tl_slot->pool_used.as<unsigned long long>() + 3, &cnt, 8, hipMemcpyHostToDevice));
     }
     StreamLease sl(st);

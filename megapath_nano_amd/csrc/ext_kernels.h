@@ -8,6 +8,10 @@
 //   ext_dp_wg_kernel<NT>      fallback (wider bands, windows beyond LDS): Suzuki-Kasahara states u,v,x,y,x2,y2 and the
 //                             H row in LDS or global scratch, one workgroup of 64 (one wave), 256, 512 or 1024 threads per window
 //   ext_bt_kernel, ext_ztest_kernel        one LANE per window: traceback is a serial pointer chase, the z-drop test a CIGAR walk
+//                             (the main lists: tens of thousands of windows per launch hide each other's latency)
+//   ext_bt_wave_kernel, ext_ztest_wave_kernel   one WAVE per window, for the launches of a few long windows (tiled, band, workgroup
+//                             lists): the direction matrix in 64 x 64 patches and the sequences in 1024-base chunks through LDS, the
+//                             lanes test a run of cells / score the columns of a match run at once.  Same rules, same results.
 #pragma once
 #include "mpn_common.h"
 #include "map_types.h"
@@ -1520,6 +1524,34 @@ __global__ __launch_bounds__(64 * NW) void ext_dp_tile_kernel(const ExtJob *__re
 
 
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Traceback.  The rules of one cell, shared by the lane-per-window and the wave-per-window kernel:
+// ksw2's band limits of anti-diagonal rr (the tiled and the band layouts recompute them; layout 0 stores them)
+__device__ __forceinline__ void ext_bt_band(int rr, int qlen, int tlen, int bw, int &st, int &en) {
+    st = 0; en = tlen - 1;
+    if (st < rr - qlen + 1) st = rr - qlen + 1;
+    if (en > rr) en = rr;
+    if (st < (rr - bw + 1) >> 1) st = (rr - bw + 1) >> 1;
+    if (en > (rr + bw) >> 1) en = (rr + bw) >> 1;
+}
+// the state a walk is forced into outside the band [st, en] of its anti-diagonal (-1: inside, the direction byte decides)
+__device__ __forceinline__ int ext_bt_force(int i, int st, int en) {
+    int force_state = -1;
+    if (i < st) force_state = 2;
+    if (i > en) force_state = 1;
+    return force_state;
+}
+// the strip and tiled kernels store the winner's rank: 4 - operand, or the operand itself for right-aligned gaps
+__device__ __forceinline__ int ext_bt_decode(int b, bool rank_is_op) { return rank_is_op ? b : (b & ~7) | (4 - (b & 7)); }
+// the state in which the walk leaves a cell whose (decoded) direction byte is tmp
+__device__ __forceinline__ int ext_bt_next_state(int state, int tmp, int force_state) {
+    if (state == 0) state = tmp & 7;
+    else if (!(tmp >> (state + 2) & 1)) state = 0;
+    if (state == 0) state = tmp & 7;
+    if (force_state >= 0) state = force_state;
+    return state;
+}
+
 // traceback: one lane per job (serial pointer chase; parallelism across jobs hides the latency)
 __global__ __launch_bounds__(64) void ext_bt_kernel(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, int n_jobs,
                                                     const uint8_t *__restrict__ P, const int32_t *__restrict__ OFF,
@@ -1576,53 +1608,38 @@ __global__ __launch_bounds__(64) void ext_bt_kernel(const ExtJob *__restrict__ j
                 for (int q = 0; q < BT_AHEAD; ++q) {
                     if (k != q) continue;             // (stopped earlier)
                     if (i - q < 0 || j - q < 0) continue;
-                    int b = ahead[q];
-                    if (!rank_is_op) b = (b & ~7) | (4 - (b & 7));
+                    const int b = ext_bt_decode(ahead[q], rank_is_op);
                     if ((b & 7) == 0) ++k; else tmp = b;
                 }
                 if (k > 0) { MPN_PUSHOP(0, (uint32_t)k); i -= k; j -= k; }
                 if (k == BT_AHEAD || i < 0 || j < 0) continue;
                 // cell (i, j): a gap wins there (tmp holds its decoded byte)
             } else {
-                tmp = p[(int64_t)(j + i / jb.strip_s) * jb.qstride + i];
-                if (!rank_is_op) tmp = (tmp & ~7) | (4 - (tmp & 7));
+                tmp = ext_bt_decode(p[(int64_t)(j + i / jb.strip_s) * jb.qstride + i], rank_is_op);
             }
         }
         else if (tiled) {
-            int st = 0, en = jb.tlen - 1;
-            if (st < rr - jb.qlen + 1) st = rr - jb.qlen + 1;
-            if (en > rr) en = rr;
-            if (st < (rr - bw + 1) >> 1) st = (rr - bw + 1) >> 1;
-            if (en > (rr + bw) >> 1) en = (rr + bw) >> 1;
-            if (i < st) force_state = 2;
-            if (i > en) force_state = 1;
+            int st, en;
+            ext_bt_band(rr, jb.qlen, jb.tlen, bw, st, en);
+            force_state = ext_bt_force(i, st, en);
             tmp = 0;
             if (force_state < 0) {
                 const int tile = i / (64 * jb.strip_s);
                 if (tile != tg_tile) { tg = tile_geom(tile, jb.qlen, jb.tlen, bw, jb.strip_s); tg_tile = tile; }   // (the walk only descends)
                 const int lt = i - tg.T0;
-                tmp = p[tg.base + (int64_t)((j - tg.jlo) + lt / jb.strip_s) * tg.W + lt];
-                if (!rank_is_op) tmp = (tmp & ~7) | (4 - (tmp & 7));
+                tmp = ext_bt_decode(p[tg.base + (int64_t)((j - tg.jlo) + lt / jb.strip_s) * tg.W + lt], rank_is_op);
             }
         }
         else if (byslot) {
-            int st = 0, en = jb.tlen - 1;
-            if (st < rr - jb.qlen + 1) st = rr - jb.qlen + 1;
-            if (en > rr) en = rr;
-            if (st < (rr - bw + 1) >> 1) st = (rr - bw + 1) >> 1;
-            if (en > (rr + bw) >> 1) en = (rr + bw) >> 1;
-            if (i < st) force_state = 2;
-            if (i > en) force_state = 1;
+            int st, en;
+            ext_bt_band(rr, jb.qlen, jb.tlen, bw, st, en);
+            force_state = ext_bt_force(i, st, en);
             tmp = force_state < 0 ? p[(int64_t)rr * jb.qstride + (i & (jb.qstride - 1))] : 0;
         } else {
-            if (i < off[rr]) force_state = 2;
-            if (i > off_end[rr]) force_state = 1;
+            force_state = ext_bt_force(i, off[rr], off_end[rr]);
             tmp = force_state < 0 ? p[(int64_t)rr * n_col + i - off[rr]] : 0;
         }
-        if (state == 0) state = tmp & 7;
-        else if (!(tmp >> (state + 2) & 1)) state = 0;
-        if (state == 0) state = tmp & 7;
-        if (force_state >= 0) state = force_state;
+        state = ext_bt_next_state(state, tmp, force_state);
         if (state == 0) { MPN_PUSHOP(0, 1); --i; --j; }
         else if (state == 1 || state == 3) { MPN_PUSHOP(2, 1); --i; }
         else { MPN_PUSHOP(1, 1); --j; }
@@ -1650,6 +1667,160 @@ __global__ __launch_bounds__(64) void ext_bt_kernel(const ExtJob *__restrict__ j
         res[jid].n_cigar = n;
         res[jid].cig_pos = (int64_t)pos;
     }
+}
+
+// traceback: one WAVE per window, for the launches of a few long windows (tiled, band and workgroup lists), where a lane per
+// window leaves a handful of lanes chasing thousands of dependent HBM loads while the queue waits for the longest of them.
+// (i, j, state) are uniform.  The wave stages a PATCH of the direction matrix in LDS -- 64 rows of the layout's major index
+// (layouts 1, 3: the step j + i / S; layouts 0, 2: the anti-diagonal) x the 64 target positions [i - 63, i], every lane one
+// column, all 64 loads in flight together -- and walks inside it until the path leaves it.  Inside the patch the lanes test a
+// whole run at once: in state 0 the next 64 cells down the diagonal ("match wins"), in a gap state the next 64 cells along the
+// gap ("the gap continues"); the leading count of the ballot is the length of the run.  The cell that ends a run takes the lane
+// kernel's step (ext_bt_next_state), and so does every cell outside the band (force_state, no byte read).  A patch of the tiled
+// layout stays inside one tile; the geometry is recomputed when the walk descends into the next tile.
+__global__ __launch_bounds__(64) void ext_bt_wave_kernel(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, int n_jobs,
+                                                         const uint8_t *__restrict__ P, const int32_t *__restrict__ OFF,
+                                                         uint32_t *__restrict__ CIG, uint32_t *__restrict__ COMPACT,
+                                                         unsigned long long *__restrict__ compact_used, ExtRes *__restrict__ res,
+                                                         unsigned long long *__restrict__ n_windows) {
+    constexpr int PR = 64, PC = 64;   // patch: rows of the major index x target positions
+    __shared__ uint8_t patch[PR * PC];
+    __shared__ int32_t s_lim[2][PR];  // layout 0: band start / end of the patch's anti-diagonals
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= n_jobs) return;
+    const int jid = order[blockIdx.x];
+    if (jid < 0) return;  // padding of a strip launch list
+    if (lane == 0) atomicAdd(n_windows, 1ULL);   // (the walk_wave_windows statistic: windows, not list entries)
+    const ExtJob jb = jobs[jid];
+    const ExtRes r = res[jid];
+    if (!r.do_bt) { if (lane == 0) res[jid].cig_pos = 0; return; }
+    const int layout = jb.layout, S = jb.strip_s > 0 ? jb.strip_s : 1, R = 64 * S;
+    const int n_col = jb.n_col, n_r = jb.qlen + jb.tlen - 1;
+    const uint8_t *p = P + jb.p_off;
+    const int32_t *off = OFF + 2 * jb.row_off, *off_end = off + n_r;
+    const bool rank_is_op = (jb.flag & EZ_RIGHT) != 0 || layout == 0 || layout == 2;   // (layouts 0 and 2 store the operand)
+    const int bw = jb.w < 0 ? (jb.tlen > jb.qlen ? jb.tlen : jb.qlen) : jb.w;
+    const bool rev_cigar = (jb.flag & EZ_REV_CIGAR) != 0;
+    uint32_t *cend = CIG + jb.cig_off;
+    const int cap = jb.qlen + jb.tlen + 2;
+    uint32_t *cbeg = cend - cap;
+    int n = 0, i = r.bt_i, j = r.bt_j, state = 0;
+    uint32_t cur_op = 0xf, cur_len = 0;
+    // (the walk's variables are uniform: lane 0 writes the operations)
+#define MPN_FLUSH() do { if (cur_len) { if (lane == 0) { if (rev_cigar) cbeg[n] = cur_len << 4 | cur_op; else cend[-1 - n] = cur_len << 4 | cur_op; } ++n; } } while (0)
+#define MPN_PUSHOP(OP, LEN) do { if ((uint32_t)(OP) == cur_op) cur_len += (LEN); else { MPN_FLUSH(); cur_op = (OP); cur_len = (LEN); } } while (0)
+    TileGeom tg{};
+    int tg_tile = -1;
+    bool p_valid = false;
+    int p_mtop = 0, p_itop = 0;   // the patch holds majors (p_mtop - 64, p_mtop] x target positions (p_itop - 64, p_itop] (layout 3: of tile tg_tile)
+    auto major_of = [&](int ii, int jj) -> int {
+        if (layout == 1) return jj + ii / S;
+        if (layout == 3) return (jj - tg.jlo) + (ii - tg.T0) / S;   // (a cell of tile tg_tile)
+        return ii + jj;
+    };
+    // where cell (ii, jj) lies in the patch; -1: not staged
+    auto patch_slot = [&](int ii, int jj) -> int {
+        if (!p_valid || ii < 0 || jj < 0) return -1;
+        if (layout == 3 && ii < tg.T0) return -1;   // (the next tile down)
+        // (layout 3: a cell with jj < tg.jlo has a negative major and may land on a zero-filled row, which decodes as "match" under
+        // EZ_RIGHT: such a cell is always outside the band (jlo = T0 - w), so every caller masks it with force_of before using it)
+        const int mrel = p_mtop - major_of(ii, jj), irel = p_itop - ii;
+        return (mrel >= 0 && mrel < PR && irel >= 0 && irel < PC) ? mrel * PC + irel : -1;
+    };
+    // force_state of a cell (layout 0: of a cell whose anti-diagonal the patch holds)
+    auto force_of = [&](int ii, int jj) -> int {
+        if (layout == 1) return -1;
+        if (layout == 0) { const int mrel = p_mtop - (ii + jj); return ext_bt_force(ii, s_lim[0][mrel], s_lim[1][mrel]); }
+        int st, en;
+        ext_bt_band(ii + jj, jb.qlen, jb.tlen, bw, st, en);
+        return ext_bt_force(ii, st, en);
+    };
+    // stage the patch whose corner is cell (i, j).  Loads stay inside the matrix: majors in [0, this cell's], target positions in
+    // [0, i] (layout 3: of this tile; layout 0: inside the stored band of their anti-diagonal)
+    auto stage = [&]() {
+        __syncthreads();
+        p_valid = true; p_itop = i; p_mtop = major_of(i, j);
+        const int ii = p_itop - lane;
+        if (layout == 0) {
+            const int m = p_mtop - lane;
+            s_lim[0][lane] = m >= 0 ? off[m] : 0;
+            s_lim[1][lane] = m >= 0 ? off_end[m] : -1;
+            __syncthreads();
+        }
+        uint8_t v[PR];
+#pragma unroll
+        for (int q = 0; q < PR; ++q) {
+            const int m = p_mtop - q;
+            bool ok = m >= 0 && ii >= 0;
+            int64_t a = 0;
+            if (layout == 1) a = (int64_t)m * jb.qstride + ii;
+            else if (layout == 3) { ok = ok && ii >= tg.T0; a = tg.base + (int64_t)m * tg.W + (ii - tg.T0); }
+            else if (layout == 2) a = (int64_t)m * jb.qstride + (ii & (jb.qstride - 1));
+            else {
+                const int lo = s_lim[0][q], hi = s_lim[1][q];
+                ok = ok && ii >= lo && ii <= hi && ii - lo < n_col;
+                a = (int64_t)m * n_col + (ii - lo);
+            }
+            v[q] = ok ? p[a] : (uint8_t)0;
+        }
+#pragma unroll
+        for (int q = 0; q < PR; ++q) patch[q * PC + lane] = v[q];
+        __syncthreads();
+    };
+    while (i >= 0 && j >= 0) {
+        if (layout == 0 && !(p_valid && p_mtop - (i + j) >= 0 && p_mtop - (i + j) < PR)) stage();   // (its band limits come with the patch)
+        const int force_state = force_of(i, j);
+        if (force_state >= 0) {
+            // outside the band no byte is read: the run of cells forced the same way, in one step
+            const int di = force_state == 1 ? 1 : 0, dj = 1 - di;
+            const int ii = i - lane * di, jj = j - lane * dj;
+            bool go = ii >= 0 && jj >= 0;
+            if (go && layout == 0) go = p_mtop - (ii + jj) < PR;
+            go = go && force_of(ii, jj) == force_state;
+            const unsigned long long mask = __ballot(go);
+            const int k = ~mask ? __builtin_ctzll(~mask) : 64;   // (>= 1: lane 0 is this cell)
+            state = force_state;
+            MPN_PUSHOP(di ? 2 : 1, (uint32_t)k);
+            i -= k * di; j -= k * dj;
+            continue;
+        }
+        if (layout == 3 && i / R != tg_tile) { tg_tile = i / R; tg = tile_geom(tg_tile, jb.qlen, jb.tlen, bw, S); p_valid = false; }   // (the walk only descends)
+        if (patch_slot(i, j) < 0) stage();
+        {   // the run from this cell on: down the diagonal while the match wins, along a gap while it continues
+            const int di = (state == 2 || state == 4) ? 0 : 1, dj = (state == 1 || state == 3) ? 0 : 1;
+            const int ii = i - lane * di, jj = j - lane * dj;
+            int slot = patch_slot(ii, jj);
+            if (slot >= 0 && force_of(ii, jj) >= 0) slot = -1;
+            const int b = ext_bt_decode(patch[slot >= 0 ? slot : 0], rank_is_op);
+            const bool go = slot >= 0 && (state == 0 ? (b & 7) == 0 : (b >> (state + 2) & 1) != 0);
+            const unsigned long long mask = __ballot(go);
+            const int k = ~mask ? __builtin_ctzll(~mask) : 64;
+            if (k > 0) {
+                MPN_PUSHOP(state == 0 ? 0 : di ? 2 : 1, (uint32_t)k);
+                i -= k * di; j -= k * dj;
+                continue;
+            }
+        }
+        // the cell that ends a run: the lane kernel's step
+        state = ext_bt_next_state(state, ext_bt_decode(patch[patch_slot(i, j)], rank_is_op), -1);
+        if (state == 0) { MPN_PUSHOP(0, 1); --i; --j; }
+        else if (state == 1 || state == 3) { MPN_PUSHOP(2, 1); --i; }
+        else { MPN_PUSHOP(1, 1); --j; }
+    }
+    if (i >= 0) MPN_PUSHOP(2, (uint32_t)(i + 1));
+    if (j >= 0) MPN_PUSHOP(1, (uint32_t)(j + 1));
+    MPN_FLUSH();
+#undef MPN_PUSHOP
+#undef MPN_FLUSH
+    // the ops in forward order into the compact pool: one atomic per window (a launch holds few windows), the copy by all lanes
+    unsigned long long base = 0;
+    if (lane == 0 && n) base = atomicAdd(compact_used, (unsigned long long)n);
+    base = (unsigned long long)__shfl((long long)base, 0);
+    __threadfence_block();
+    __syncthreads();   // (lane 0's scratch writes are visible to the wave)
+    const uint32_t *src = rev_cigar ? cbeg : cend - n;
+    for (int q = lane; q < n; q += 64) COMPACT[base + q] = src[q];
+    if (lane == 0) { res[jid].n_cigar = n; res[jid].cig_pos = (int64_t)base; }
 }
 
 // z-drop test of a finished gap-fill CIGAR (minimap2 mm_test_zdrop without the inversion probe): one lane per job
@@ -1733,6 +1904,160 @@ __global__ __launch_bounds__(64) void ext_ztest_kernel(const ExtJob *__restrict_
         return;
     }
     report(over);
+}
+
+// z-drop test, one WAVE per window (the launches of a few long windows; the verdicts, the redo list's members and the probes are the
+// lane kernel's).  The CIGAR-only bound is a wave reduction over the operations.  For the walk the two sequences are staged in LDS
+// as 0..4 codes, ZW bases at a time (a lane decodes one 16-base target word; an ambiguous run that touches the word sends it
+// through ref_code), the operations come 64 at a time into registers, and the columns of a match operation are scored 64 at a
+// time: prefix sum of the column scores, the running maximum before each column with the LATER position on ties (in-run
+// positions win over the incoming maximum: the lane kernel replaces it on >=), the largest drop with the EARLIEST position on
+// ties.  Inside a match run i and j advance together, so diff is |(i - max_i) - (j - max_j)| against the incoming maximum and 0
+// against one of the run itself.
+__global__ __launch_bounds__(64) void ext_ztest_wave_kernel(const ExtJob *__restrict__ jobs, const int32_t *__restrict__ order, int n_jobs,
+                                                            ExtParams prm, const uint8_t *__restrict__ reads,
+                                                            const int64_t *__restrict__ read_off, const int32_t *__restrict__ read_len,
+                                                            RefView rv,
+                                                            const uint32_t *__restrict__ CIG, ExtRes *__restrict__ res,
+                                                            int32_t *__restrict__ redo_ids, unsigned long long *__restrict__ n_redo,
+                                                            InvProbe *__restrict__ probes, unsigned long long *__restrict__ n_probe,
+                                                            unsigned long long *__restrict__ n_failed) {
+    constexpr int ZW = 1024;   // staged bases per sequence: 16 per lane
+    __shared__ uint8_t s_t[ZW], s_q[ZW];
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= n_jobs) return;
+    const int jid = order[blockIdx.x];
+    if (jid < 0) return;  // padding of a strip launch list
+    const ExtJob jb = jobs[jid];
+    if (!(jb.flag & EZ_APPROX_MAX)) return;  // only gap fills are tested
+    const ExtRes r = res[jid];
+    const int zmin = prm.zdrop_thres < prm.zdrop_inv ? prm.zdrop_thres : prm.zdrop_inv;
+    const int n_cig = r.n_cigar;
+    const uint32_t *cig = CIG + jb.cig_off - n_cig;  // gap-fill jobs are never REV_CIGAR
+    if ((jb.layout == 1 || jb.layout == 3) && r.do_bt && !r.zdropped) {   // the CIGAR-only bound (ext_ztest_kernel)
+        long long m_cols = 0, extra = 0;
+        for (int c = lane; c < n_cig; c += 64) {
+            const uint32_t op = cig[c] & 0xf;
+            const int64_t len = cig[c] >> 4;
+            if (op == 0) m_cols += len;
+            else if (op == 1 || op == 2) {
+                const int64_t w1 = prm.q + prm.e * len, w2 = prm.q2 + prm.e2 * len;
+                extra += w1 - (w1 < w2 ? w1 : w2);
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { m_cols += __shfl_xor(m_cols, d); extra += __shfl_xor(extra, d); }
+        if ((int64_t)prm.sc_mch * m_cols - r.score + extra <= zmin) { if (lane == 0) res[jid].zcode = 0; return; }
+    }
+    const int64_t roff = read_off[jb.read];
+    const int32_t rlen = read_len[jb.read];
+    const int64_t g0 = rv.seq_off[jb.rid] + jb.ts;
+    int32_t score = 0, mx = INT32_MIN, max_i = -1, max_j = -1, i = 0, j = 0, max_zdrop = 0;
+    int32_t p00 = -1, p01 = -1, p10 = -1, p11 = -1;   // where the largest drop starts (the running maximum) and ends
+    int t_base = 0, q_base = 0;
+    bool staged = false;
+    // codes of target positions [t_base, t_base + ZW) and query positions [q_base, q_base + ZW) of the window (4 past their ends)
+    auto stage = [&](int ti, int qi) {
+        __syncthreads();
+        staged = true;
+        t_base = (int)(((g0 + ti) & ~(int64_t)15) - g0);   // (word-aligned in the concatenated targets; may be below 0)
+        q_base = qi;
+        {
+            const int64_t gw = g0 + t_base + 16 * lane;    // this lane's word
+            uint32_t word = 0;
+            bool slow = false;
+            if (gw < g0 + jb.tlen) {
+                word = rv.seq2[gw >> 4];
+                if (rv.n_runs > 0) {   // an ambiguous run touches the word iff the last run that starts at or before its last base ends after its first
+                    int lo = 0, hi = rv.n_runs;
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (rv.nrun_s[mid] <= gw + 15) lo = mid + 1; else hi = mid; }
+                    slow = lo > 0 && rv.nrun_e[lo - 1] > gw;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const int64_t g = gw + b;
+                int c = (int)((word >> (2 * b)) & 3u);
+                if (g < g0 || g >= g0 + jb.tlen) c = 4;
+                else if (slow) c = ref_code(rv, g);
+                s_t[16 * lane + b] = (uint8_t)c;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < ZW / 64; ++u) {
+            const int x = q_base + 64 * u + lane;
+            s_q[64 * u + lane] = x < jb.qlen ? ext_qbase(reads, roff, rlen, jb.rev, jb.qs + x) : (uint8_t)4;
+        }
+        __syncthreads();
+    };
+    for (int c0 = 0; c0 < n_cig; c0 += 64) {
+        const uint32_t mine = c0 + lane < n_cig ? cig[c0 + lane] : 0u;
+        const int nc = n_cig - c0 < 64 ? n_cig - c0 : 64;
+        for (int c = 0; c < nc; ++c) {
+            const uint32_t word = (uint32_t)__shfl((int)mine, c);
+            const uint32_t op = word & 0xf, len = word >> 4;
+            if (op == 0) {
+                for (uint32_t l0 = 0; l0 < len; l0 += 64) {
+                    const int cnt = len - l0 < 64 ? (int)(len - l0) : 64, ci = i + (int)l0, cj = j + (int)l0;
+                    if (!staged || ci < t_base || ci + cnt > t_base + ZW || cj < q_base || cj + cnt > q_base + ZW) stage(ci, cj);
+                    const int ct = s_t[(ci - t_base + lane) & (ZW - 1)], cq = s_q[(cj - q_base + lane) & (ZW - 1)];
+                    const int sc1 = lane < cnt ? ((ct == 4 || cq == 4) ? prm.sc_n : ct == cq ? prm.sc_mch : prm.sc_mis) : 0;
+                    int sc = sc1;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(sc, d); if (lane >= d) sc += o; }
+                    sc += score;   // the score after this lane's column
+                    // running maximum over the run's columns up to this lane: value and (later on ties) column
+                    int mv = lane < cnt ? sc : INT32_MIN, mi = lane;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const int ov = __shfl_up(mv, d), oi = __shfl_up(mi, d);
+                        if (lane >= d && ov > mv) { mv = ov; mi = oi; }
+                    }
+                    // the maximum BEFORE this lane's column: of the run (in-run wins ties), else the incoming one
+                    int bv = __shfl_up(mv, 1), bi = __shfl_up(mi, 1);
+                    if (lane == 0) { bv = INT32_MIN; bi = -1; }
+                    const bool in_run = bi >= 0 && bv >= mx;
+                    const int d0 = (ci - max_i) - (cj - max_j), diff = in_run ? 0 : d0 < 0 ? -d0 : d0;
+                    const int before = in_run ? bv : mx;
+                    int z = 0;
+                    if (lane < cnt && sc < before) z = before - sc - diff * prm.e;
+                    int zbest = z;
+#pragma unroll
+                    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(zbest, d); zbest = o > zbest ? o : zbest; }
+                    if (zbest > max_zdrop) {
+                        const int src = __builtin_ctzll(__ballot(z == zbest));   // the earliest column with the largest drop
+                        const int s_in = __shfl((int)in_run, src), s_bi = __shfl(bi, src);
+                        max_zdrop = zbest;
+                        p00 = s_in ? ci + s_bi : max_i; p01 = s_in ? cj + s_bi : max_j;
+                        p10 = ci + src; p11 = cj + src;
+                    }
+                    const int ev = __shfl(mv, cnt - 1), ei = __shfl(mi, cnt - 1);
+                    score = __shfl(sc, cnt - 1);
+                    if (ev >= mx) { mx = ev; max_i = ci + ei; max_j = cj + ei; }
+                }
+                i += len; j += len;
+            } else if (op == 1 || op == 2) {
+                score -= prm.q + prm.e * (int)len;
+                if (op == 1) j += len; else i += len;
+                if (score < mx) {
+                    const int li = i - max_i, lj = j - max_j, diff = li > lj ? li - lj : lj - li;
+                    const int z = mx - score - diff * prm.e;
+                    if (z > max_zdrop) { max_zdrop = z; p00 = max_i; p01 = max_j; p10 = i; p11 = j; }
+                } else { mx = score; max_i = i; max_j = j; }
+            }
+        }
+    }
+    if (lane != 0) return;
+    const int over = max_zdrop > prm.zdrop_thres ? 1 : 0;
+    const int q_len = p11 - p01, t_len = p10 - p00;
+    if (max_zdrop > prm.zdrop_inv && q_len < prm.max_gap && t_len < prm.max_gap && q_len > 0 && t_len > 0) {
+        res[jid].zcode = over;
+        probes[atomicAdd(n_probe, 1ULL)] = InvProbe{jid, p00, p01, p10, p11, over};
+        atomicAdd(n_failed, 1ULL);   // (the walk_wave_failed statistic: fills this kernel sent to the second pass or to the probe)
+        return;
+    }
+    res[jid].zcode = over;
+    if (over) { redo_ids[atomicAdd(n_redo, 1ULL)] = jid; atomicAdd(n_failed, 1ULL); }
 }
 
 }  // namespace mpn

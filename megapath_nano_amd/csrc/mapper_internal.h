@@ -83,12 +83,16 @@ struct HostChains {
     void chain_order(int i, int32_t *order, int64_t *src) const;
 };
 
-constexpr int MPN_NSTATS = 73;
+constexpr int MPN_NSTATS = 76;
 constexpr int STAT_LEASE_WAIT = 65;   // wall time the workers waited for a free submission stream (StreamLease)
 // extension groups with side work (long windows, tiles): [66] it got leased side streams, [67] it ran on the worker's own stream
 constexpr int STAT_SIDE_LEASED = 66, STAT_SIDE_OWN = 67;
 // tiled DP windows per tiled class ([68] one wave, [69..71] pipelined, plan_kernels.h tile_class_*), [72] hand-off waits given up (must be 0)
 constexpr int STAT_TILE_CLASS = 68, STAT_TILE_GIVEUPS = 72;
+// [73] windows whose traceback took a wave (ext_bt_wave_kernel), [74] event span of the long lists' traceback + z-drop test where they
+// run on the worker's own stream (time that [15] held before)
+// [75] gap fills that ext_ztest_wave_kernel failed (listed for the second pass, or handed to the inversion probe)
+constexpr int STAT_WALK_WAVE = 73, STAT_EV_WALK_LONG = 74, STAT_WALK_WAVE_FAILED = 75;
 extern thread_local int64_t g_stats[MPN_NSTATS];
 
 // 2-bit packing of 0..4 codes (N -> 0 + run list)

@@ -620,7 +620,12 @@ STAT_NAMES = {0: 'bases', 1: 'minimizers', 2: 'anchors', 3: 'chains', 4: 'dp_job
               50: 'k_seed_filter_ns', 51: 'anchors_emitted', 52: 'k_finish_ns', 53: 'cigar_ops', 54: 'k_stitch_ns', 55: 'k_plan_ns', 56: 'k_layout_ns', 57: 'k_xstrip_ns', 58: 'xstrip_cells', 59: 'anchors_squeezed', 60: 'workers_shed', 61: 'workers', 62: 'k_hit_select_ns', 63: 'reads_hits_on_host',
               64: 'tile_windows', 65: 'wall_lease_wait_ns', 66: 'ext_groups_side_leased', 67: 'ext_groups_side_own',
               68: 'tile_windows_1w_s16', 69: 'tile_windows_s4_nw8', 70: 'tile_windows_s8_nw4', 71: 'tile_windows_s4_nw16',
-              72: 'tile_wait_giveups'}
+              72: 'tile_wait_giveups',
+              # ev_ext_walk_long_ns: traceback + z-drop test of the tile and side lists where they run on the worker's own
+              # stream (MPN_KERNEL_EVENTS on: two more events per extension group); ev_ext_dp_ns held this time before and no
+              # longer does.  Where the side / tile work got leased streams the span is ~0 and their walks are in no slot.
+              73: 'walk_wave_windows', 74: 'ev_ext_walk_long_ns',
+              75: 'walk_wave_failed'}   # gap fills the wave z-drop test failed (second pass or inversion probe)
 
 
 def last_stats():
