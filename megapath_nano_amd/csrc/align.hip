@@ -1560,7 +1560,13 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
         const RefView rv{idx->d_seq2.p, idx->d_seq_off.p, idx->d_nrun_s.p, idx->d_nrun_e.p, idx->n_nruns};
         const HostSeqs hseqs{seqs, seq_off, seq_len, idx->seq_off.data()};
         std::vector<int32_t> sr_base((size_t)n + 1, 0);
-        for (int round = 0; round < 64; ++round) {
+        // a round aligns every pending hit; a hit cut at a z-drop leaves a remainder with fewer anchors for the next round (minimap2 aligns it
+        // in the same loop), so round k sees no hit with more anchors than the most any read has, minus k, and the last round allowed
+        // finds nothing pending: one 60-kb read under scores that z-drop every few hundred bases takes well over a hundred rounds
+        int64_t max_rounds = 1;
+        for (int i = 0; i < n; ++i) max_rounds = std::max<int64_t>(max_rounds, (int64_t)rs[i].n_a + 1);
+        bool rounds_done = false;
+        for (int64_t round = 0; round < max_rounds; ++round) {
             wt.stop_into(g_stats[23]);
             // the hits to align in this round: 40 bytes each go up; their windows are planned, laid out, computed, traced back and
             // stitched on the device
@@ -1576,7 +1582,7 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
             }, 2);
             for (int i = 0; i < n; ++i) sr_base[(size_t)i + 1] = sr_base[(size_t)i] + (int32_t)rs[i].pending.size();
             const int n_sr = sr_base[(size_t)n];
-            if (n_sr == 0) { wt.stop_into(g_stats[20]); break; }
+            if (n_sr == 0) { wt.stop_into(g_stats[20]); rounds_done = true; break; }
             std::vector<int64_t> cap_t((size_t)std::max(1, n_threads), 0);
             if (SL.pin_pregs.ensure((size_t)n_sr * sizeof(PlanReg) + 64) || SL.pool_pregs.ensure((size_t)n_sr * sizeof(PlanReg) + 16) ||
                 SL.pool_psum.ensure((size_t)n_sr * sizeof(PlanSum) + 16) || SL.pool_sregs.ensure((size_t)n_sr * sizeof(StitchReg) + 16) || SL.pool_used.ensure(128))
@@ -1622,6 +1628,7 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
             if (stitch_and_finish(idx, opt, rs, n, seq_len, dv, rd, sr_base, d_seqs.p, d_off.p, d_len.p, n_threads, st)) return -1;
             wt.stop_into(g_stats[22]);
         }
+        if (!rounds_done) { set_error("hits still unaligned after the last alignment round"); return -1; }   // (never: no hit without CIGAR leaves quietly)
         // ---- inversions (mm_align1_inv): where a hit was cut at an inversion, the read's gap between the two pieces is aligned
         // to the target's gap on the opposite strand.  Rare; the candidates are gathered on the host, the local alignment that
         // locates the inverted segment runs on the SSW kernels, its extension is one more (tiny) round of the DP pipeline.

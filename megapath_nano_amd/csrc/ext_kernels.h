@@ -1149,8 +1149,20 @@ __host__ __device__ inline bool ext_tile_ok(int qlen, int tlen, int w) {
 // band limits come from a second table -- and the rule is applied over the anti-diagonals in order after the last tile, like the
 // exact strip variants do.  RIGHT: right-aligned gaps (the left extension).
 // LDS: query | score table | [NW > 1: hand-off counters | rings] | BEST[n_r] | (st, en)[n_r].
-__host__ __device__ inline bool ext_tile_exact_ok(int qlen, int tlen, int w) {
-    return qlen > 0 && tlen > 0 && w >= 1 && tlen <= 8191 && qlen <= 16384 && qlen + tlen - 1 <= 14000;
+// The slot's word keeps H + 32768 in 16 bits, so H of every in-band cell must be a 16-bit number (like ext_strip_exact_ok):
+//  * above, H(t, j) <= match * min(t + 1, j + 1);
+//  * below, the path "m = min(t, j) + 1 diagonal steps, then one gap of d = |t - j|" stays in the band of an in-band cell and costs at
+//    most worst * m + gap(d), worst = the lowest substitution score, with m <= min(qlen, tlen) and m + d <= max(qlen, tlen); against
+//    either linear gap cost that is largest at m = min(qlen, tlen) or at m = 0, and the real (concave) gap cost is below both.
+// At match 2, mismatch 4, gaps (4,2 / 24,1) the geometry bound alone gives H in [-28025, 14000]: no window is refused there.
+__host__ __device__ inline bool ext_tile_exact_ok(int mch, int mis, int amb, int q, int e, int q2, int e2, int qlen, int tlen, int w) {
+    if (!(qlen > 0 && tlen > 0 && w >= 1 && tlen <= 8191 && qlen <= 16384 && qlen + tlen - 1 <= 14000)) return false;
+    const int mn = qlen < tlen ? qlen : tlen, mx = qlen > tlen ? qlen : tlen;
+    int worst = mis < amb ? -mis : -amb;
+    if (worst < 0) worst = 0;
+    const int g1 = worst * mn + q + e * (mx - mn + 1), g1b = q + e * (mx + 1), g2 = worst * mn + q2 + e2 * (mx - mn + 1), g2b = q2 + e2 * (mx + 1);
+    const int lo1 = g1 > g1b ? g1 : g1b, lo2 = g2 > g2b ? g2 : g2b;
+    return mch * mn < 32000 && (lo1 < lo2 ? lo1 : lo2) < 32000;
 }
 // The pipelined variant's hand-off: wave k's ring feeds wave k + 1 (mod NW), C = TILE_RING_COLS / NW columns of (v, x, H) each, with
 // two monotonic item counters per ring (produced, consumed).  Waiting cannot close a cycle while the rings together hold more than
@@ -1182,7 +1194,7 @@ __device__ __forceinline__ void ext_tile_body(const ExtJob &jb, const int jid, c
     ExtRes out;
     out.max = 0; out.zdropped = 0; out.max_q = out.max_t = out.mqe_t = -1; out.mqe = NEG_INF; out.score = NEG_INF;
     out.reach_end = 0; out.n_cigar = 0; out.r_done = -1; out.bt_i = out.bt_j = -1; out.do_bt = 0; out.zcode = 0; out.cig_pos = 0;
-    if (!(EXACT ? ext_tile_exact_ok(qlen, tlen, w) : ext_tile_ok(qlen, tlen, w)) || -prm.sc_mis > 2 * (q + e) ||
+    if (!(EXACT ? ext_tile_exact_ok(prm.sc_mch, prm.sc_mis, prm.sc_n, prm.q, prm.e, prm.q2, prm.e2, qlen, tlen, w) : ext_tile_ok(qlen, tlen, w)) || -prm.sc_mis > 2 * (q + e) ||
         (NW > 1 && !ext_tile_pipe_ok(w, S, NW))) { if (tid == 0) res[jid] = out; return; }
     // ---- the cell's constants (see ext_strip_exact) ----
     constexpr int RS = RIGHT ? 0 : 4, RA = RIGHT ? 1 : 3, RB = 2, RA2 = RIGHT ? 3 : 1, RB2 = RIGHT ? 4 : 0;

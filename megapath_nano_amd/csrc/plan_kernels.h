@@ -360,7 +360,7 @@ __global__ __launch_bounds__(256) void job_classify_kernel(ExtJob *__restrict__ 
         const bool tile_exact = !(jb.flag & EZ_APPROX_MAX);
         int tcls = -1;   // tiled class
         if (!strip && strip_scores && !no_tile && (force_kernel == 0 || force_kernel == 6) &&
-            (tile_exact ? ext_tile_exact_ok(jb.qlen, jb.tlen, w)
+            (tile_exact ? ext_tile_exact_ok(prm.sc_mch, prm.sc_mis, prm.sc_n, prm.q, prm.e, prm.q2, prm.e2, jb.qlen, jb.tlen, w)
                         : (!(jb.flag & (EZ_EXTZ_ONLY | EZ_RIGHT)) && !jb.reversed && ext_tile_ok(jb.qlen, jb.tlen, w)))) {
             const int c = tile_pick < 0 ? TILE_AUTO_CLASS : tile_pick;
             if (c > 0 && ext_tile_pipe_ok(w, tile_class_s(c), tile_class_nw(c)) &&

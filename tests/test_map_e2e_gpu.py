@@ -527,3 +527,76 @@ def test_worker_sheds_on_arena_oom(world):
     assert got['sub_batches'] >= 8 and got['workers'] == 4
     assert got['shed'] >= 1, got['shed']
     assert got['paf'] == want
+
+
+def seedless_end_reads(gen):
+    """3 kb of genome 0 as it is, joined to 5.5 kb in which every 12th base is complemented: no 15-mer of that end matches, so it
+    gets no seed and the read end is one end extension of the longest window minimap2 allows (max_gap = 5000 bases a side)."""
+    from megapath_nano_amd import synth
+    g0 = gen[0][1]
+
+    def noisy(seg):
+        s = seg.copy()
+        s[::12] = synth.COMP[s[::12]]
+        return s
+    left = np.concatenate([noisy(g0[90000:95500]), g0[95500:98500]])
+    right = np.concatenate([g0[100000:103000], noisy(g0[103000:108500])])
+    return [dict(name='left', seq=left), dict(name='right', seq=right), dict(name='left_rc', seq=synth.COMP[left[::-1]].copy())]
+
+
+SCORING_SETS = {
+    'sr': dict(a=2, b=8, q=12, e=2, q2=32, e2=1),
+    'asm20': dict(a=1, b=4, q=6, e=2, q2=26, e2=1),
+    'asm10': dict(a=1, b=9, q=16, e=2, q2=41, e2=1),
+    'asm5': dict(a=1, b=19, q=39, e=3, q2=81, e2=1),
+    'z100': dict(a=3, b=5, q=6, e=3, q2=30, e2=1, zdrop=100, zdrop_inv=60, min_dp_max=40),
+    'A10': dict(a=10, b=12, q=16, e=4, q2=60, e2=2),   # the seedless-end reads only: their end extensions score above 32767
+}
+
+
+@pytest.mark.parametrize('name', list(SCORING_SETS))
+def test_hard_reads_under_other_scoring(world, name):
+    """hard_reads (z-drop verdicts, the wave-per-window walk, the second exact pass, the inversion probe) and three reads with a
+    seedless end (5000 x 5000 end extensions, which the dispatcher gives to the tiled class) under scoring sets other than the
+    default: the PAF of every read equals the oracle's.  A10 runs the seedless-end reads only.
+
+    Observed on an MI355X (hard reads: mapped of 13 / lines with zd:i: / tp:A:I lines / second_pass_jobs / dp_rounds / tile_windows;
+    seedless-end reads: tile_windows):
+      sr    13 / 10 / 1 / 5 / 2 / 25; 6        asm20 13 / 10 / 1 / 5 / 2 / 26; 10      asm10 13 / 9 / 0 / 7 / 4 / 22; 6
+      asm5  7 / 15 / 0 / (13875 / 64) / 0; 0                         z100  13 / 12 / 1 / 6 / 2 / 26; 10      A10   -; 6
+    asm5 z-drops the 60-kb read every few hundred bases: every cut leaves a remainder for one more round of windows, far more
+    rounds than any default run takes.  The asm5 figures in brackets are from the run that still stopped at 64 rounds, where this
+    test failed on long_60k (the rest of that read came out without a CIGAR); the figures without that limit are not recorded
+    yet, the assertion below only requires more than 64 rounds."""
+    from map_cases import hard_reads
+    from megapath_nano_amd import mapper
+    from oracle import mm2_bindings as mb
+    gen, _, gidx, oidx = world
+    kw = SCORING_SETS[name]
+    gopt, oopt = mapper.default_opt(**kw), mb.default_opt(**kw)
+    ends = seedless_end_reads(gen)
+    names = [r['name'] for r in ends]
+    got = split_by_read(mapper.map_batch(gidx, gopt, names, [r['seq'] for r in ends]), names)
+    st = mapper.last_stats()
+    want = oracle_paf(oidx, oopt, ends)
+    print(name, 'ends: mapped', sum(bool(x) for x in want), 'tile_windows', st['tile_windows'], 'second_pass_jobs', st['second_pass_jobs'])
+    for r, g, x in zip(ends, got, want):
+        assert g == x, (name, r['name'])
+    # (asm5's mismatch score is outside the packed cells' domain: no strip, no tile, the band / workgroup kernels carry everything)
+    assert all(want) and (st['tile_windows'] > 0) == (name != 'asm5'), st
+    if name == 'A10':
+        return
+    reads = hard_reads(gen)
+    names = [r['name'] for r in reads]
+    got = split_by_read(mapper.map_batch(gidx, gopt, names, [r['seq'] for r in reads]), names)
+    st = mapper.last_stats()
+    want = oracle_paf(oidx, oopt, reads)
+    text = ''.join(want)
+    print(name, 'hard: mapped', sum(bool(x) for x in want), 'zd', sum('zd:i:' in l for l in text.splitlines()), 'inv', text.count('tp:A:I'),
+          'second_pass_jobs', st['second_pass_jobs'], 'dp_rounds', st['dp_rounds'], 'tile_windows', st['tile_windows'])
+    for r, g, x in zip(reads, got, want):
+        assert g == x, (name, r['name'])
+    assert 'zd:i:' in text, name
+    assert st['second_pass_jobs'] >= 1 and st['dp_rounds'] >= 2, st
+    if name == 'asm5':
+        assert st['dp_rounds'] > 64, st
