@@ -17,6 +17,12 @@
  *
  * Stage entry points (mpn_sketch_batch, mpn_seed_chain_batch) exist so that the parity tests can compare every
  * GPU stage with the oracle; mpn_map_batch is the product call.
+ *
+ * Difference strings (minimap2 --cs, --cs=long, --MD, --eqx): mpn_map_opt.out_tags.  The strings are made on the GPU when the
+ * alignment is finished, because only there are the read, the fixed CIGAR and the packed target together; they are written
+ * for hits that have a CIGAR, in PAF after cg:Z and in SAM before rl:i.  A column of an M op matches iff the two 0..4 codes
+ * are equal (N against N matches, unlike in NM).  cs and MD are both written when both are asked for, and MD always ends in
+ * a count.
  */
 #ifndef MPN_MAP_H
 #define MPN_MAP_H
@@ -51,7 +57,16 @@ typedef struct {
                                    * (aligner.py:188-192; header lines: mpn_sam_header), 2 = PAF lines AND kept SAM records
                                    * (mpn_map_batch_q).  Unmapped reads get a flag-4 record; QUAL is '*' unless the
                                    * qualities are handed over (mpn_map_batch_q, mpn_hits_finish). */
+    int32_t out_tags;             /* MPN_TAG_* bits: cs:Z / MD:Z tags and =/X CIGARs on every hit that has a CIGAR (text output with
+                                   * with_cigar only; calls that return columns alone ignore it).  0 = none. */
 } mpn_map_opt;
+
+enum {
+    MPN_TAG_CS = 1,       /* --cs, --cs=short: cs:Z in the short form (:k for k matching columns) */
+    MPN_TAG_CS_LONG = 2,  /* --cs=long: cs:Z with the matching bases spelled out (=ACGT); implies MPN_TAG_CS */
+    MPN_TAG_MD = 4,       /* --MD */
+    MPN_TAG_EQX = 8       /* --eqx: M ops of cg:Z, the SAM CIGAR column and BAM records split into = (op 7) and X (op 8) */
+};
 
 /* minimap2 2.17 defaults for `-x map-ont -c` (-N 5 -p 0.8) */
 void mpn_map_opt_init(mpn_map_opt *opt);
@@ -123,6 +138,21 @@ int mpn_ext_dp_batch(const mpn_map_opt *opt, int32_t n, const uint8_t *qcodes, c
                      const int32_t *end_bonus, const int32_t *flag, int32_t force_kernel, int32_t *out9, uint32_t *cigar_pool,
                      int64_t cigar_cap, int64_t *cig_off);
 
+/* ---- stage: the difference-string kernel on arbitrary alignments (tests) ---------------------------------------------------
+ * Pair i: read codes qcodes[q_off[i] .. +q_len[i]) (read orientation), of which [qs[i], qe[i]) is aligned on strand rev[i]
+ * (1 = the reverse complement of the interval is what the CIGAR walks); target codes tcodes[t_off[i] .. +t_len[i]) from ts[i];
+ * CIGAR cigar[cig_off[i] .. +n_cigar[i]) as len<<4|op with op 0 M, 1 I, 2 D only.  Validated on the host before any launch:
+ * no other op, no empty op, exactly qe-qs read bases consumed, inside the target; else -1.  Outputs by out_tags (MPN_TAG_*):
+ * cs / md bytes (no NUL) and eqx ops concatenated in pair order, pair i at [*_off[i], *_off[i+1]) (n+1 entries each; outputs
+ * that are not asked for may be NULL).  A pair with n_cigar = 0 has no alignment and gets empty outputs.  Returns 0, -3 if a cap
+ * is too small, -1 on bad arguments or a device error. */
+int mpn_aln_tags_batch(int32_t n, const uint8_t *qcodes, const int64_t *q_off, const int32_t *q_len,
+                       const int32_t *qs, const int32_t *qe, const int32_t *rev,
+                       const uint8_t *tcodes, const int64_t *t_off, const int32_t *t_len, const int32_t *ts,
+                       const uint32_t *cigar, const int64_t *cig_off, const int32_t *n_cigar, int32_t out_tags,
+                       char *cs, int64_t cs_cap, int64_t *cs_off, char *md, int64_t md_cap, int64_t *md_off,
+                       uint32_t *eqx, int64_t eqx_cap, int64_t *eqx_off);
+
 /* ---- product call: map a batch of reads, PAF text out ----------------------------------------------------
  * names: n NUL-terminated read names.  paf receives the lines of all reads in input order (NUL terminated).
  * Returns the number of bytes written, or negative error (-3: paf_cap too small). */
@@ -180,6 +210,10 @@ int mpn_map_batch_part(const mpn_index *part, const mpn_map_opt *opt, int32_t n,
 int mpn_map_batch_parts(const mpn_index *const *parts, int32_t n_parts, const mpn_map_opt *opt, int32_t n, const char *const *names,
                         const char *seqs, const int64_t *seq_off, const int32_t *seq_len, const void *r_seqs, const int64_t *r_off,
                         const int32_t *r_len, mpn_hits *acc);
+/* out_tags: the strings are made while a part is resident and kept with its hits, so every part of one accumulator is mapped
+ * with the same out_tags, and mpn_hits_finish fails (-1) when its opt asks for a tag the accumulated hits do not carry (or for
+ * the other cs form).  An accumulator with want_text = 0 computes none.  mpn_hits_export refuses (-1) an accumulator whose hits
+ * carry tag strings or =/X CIGARs: the block format does not hold them. */
 int64_t mpn_hits_finish(mpn_hits *acc, const mpn_map_opt *opt, int32_t n, const char *const *names, const char *seqs,
                         const char *quals, const int64_t *seq_off, const int32_t *seq_len, char *paf, int64_t paf_cap,
                         mpn_aln_cols *cols);
@@ -234,7 +268,8 @@ void mpn_map_last_stats(int64_t stats[32]);
  *  [38] strip DP <16>  [39] strip DP <32>  [40] strip DP <64>  and their cells [41] [42] [43]
  *  [44] anchors that entered the sort x effective radix passes (bytes moved by the sort = 32 x this)
  *  [45] anchors kept for chaining (segments of at least min_cnt anchors)  [46] device ns of the compaction kernels
- *  device ns of the anchor sort's kernels: [47] partition  [48] chunk sort in LDS  [49] radix passes over the large buckets */
+ *  device ns of the anchor sort's kernels: [47] partition  [48] chunk sort in LDS  [49] radix passes over the large buckets
+ *  [52] device ns of the finishing kernel  [76] device ns of the difference-string kernel's launches (0 unless out_tags asks for text) */
 int32_t mpn_map_last_stats_ex(int64_t *stats, int32_t n);
 
 #ifdef __cplusplus

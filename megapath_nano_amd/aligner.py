@@ -50,12 +50,16 @@ class AlignerOptions:
     """The subset of minimap2's command line the reference uses (megapath_nano.py:1124,:1270,:1383,:221-241)."""
 
     _INT = {'-N': 'best_n', '-k': None, '-w': None, '-A': 'a', '-B': 'b', '-s': 'min_dp_max'}
+    # difference strings of every hit that has a CIGAR (MapOpt.out_tags; mapping-only calls ignore them, as minimap2 does)
+    _TAGS = {'--cs': mapper.TAG_CS, '--cs=short': mapper.TAG_CS, '--cs=long': mapper.TAG_CS | mapper.TAG_CS_LONG, '--MD': mapper.TAG_MD,
+             '--eqx': mapper.TAG_EQX}
 
     def __init__(self, args, mapping_only):
         self.k, self.w = 15, 10
         self.batch_bases = IDX_BATCH_DEFAULT
         self.split = False
         fields = {}
+        out_tags = 0
         args = list(args or [])
         i = 0
         while i < len(args):
@@ -66,6 +70,12 @@ class AlignerOptions:
             if a == '--split-prefix':
                 self.split = True
                 i += 2
+                continue
+            if a in self._TAGS or a.startswith('--cs='):
+                if a not in self._TAGS:
+                    raise ValueError(f'aligner option {a}: the cs form is short or long')
+                out_tags |= self._TAGS[a]
+                i += 1
                 continue
             flag = a[:2]
             if not a.startswith('-') or a.startswith('--') or flag not in ('-x', '-N', '-p', '-k', '-w', '-A', '-B', '-O', '-E', '-s',
@@ -103,7 +113,7 @@ class AlignerOptions:
             elif flag == '-I':
                 self.batch_bases = parse_num(value)
             # -t: the library owns its threads
-        self.opt = mapper.default_opt(with_cigar=0 if mapping_only else 1, **fields)
+        self.opt = mapper.default_opt(with_cigar=0 if mapping_only else 1, out_tags=out_tags, **fields)
 
 
 def parse_aligner_options(aligner_options, mapping_only):

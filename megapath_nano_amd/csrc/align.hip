@@ -9,6 +9,7 @@
 #include "map_types.h"
 #include "ext_kernels.h"
 #include "fin_kernels.h"
+#include "tag_kernels.h"
 #include "stitch_kernels.h"
 #include "plan_kernels.h"
 #include "hit_kernels.h"
@@ -55,7 +56,8 @@ struct Reg {
     int32_t mlen = 0, blen = 0, n_sub = 0, score0 = 0;
     uint32_t mapq = 0, split = 0, rev = 0, inv = 0, sam_pri = 0, split_inv = 0, hash = 0;
     int32_t has_p = 0, dp_score = 0, dp_max = 0, dp_max2 = 0, n_ambi = 0;
-    std::vector<uint32_t> cigar;
+    std::vector<uint32_t> cigar;   // with MPN_TAG_EQX: its M ops already split into = (7) and X (8)
+    std::string cs, md;            // cs:Z / MD:Z strings of the alignment (tag_kernels.h), when the call asked for them
     int32_t aligned = 0;  // base-level extension already done (or not needed)
     int32_t fin_qs = 0, fin_rs = 0, fin_ql = 0, fin_tl = 0;   // an inversion hit before its extension: the window to extend
     int32_t fin_idx = -1;  // >= 0: stitched this round (its index among the round's hits): CIGAR fix-up and statistics are due
@@ -401,7 +403,7 @@ static void split_reg(Reg &r, Reg &r2, int n, int qlen, const SplitRec *sp) {
     r2 = r;
     r2.id = -1;
     r2.sam_pri = 0;
-    r2.has_p = 0; r2.cigar.clear(); r2.dp_score = r2.dp_max = r2.dp_max2 = r2.n_ambi = 0;
+    r2.has_p = 0; r2.cigar.clear(); r2.cs.clear(); r2.md.clear(); r2.dp_score = r2.dp_max = r2.dp_max2 = r2.n_ambi = 0;
     r2.split_inv = 0;
     r2.aligned = 0;
     r2.cnt = r.cnt - n;
@@ -561,6 +563,13 @@ struct Targets {
     const std::vector<int32_t> *lens;
 };
 
+// cs:Z and MD:Z of a hit that has a CIGAR, in this order (both when both were asked for: DESIGN.md section 6)
+static void write_diff_tags(const mpn_map_opt *o, const Reg &r, std::string &out) {
+    if (r.cigar.empty()) return;
+    if (o->out_tags & (MPN_TAG_CS | MPN_TAG_CS_LONG)) { out += "\tcs:Z:"; out += r.cs; }
+    if (o->out_tags & MPN_TAG_MD) { out += "\tMD:Z:"; out += r.md; }
+}
+
 static void write_paf(const Targets mi_, const mpn_map_opt *o, const char *name, int32_t qlen, const std::vector<Reg> &regs,
                       int32_t rep_len, std::string &out) {
     const Targets *mi = &mi_;
@@ -590,7 +599,8 @@ static void write_paf(const Targets mi_, const mpn_map_opt *o, const char *name,
         out += buf;
         if (r.has_p && o->with_cigar) {
             out += "\tcg:Z:";
-            for (uint32_t c : r.cigar) { snprintf(buf, sizeof(buf), "%d%c", c >> 4, "MIDNSH"[c & 0xf]); out += buf; }
+            for (uint32_t c : r.cigar) { snprintf(buf, sizeof(buf), "%d%c", c >> 4, "MIDNSHP=X"[c & 0xf]); out += buf; }
+            write_diff_tags(o, r, out);
         }
         out += '\n';
     }
@@ -617,7 +627,7 @@ static void sam_qual(std::string &out, const char *qual, int st, int en, bool re
     else for (int i = en - 1; i >= st; --i) out += qual[i];
 }
 
-static void write_sam(const Targets mi_, const char *name, int32_t qlen, const char *seq, const char *qual, const std::vector<Reg> &regs,
+static void write_sam(const Targets mi_, const mpn_map_opt *o, const char *name, int32_t qlen, const char *seq, const char *qual, const std::vector<Reg> &regs,
                       int32_t rep_len, std::string &out) {
     const Targets *mi = &mi_;
     char buf[1024];
@@ -647,7 +657,7 @@ static void write_sam(const Targets mi_, const char *name, int32_t qlen, const c
             const int clip0 = r.rev ? qlen - r.qe : r.qs, clip1 = r.rev ? r.qs : qlen - r.qe;
             const char clip_char = (flag & 0x800) ? 'H' : 'S';
             if (clip0) { snprintf(buf, sizeof(buf), "%d%c", clip0, clip_char); out += buf; }
-            for (uint32_t c : r.cigar) { snprintf(buf, sizeof(buf), "%d%c", c >> 4, "MIDNSH"[c & 0xf]); out += buf; }
+            for (uint32_t c : r.cigar) { snprintf(buf, sizeof(buf), "%d%c", c >> 4, "MIDNSHP=X"[c & 0xf]); out += buf; }
             if (clip1) { snprintf(buf, sizeof(buf), "%d%c", clip1, clip_char); out += buf; }
         }
         out += "\t*\t0\t0\t";
@@ -689,6 +699,7 @@ static void write_sam(const Targets mi_, const char *name, int32_t qlen, const c
                 out += buf;
             }
         }
+        if (r.has_p && o->with_cigar) write_diff_tags(o, r, out);
         snprintf(buf, sizeof(buf), "\trl:i:%d\n", rep_len);
         out += buf;
     }
@@ -701,17 +712,17 @@ struct Slot {
     Arena arena;
     PoolBuf pool_jobs, pool_P, pool_P2, pool_OFF, pool_order, pool_state, pool_CIG, pool_res, pool_redo, pool_compact, pool_used;
     PoolBuf pool_redo_ids, pool_sregs, pool_souts, pool_fin_jobs, pool_fin_out, pool_fin_cig;
-    PoolBuf pool_probes, pool_sizes, pool_buckets, pool_pregs, pool_psum, pool_job_anchor, pool_splits;
+    PoolBuf pool_probes, pool_sizes, pool_buckets, pool_pregs, pool_psum, pool_job_anchor, pool_splits, pool_tags;
     PoolBuf pin_segs{nullptr, 0, true}, pin_pregs{nullptr, 0, true}, pin_hits{nullptr, 0, true};
     PoolBuf pin_order{nullptr, 0, true}, pin_res{nullptr, 0, true};
     PoolBuf pin_chain_u{nullptr, 0, true}, pin_chain_b{nullptr, 0, true};
-    PoolBuf pin_fin_cig{nullptr, 0, true}, pin_fin_out{nullptr, 0, true};
+    PoolBuf pin_fin_cig{nullptr, 0, true}, pin_fin_out{nullptr, 0, true}, pin_tags{nullptr, 0, true}, pin_tag_bytes{nullptr, 0, true};
     std::vector<std::vector<SqueezeSeg>> seg_stage;   // per pool thread: the squeeze segments of the reads it handled
     size_t device_bytes() const {
         size_t h = 0;
         for (const PoolBuf *pb : {&pool_jobs, &pool_P, &pool_P2, &pool_OFF, &pool_order, &pool_state, &pool_CIG, &pool_res, &pool_redo, &pool_compact, &pool_used,
                                   &pool_redo_ids, &pool_sregs, &pool_souts, &pool_fin_jobs, &pool_fin_out, &pool_fin_cig, &pool_probes, &pool_sizes, &pool_buckets,
-                                  &pool_pregs, &pool_psum, &pool_job_anchor, &pool_splits})
+                                  &pool_pregs, &pool_psum, &pool_job_anchor, &pool_splits, &pool_tags})
             h += pb->cap;
         for (const auto &c : arena.chunks) h += c.cap;
         return h;
@@ -721,7 +732,7 @@ struct Slot {
         arena.release_all();
         for (PoolBuf *pb : {&pool_jobs, &pool_P, &pool_P2, &pool_OFF, &pool_order, &pool_state, &pool_CIG, &pool_res, &pool_redo, &pool_compact, &pool_used,
                             &pool_redo_ids, &pool_sregs, &pool_souts, &pool_fin_jobs, &pool_fin_out, &pool_fin_cig, &pool_probes, &pool_sizes, &pool_buckets,
-                            &pool_pregs, &pool_psum, &pool_job_anchor, &pool_splits})
+                            &pool_pregs, &pool_psum, &pool_job_anchor, &pool_splits, &pool_tags})
             pb->release();
     }
 };
@@ -1268,6 +1279,98 @@ struct RoundDev {
     const StitchReg *sregs; const PlanReg *pregs; const PlanSum *psum; const int32_t *job_anchor; const u128 *anchors;
 };
 
+// ---- cs / MD / =X strings of finished alignments (tag_kernels.h): host side ------------------------------------------------
+// tags_enqueue launches aln_tags_wave_kernel for the listed alignments (FinJob / FinOut / fixed CIGARs resident) and queues the
+// download of the per-alignment TagOut records and the pools' cursors; after the caller's wait on the stream, tags_fetch checks
+// the overflow flag and downloads exactly the bytes the kernel produced.  The pools are sized from bounds the host knows
+// before the launch: with M <= min(qspan, tspan) match-op columns, cs needs at most M + qspan + tspan + 2 per op bytes (three
+// per mismatch, a count of a run is no longer than the run plus its ':'), MD at most M + tspan + 2 per op, and there are at
+// most M + n_ops =/X ops; the kernel takes exact slices from them and flags any write that would pass one.
+struct TagJobDim { int32_t id, n_ops, qspan, tspan; };
+struct TagRun {
+    int tags = 0, n_jobs = 0;
+    std::vector<int32_t> order;
+    TagOut *d_out = nullptr;
+    char *d_cs = nullptr, *d_md = nullptr;
+    uint32_t *d_eqx = nullptr;
+    const TagOut *h_out = nullptr;
+    const unsigned long long *h_cur = nullptr;
+    const char *h_cs = nullptr, *h_md = nullptr;
+    const uint32_t *h_eqx = nullptr;
+};
+static inline int norm_tags(int t) { return (t & (MPN_TAG_CS | MPN_TAG_CS_LONG | MPN_TAG_MD | MPN_TAG_EQX)) | (t & MPN_TAG_CS_LONG ? MPN_TAG_CS : 0); }
+
+static int tags_enqueue(Slot &SL, const std::vector<TagJobDim> &dims, int n_jobs, int64_t n_ops_total, const FinJob *d_fj, const FinOut *d_fo,
+                        const uint32_t *d_cig, const uint8_t *d_seqs, const int64_t *d_off, const int32_t *d_len, const RefView &rvw, int tags,
+                        hipStream_t st, TagRun &tr, EvTimer *ev = nullptr) {
+    constexpr int NC = 2;
+    static const int kOps[NC] = {512, 4096};   // 12 bytes of LDS per op: 6 KB and 48 KB; longer CIGARs keep the positions in global scratch
+    tr.tags = tags = norm_tags(tags);
+    tr.n_jobs = n_jobs;
+    std::vector<int32_t> lists[NC + 1];
+    int64_t cs_cap = 0, md_cap = 0, eqx_cap = 0;
+    for (const TagJobDim &d : dims) {
+        int c = 0;
+        while (c < NC && d.n_ops > kOps[c]) ++c;
+        lists[c].push_back(d.id);
+        const int64_t q = std::max(0, d.qspan), t = std::max(0, d.tspan), m = std::min(q, t);
+        if (tags & MPN_TAG_CS) cs_cap += m + q + t + 2 * (int64_t)d.n_ops + 16;
+        if (tags & MPN_TAG_MD) md_cap += m + t + 2 * (int64_t)d.n_ops + 16;
+        if (tags & MPN_TAG_EQX) eqx_cap += m + d.n_ops + 4;
+    }
+    int base[NC + 1];
+    tr.order.clear();
+    for (int c = 0; c <= NC; ++c) { base[c] = (int)tr.order.size(); tr.order.insert(tr.order.end(), lists[c].begin(), lists[c].end()); }
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_out = 0, o_cur = up16((size_t)n_jobs * sizeof(TagOut)), o_eqx = o_cur + 64, o_pos = o_eqx + up16((size_t)eqx_cap * 4),
+                 o_list = o_pos + up16(lists[NC].empty() ? 0 : (size_t)n_ops_total * 12), o_cs = o_list + up16(tr.order.size() * 4),
+                 o_md = o_cs + up16((size_t)cs_cap), total = o_md + up16((size_t)md_cap);
+    if (SL.pool_tags.ensure(total + 16) || SL.pin_tags.ensure(o_eqx + 16)) return -1;
+    uint8_t *d = SL.pool_tags.as<uint8_t>();
+    tr.d_out = reinterpret_cast<TagOut *>(d + o_out);
+    unsigned long long *d_cur = reinterpret_cast<unsigned long long *>(d + o_cur);
+    tr.d_eqx = reinterpret_cast<uint32_t *>(d + o_eqx);
+    int32_t *d_pos = reinterpret_cast<int32_t *>(d + o_pos), *d_list = reinterpret_cast<int32_t *>(d + o_list);
+    tr.d_cs = reinterpret_cast<char *>(d + o_cs);
+    tr.d_md = reinterpret_cast<char *>(d + o_md);
+    MPN_HIP_CHECK(hipMemsetAsync(d, 0, o_eqx, st));   // alignments that are not listed have no strings; cursors and flag start at 0
+    if (!tr.order.empty()) {
+        MPN_HIP_CHECK(hipMemcpyAsync(d_list, tr.order.data(), tr.order.size() * 4, hipMemcpyHostToDevice, st));
+        if (ev) ev->skip();   // (the span charged to the kernel holds its launches alone, not the memset and the list's upload)
+        for (int c = 0; c < NC; ++c)
+            if (!lists[c].empty())
+                hipLaunchKernelGGL(aln_tags_wave_kernel<true>, dim3((unsigned)std::min<size_t>(lists[c].size(), 256 * 64)), dim3(64), (size_t)kOps[c] * 12, st, d_fj, d_fo,
+                                   (const int32_t *)d_list + base[c], (int)lists[c].size(), d_cig, (int32_t *)nullptr, d_seqs, d_off, d_len, rvw, tags, tr.d_cs,
+                                   (long long)cs_cap, tr.d_md, (long long)md_cap, tr.d_eqx, (long long)eqx_cap, d_cur, tr.d_out);
+        if (!lists[NC].empty())
+            hipLaunchKernelGGL(aln_tags_wave_kernel<false>, dim3((unsigned)std::min<size_t>(lists[NC].size(), 256 * 64)), dim3(64), 0, st, d_fj, d_fo,
+                               (const int32_t *)d_list + base[NC], (int)lists[NC].size(), d_cig, d_pos, d_seqs, d_off, d_len, rvw, tags, tr.d_cs,
+                               (long long)cs_cap, tr.d_md, (long long)md_cap, tr.d_eqx, (long long)eqx_cap, d_cur, tr.d_out);
+        MPN_HIP_CHECK(hipGetLastError());
+    }
+    MPN_HIP_CHECK(hipMemcpyAsync(SL.pin_tags.p, d, o_eqx, hipMemcpyDeviceToHost, st));
+    tr.h_out = SL.pin_tags.as<TagOut>();
+    tr.h_cur = reinterpret_cast<const unsigned long long *>(SL.pin_tags.as<uint8_t>() + o_cur);
+    return 0;
+}
+
+// after the stream has been waited for: the strings themselves (the used part of each pool), waits for them
+template <typename Stream> static int tags_fetch(Slot &SL, TagRun &tr, Stream &st) {
+    if (tr.h_cur[TAGC_OVERFLOW]) { set_error("difference-string kernel: an output would have passed its slice (cs %llu, MD %llu bytes, %llu =/X ops used)", tr.h_cur[TAGC_CS], tr.h_cur[TAGC_MD], tr.h_cur[TAGC_EQX]); return -1; }
+    const size_t n_cs = (size_t)tr.h_cur[TAGC_CS], n_md = (size_t)tr.h_cur[TAGC_MD], n_eqx = (size_t)tr.h_cur[TAGC_EQX];
+    const size_t o_cs = n_eqx * 4, o_md = o_cs + n_cs;
+    if (SL.pin_tag_bytes.ensure(o_md + n_md + 16)) return -1;
+    uint8_t *h = SL.pin_tag_bytes.as<uint8_t>();
+    if (n_eqx) MPN_HIP_CHECK(hipMemcpyAsync(h, tr.d_eqx, n_eqx * 4, hipMemcpyDeviceToHost, st));
+    if (n_cs) MPN_HIP_CHECK(hipMemcpyAsync(h + o_cs, tr.d_cs, n_cs, hipMemcpyDeviceToHost, st));
+    if (n_md) MPN_HIP_CHECK(hipMemcpyAsync(h + o_md, tr.d_md, n_md, hipMemcpyDeviceToHost, st));
+    if (n_eqx + n_cs + n_md) MPN_HIP_CHECK(stream_sync(st));
+    tr.h_eqx = reinterpret_cast<const uint32_t *>(h);
+    tr.h_cs = reinterpret_cast<const char *>(h + o_cs);
+    tr.h_md = reinterpret_cast<const char *>(h + o_md);
+    return 0;
+}
+
 static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadState *rs, int n, const int32_t *seq_len, const DevRound &dv,
                              const RoundDev &rd, const std::vector<int32_t> &sr_base, const uint8_t *d_seqs, const int64_t *d_off, const int32_t *d_len,
                              int n_threads, StreamLease &st) {
@@ -1339,6 +1442,9 @@ static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadS
     std::vector<int32_t> order;
     int base[NC + 1];
     for (int c = 0; c <= NC; ++c) { base[c] = (int)order.size(); order.insert(order.end(), lists[c].begin(), lists[c].end()); }
+    const int out_tags = g_need_cigar ? norm_tags(opt->out_tags) : 0;   // nothing is launched, allocated or copied without them
+    const bool want_tags = out_tags != 0, want_eqx = (out_tags & MPN_TAG_EQX) != 0;
+    TagRun tr;
     if (!order.empty()) {
         DevBuf<uint32_t> d_aux;
         DevBuf<uint8_t> d_codes;
@@ -1365,12 +1471,20 @@ static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadS
                                (const int64_t *)d_code_offs.p);
         MPN_HIP_CHECK(hipGetLastError());
         ev.mark(52);
+        if (want_tags) {   // cs / MD / =X of the round's alignments, while their part of the target set is resident (tag_kernels.h)
+            std::vector<TagJobDim> dims;
+            dims.reserve(order.size());
+            for (int32_t j : order) dims.push_back({j, h_so[j].n_ops, h_so[j].qe1 - h_so[j].qs1, h_so[j].re1 - h_so[j].rs1});
+            if (tags_enqueue(SL, dims, n_sr, n_ops, d_fj, d_fo, d_cig, d_seqs, d_off, d_len, rvw, opt->out_tags, st, tr, &ev)) return -1;
+            ev.mark(STAT_K_TAGS);
+        }
         MPN_HIP_CHECK(hipMemcpyAsync(h_fo, d_fo, (size_t)n_sr * sizeof(FinOut), hipMemcpyDeviceToHost, st));
-        if (g_need_cigar) {
+        if (g_need_cigar && !want_eqx) {   // (with =/X CIGARs asked for, those come back instead)
             if (SL.pin_fin_cig.ensure((size_t)n_ops * 4 + 16)) return -1;
             MPN_HIP_CHECK(hipMemcpyAsync(SL.pin_fin_cig.p, d_cig, (size_t)n_ops * 4, hipMemcpyDeviceToHost, st));
         }
         MPN_HIP_CHECK(stream_sync(st));
+        if (want_tags && tags_fetch(SL, tr, st)) return -1;
     }
     ev.resolve();
     g_stats[53] += n_ops;
@@ -1381,7 +1495,13 @@ static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadS
             const StitchOut &so = h_so[r.fin_idx];
             if (so.n_ops == 0) { r.blen = r.mlen = 0; r.dp_max = 0; r.fin_idx = -1; continue; }   // (what update_extra leaves for an empty CIGAR)
             const FinOut &f = h_fo[r.fin_idx];
-            if (g_need_cigar) r.cigar.assign(h_cig + so.cig_off, h_cig + so.cig_off + f.n_cigar);
+            if (g_need_cigar && !want_eqx) r.cigar.assign(h_cig + so.cig_off, h_cig + so.cig_off + f.n_cigar);
+            if (want_tags && so.has_p) {
+                const TagOut &to = tr.h_out[r.fin_idx];
+                if (want_eqx) r.cigar.assign(tr.h_eqx + to.eqx_off, tr.h_eqx + to.eqx_off + to.n_eqx);
+                if (out_tags & MPN_TAG_CS) r.cs.assign(tr.h_cs + to.cs_off, (size_t)to.cs_len);
+                if (out_tags & MPN_TAG_MD) r.md.assign(tr.h_md + to.md_off, (size_t)to.md_len);
+            }
             if (f.qshift) { if (r.rev) r.qe -= f.qshift; else r.qs += f.qshift; }
             r.rs += f.tshift;
             r.blen = f.blen; r.mlen = f.mlen; r.n_ambi += f.n_ambi; r.dp_max = f.dp_max;
@@ -1748,6 +1868,7 @@ struct mpn_hits {
     std::vector<int32_t> rep_len;
     std::vector<std::string> names;
     std::vector<int32_t> lens;
+    int32_t tags = 0;        // MPN_TAG_* outputs the accumulated hits carry (made while each part was resident)
 };
 
 // Threads of the host pool: what the caller asks for, else the cores this process may actually use -- the container's CPU
@@ -1991,7 +2112,7 @@ static int map_batch_core(const mpn_index *const *parts, int n_parts, const mpn_
             for (const auto &c : S.arena.chunks) arena += c.cap;
             const size_t pools = S.pool_jobs.cap + S.pool_P.cap + S.pool_P2.cap + S.pool_OFF.cap + S.pool_order.cap + S.pool_state.cap + S.pool_CIG.cap +
                                  S.pool_res.cap + S.pool_redo.cap + S.pool_compact.cap + S.pool_used.cap;
-            const size_t pinned = S.pin_order.cap + S.pin_res.cap + S.pin_chain_u.cap + S.pin_chain_b.cap + S.pin_segs.cap + S.pin_pregs.cap + S.pin_fin_cig.cap + S.pin_fin_out.cap;
+            const size_t pinned = S.pin_order.cap + S.pin_res.cap + S.pin_chain_u.cap + S.pin_chain_b.cap + S.pin_segs.cap + S.pin_pregs.cap + S.pin_fin_cig.cap + S.pin_fin_out.cap + S.pin_tags.cap + S.pin_tag_bytes.cap;
             fprintf(stderr, "[slot %d] arena %.2f GB, pools %.2f GB (P %.2f, CIG %.2f, compact %.2f), pinned host %.2f GB\n", wdx, arena / 1e9,
                     pools / 1e9, S.pool_P.cap / 1e9, S.pool_CIG.cap / 1e9, S.pool_compact.cap / 1e9, pinned / 1e9);
         }
@@ -2046,7 +2167,7 @@ static int64_t emit_batch(const Targets tg, const mpn_map_opt *opt, int32_t n, c
         parallel_for(n, n_threads, [&](int i, int) {
             const char *nm = names && names[i] ? names[i] : "*";
             if (want_paf && !regs[i]->empty()) write_paf(tg, opt, nm, seq_len[i], *regs[i], rep_len[i], paf_lines[i]);
-            if (want_sam) write_sam(tg, nm, seq_len[i], seqs + seq_off[i], quals ? quals + seq_off[i] : nullptr, *regs[i], rep_len[i], sam_lines[i]);
+            if (want_sam) write_sam(tg, opt, nm, seq_len[i], seqs + seq_off[i], quals ? quals + seq_off[i] : nullptr, *regs[i], rep_len[i], sam_lines[i]);
         }, 0, 16);   // (text is heavy per read)
     bool short_cols = false, short_text = false;
     g_kept.cols.clear(); g_kept.text.clear(); g_kept.sam.clear(); g_kept.n_rows = -1; g_kept.has_text = g_kept.has_sam = false;
@@ -2165,6 +2286,8 @@ extern "C" int mpn_map_batch_parts(const mpn_index *const *parts, int32_t n_part
     if (!parts || n_parts <= 0) { set_error("mpn_map_batch_parts: no index part"); return -1; }
     for (int p = 0; p < n_parts; ++p)
         if (!parts[p] || parts[p]->k != parts[0]->k) { set_error("mpn_map_batch_parts: null part or parts built with different k"); return -1; }
+    const int part_tags = acc->want_text && opt->with_cigar ? norm_tags(opt->out_tags) : 0;
+    if (acc->n_parts > 0 && part_tags != acc->tags) { set_error("mpn_map_batch_parts: out_tags differs from that of the parts already accumulated"); return -1; }
     std::lock_guard<std::mutex> call_guard(g_call_mu);
     memset(g_stats, 0, sizeof(g_stats));
     if (n > 0) {
@@ -2189,6 +2312,7 @@ extern "C" int mpn_map_batch_parts(const mpn_index *const *parts, int32_t n_part
             }
         }, 10);
     }
+    acc->tags = part_tags;   // (only now: a call that failed leaves no claim)
     for (int p = 0; p < n_parts; ++p) {
         acc->names.insert(acc->names.end(), parts[p]->names.begin(), parts[p]->names.end());
         acc->lens.insert(acc->lens.end(), parts[p]->lens.begin(), parts[p]->lens.end());
@@ -2227,6 +2351,13 @@ extern "C" int64_t mpn_hits_finish(mpn_hits *acc, const mpn_map_opt *opt, int32_
     g_pool.ensure(n_threads);
     if (!acc->n_parts) { set_error("mpn_hits_finish: no part was mapped"); return -1; }
     if (!acc->want_text && (paf || opt->out_sam != 0)) { set_error("mpn_hits_finish: text asked of an accumulator that was told there would be none (mpn_hits_set_text)"); return -1; }
+    if ((paf || opt->out_sam != 0) && opt->with_cigar) {   // the strings were made while the parts were resident: they cannot be made now
+        const int req = norm_tags(opt->out_tags);
+        if ((req & ~acc->tags) || ((req & MPN_TAG_CS) && ((req ^ acc->tags) & MPN_TAG_CS_LONG))) {
+            set_error("mpn_hits_finish: out_tags 0x%x asks for output that the accumulated hits do not carry (parts were mapped with 0x%x)", req, acc->tags);
+            return -1;
+        }
+    }
     if (g_cpu_on) { g_cpu_ns[11] = 0; g_cpu_ns[0] = 0; }
     struct Report { ~Report() { if (g_cpu_on) fprintf(stderr, "[cpu] finish: merge %.0f ms, text/other %.0f ms (thread CPU in parallel regions)\n", g_cpu_ns[11].load() / 1e6, g_cpu_ns[0].load() / 1e6); } } report_;
     parallel_for(n, n_threads, [&](int i, int) { merge_regs(opt, acc->k, acc->regs[(size_t)i], acc->rep_len[(size_t)i]); }, 11, 128);
@@ -2275,6 +2406,7 @@ static inline void hit_from_fields(const int32_t *f, Reg &r) {
 
 extern "C" int64_t mpn_hits_export(const mpn_hits *h, int32_t lo, int32_t hi, void *buf, int64_t cap) {
     if (!h || lo < 0 || hi < lo || hi > h->n_reads) { set_error("mpn_hits_export: no accumulator or reads [%d, %d) outside its batch", lo, hi); return -1; }
+    if (h->tags) { set_error("mpn_hits_export: the hits carry cs/MD strings or =/X CIGARs (out_tags 0x%x), which the block format does not hold", h->tags); return -1; }
     int64_t payload = 0;
     for (int32_t i = lo; i < hi; ++i) {
         payload += 8;
@@ -2505,6 +2637,95 @@ extern "C" int mpn_ext_dp_batch(const mpn_map_opt *opt, int32_t n, const uint8_t
         if (used + e.n_cigar > cigar_cap) return -3;
         if (e.n_cigar) memcpy(cigar_pool + used, cig.data() + e.cig_pos, (size_t)e.n_cigar * 4);
         used += e.n_cigar;
+    }
+    return 0;
+}
+
+// stage entry point for the tests of the difference-string kernel: aln_tags_wave_kernel, as the product launches it, on
+// arbitrary (read, target, CIGAR) triples
+extern "C" int mpn_aln_tags_batch(int32_t n, const uint8_t *qcodes, const int64_t *q_off, const int32_t *q_len, const int32_t *qs,
+                                  const int32_t *qe, const int32_t *rev, const uint8_t *tcodes, const int64_t *t_off, const int32_t *t_len,
+                                  const int32_t *ts, const uint32_t *cigar, const int64_t *cig_off, const int32_t *n_cigar, int32_t out_tags,
+                                  char *cs, int64_t cs_cap, int64_t *cs_off, char *md, int64_t md_cap, int64_t *md_off, uint32_t *eqx,
+                                  int64_t eqx_cap, int64_t *eqx_off) {
+    std::lock_guard<std::mutex> call_guard(g_call_mu);
+    hipStream_t st = 0;
+    if (n < 0) { set_error("mpn_aln_tags_batch: negative count"); return -1; }
+    if (cs_off) cs_off[0] = 0;
+    if (md_off) md_off[0] = 0;
+    if (eqx_off) eqx_off[0] = 0;
+    if (n == 0) return 0;
+    const int tags = norm_tags(out_tags);
+    if (((tags & MPN_TAG_CS) && !cs_off) || ((tags & MPN_TAG_MD) && !md_off) || ((tags & MPN_TAG_EQX) && !eqx_off)) { set_error("mpn_aln_tags_batch: an output that out_tags asks for has no offset array"); return -1; }
+    // everything is checked here, before any launch: only M/I/D ops, none empty, exactly the read interval, inside the target
+    int64_t qtot = 0, ttot = 0, ctot = 0;
+    std::vector<FinJob> jobs((size_t)n);
+    std::vector<FinOut> fouts((size_t)n);
+    std::vector<TagJobDim> dims;
+    for (int i = 0; i < n; ++i) {
+        if (q_len[i] < 0 || t_len[i] < 0 || n_cigar[i] < 0 || qs[i] < 0 || qe[i] < qs[i] || qe[i] > q_len[i] || ts[i] < 0 || ts[i] > t_len[i]) {
+            set_error("mpn_aln_tags_batch: pair %d: intervals outside the sequences", i); return -1;
+        }
+        int64_t ql = 0, tl = 0;
+        for (int k = 0; k < n_cigar[i]; ++k) {
+            const uint32_t c = cigar[cig_off[i] + k], op = c & 0xf, len = c >> 4;
+            if (op > 2 || len == 0) { set_error("mpn_aln_tags_batch: pair %d: op %d is not a non-empty M, I or D", i, k); return -1; }
+            ql += op != 2 ? len : 0; tl += op != 1 ? len : 0;
+        }
+        if (ql != qe[i] - qs[i] || ts[i] + tl > t_len[i]) { set_error("mpn_aln_tags_batch: pair %d: the CIGAR does not consume its read interval or leaves the target", i); return -1; }
+        qtot = std::max<int64_t>(qtot, q_off[i] + q_len[i]); ttot = std::max<int64_t>(ttot, t_off[i] + t_len[i]);
+        ctot = std::max<int64_t>(ctot, cig_off[i] + n_cigar[i]);
+        FinJob &f = jobs[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        f.cig_off = cig_off[i]; f.n_cigar = n_cigar[i]; f.read = i; f.rid = i; f.rev = rev[i] ? 1 : 0;
+        f.qs1 = rev[i] ? q_len[i] - qe[i] : qs[i]; f.rs1 = ts[i]; f.qspan = (int32_t)ql; f.tspan = (int32_t)tl;
+        FinOut &o = fouts[(size_t)i];
+        memset(&o, 0, sizeof(o));
+        o.n_cigar = n_cigar[i];
+        if (n_cigar[i] > 0) dims.push_back({i, n_cigar[i], (int32_t)ql, (int32_t)tl});
+    }
+    std::vector<uint8_t> ascii(((size_t)qtot + 19) & ~(size_t)3, 'N');
+    for (int64_t i = 0; i < qtot; ++i) ascii[(size_t)i] = (uint8_t)"ACGTN"[qcodes[i] > 4 ? 4 : qcodes[i]];
+    std::vector<uint32_t> words;
+    std::vector<int64_t> ns, ne;
+    pack_2bit(tcodes, ttot, words, ns, ne);
+    words.push_back(0);
+    DevBuf<uint8_t> d_reads;
+    DevBuf<uint32_t> d_ref, d_cig;
+    DevBuf<int64_t> d_qoff, d_toff, d_ns, d_ne;
+    DevBuf<int32_t> d_qlen;
+    DevBuf<FinJob> d_fj;
+    DevBuf<FinOut> d_fo;
+    std::vector<uint32_t> cig_pad(cigar, cigar + ctot);
+    cig_pad.push_back(0);
+    if (d_reads.upload(ascii.data(), ascii.size(), st) || d_ref.upload(words.data(), words.size(), st) || d_ns.upload(ns.data(), ns.size(), st) ||
+        d_ne.upload(ne.data(), ne.size(), st) || d_qoff.upload(q_off, n, st) || d_qlen.upload(q_len, n, st) || d_toff.upload(t_off, n, st) ||
+        d_cig.upload(cig_pad.data(), cig_pad.size(), st) || d_fj.upload(jobs.data(), jobs.size(), st) || d_fo.upload(fouts.data(), fouts.size(), st))
+        return -1;
+    Slot &SL = *tl_slot;
+    TagRun tr;
+    const RefView rvw{d_ref.p, d_toff.p, d_ns.p, d_ne.p, (int32_t)ns.size()};
+    if (tags_enqueue(SL, dims, n, ctot, d_fj.p, d_fo.p, d_cig.p, d_reads.p, d_qoff.p, d_qlen.p, rvw, tags, st, tr)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    if (tags_fetch(SL, tr, st)) return -1;
+    int64_t c_used = 0, m_used = 0, e_used = 0;
+    for (int i = 0; i < n; ++i) {
+        const TagOut &to = tr.h_out[i];
+        if (tags & MPN_TAG_CS) {
+            if (c_used + to.cs_len > cs_cap) return -3;
+            if (to.cs_len) memcpy(cs + c_used, tr.h_cs + to.cs_off, (size_t)to.cs_len);
+            c_used += to.cs_len; cs_off[i + 1] = c_used;
+        }
+        if (tags & MPN_TAG_MD) {
+            if (m_used + to.md_len > md_cap) return -3;
+            if (to.md_len) memcpy(md + m_used, tr.h_md + to.md_off, (size_t)to.md_len);
+            m_used += to.md_len; md_off[i + 1] = m_used;
+        }
+        if (tags & MPN_TAG_EQX) {
+            if (e_used + to.n_eqx > eqx_cap) return -3;
+            if (to.n_eqx) memcpy(eqx + e_used, tr.h_eqx + to.eqx_off, (size_t)to.n_eqx * 4);
+            e_used += to.n_eqx; eqx_off[i + 1] = e_used;
+        }
     }
     return 0;
 }

@@ -83,7 +83,7 @@ struct HostChains {
     void chain_order(int i, int32_t *order, int64_t *src) const;
 };
 
-constexpr int MPN_NSTATS = 76;
+constexpr int MPN_NSTATS = 77;
 constexpr int STAT_LEASE_WAIT = 65;   // wall time the workers waited for a free submission stream (StreamLease)
 // extension groups with side work (long windows, tiles): [66] it got leased side streams, [67] it ran on the worker's own stream
 constexpr int STAT_SIDE_LEASED = 66, STAT_SIDE_OWN = 67;
@@ -93,6 +93,8 @@ constexpr int STAT_TILE_CLASS = 68, STAT_TILE_GIVEUPS = 72;
 // run on the worker's own stream (time that [15] held before)
 // [75] gap fills that ext_ztest_wave_kernel failed (listed for the second pass, or handed to the inversion probe)
 constexpr int STAT_WALK_WAVE = 73, STAT_EV_WALK_LONG = 74, STAT_WALK_WAVE_FAILED = 75;
+// [76] device ns of the difference-string kernel (aln_tags_wave_kernel: cs / MD / =X); 0 unless a call asks for them
+constexpr int STAT_K_TAGS = 76;
 extern thread_local int64_t g_stats[MPN_NSTATS];
 
 // 2-bit packing of 0..4 codes (N -> 0 + run list)

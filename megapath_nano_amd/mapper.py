@@ -17,7 +17,11 @@ class MapOpt(ct.Structure):
                 ('e2', ct.c_int32), ('sc_ambi', ct.c_int32), ('zdrop', ct.c_int32), ('zdrop_inv', ct.c_int32),
                 ('end_bonus', ct.c_int32), ('min_dp_max', ct.c_int32), ('min_ksw_len', ct.c_int32),
                 ('max_clip_ratio', ct.c_float), ('max_sw_mat', ct.c_int64), ('with_cigar', ct.c_int32),
-                ('seed', ct.c_uint32), ('host_threads', ct.c_int32), ('out_sam', ct.c_int32)]
+                ('seed', ct.c_uint32), ('host_threads', ct.c_int32), ('out_sam', ct.c_int32), ('out_tags', ct.c_int32)]
+
+
+# MapOpt.out_tags bits (include/mpn_map.h MPN_TAG_*)
+TAG_CS, TAG_CS_LONG, TAG_MD, TAG_EQX = 1, 2, 4, 8
 
 
 COL_NAMES = ('read_idx', 'qs', 'qe', 'rev', 'rid', 'rs', 're', 'mlen', 'blen', 'mapq', 'nm', 'as_', 'primary')
@@ -119,6 +123,9 @@ def _bind():
         lib.mpn_map_fetch_text.restype = ct.c_int64
         lib.mpn_ext_dp_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, P, P, P, P, P, P, P, P, P, P, ct.c_int32, P, P, ct.c_int64, P]
         lib.mpn_ext_dp_batch.restype = ct.c_int
+        lib.mpn_aln_tags_batch.argtypes = [ct.c_int32, P, P, P, P, P, P, P, P, P, P, P, P, P, ct.c_int32, P, ct.c_int64, P, P, ct.c_int64, P,
+                                           P, ct.c_int64, P]
+        lib.mpn_aln_tags_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
         lib.mpn_map_last_stats_ex.argtypes = [P, ct.c_int32]
@@ -418,6 +425,9 @@ def _emit(call, opt, packed, want_paf, want_cols):
     lib = _bind()
     n = packed.n
     per_base = 3 if opt.out_sam == 1 else 0.5
+    if opt.with_cigar:   # the difference strings of ~10 % error reads, per text (out_sam == 2 keeps the SAM in the library)
+        per_base += (2.5 if opt.out_tags & TAG_CS_LONG else 1 if opt.out_tags & TAG_CS else 0) + (0.5 if opt.out_tags & TAG_MD else 0) + \
+            (0.25 if opt.out_tags & TAG_EQX else 0)
     paf_cap = int(packed.bases * per_base) + 512 * n + 4096 if want_paf else 0
     rows_cap = max(64, int(n * _rows_per_read * 1.25) + 16)
 
@@ -607,6 +617,48 @@ def ext_dp_batch(opt, queries, targets, w, zdrop, end_bonus, flag, force_kernel=
     return res
 
 
+def aln_tags_batch(queries, q_ivals, revs, targets, t_starts, cigars, out_tags, caps=None):
+    """The difference-string kernel on arbitrary alignments (mpn_aln_tags_batch).  queries / targets: 0..4 code arrays (reads in
+    read orientation); q_ivals: (qs, qe) per pair in read coordinates; revs: strand per pair; t_starts: first target base;
+    cigars: lists of len << 4 | op (M 0, I 1, D 2); out_tags: TAG_* bits; caps: (cs bytes, MD bytes, =/X ops) or None for bounds
+    that always fit.  -> list of dict(cs=str or None, md=str or None, eqx=list or None), outputs that were not asked for None."""
+    lib = _bind()
+    n = len(queries)
+    qbuf, qoff, qlen = pack_seqs([np.asarray(q, dtype=np.uint8) for q in queries])
+    tbuf, toff, tlen = pack_seqs([np.asarray(t, dtype=np.uint8) for t in targets])
+    qs = np.ascontiguousarray([iv[0] for iv in q_ivals], dtype=np.int32)
+    qe = np.ascontiguousarray([iv[1] for iv in q_ivals], dtype=np.int32)
+    rev = np.ascontiguousarray(np.broadcast_to(np.asarray(revs, dtype=np.int32), (n,)))
+    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(t_starts, dtype=np.int32), (n,)))
+    ncig = np.array([len(c) for c in cigars], dtype=np.int32)
+    coff = np.zeros(n, dtype=np.int64)
+    if n > 1:
+        coff[1:] = np.cumsum(ncig[:-1].astype(np.int64))
+    cig = np.zeros(int(ncig.astype(np.int64).sum()) + 1, dtype=np.uint32)
+    for c, o in zip(cigars, coff):
+        cig[o:o + len(c)] = np.asarray(c, dtype=np.uint32)
+    cols = sum(int(x) >> 4 for c in cigars for x in c)
+    ops = int(ncig.astype(np.int64).sum())
+    want_cs, want_md, want_eqx = bool(out_tags & (TAG_CS | TAG_CS_LONG)), bool(out_tags & TAG_MD), bool(out_tags & TAG_EQX)
+    cs_cap, md_cap, eqx_cap = caps if caps is not None else (3 * cols + 2 * ops + 16, 2 * cols + 2 * ops + 16 * n + 16, cols + ops + 16)
+    cs = np.zeros(cs_cap if want_cs else 1, dtype=np.uint8)
+    md = np.zeros(md_cap if want_md else 1, dtype=np.uint8)
+    eqx = np.zeros(eqx_cap if want_eqx else 1, dtype=np.uint32)
+    cs_off, md_off, eqx_off = (np.zeros(n + 1, dtype=np.int64) for _ in range(3))
+    rc = lib.mpn_aln_tags_batch(n, qbuf.ctypes.data, qoff.ctypes.data, qlen.ctypes.data, qs.ctypes.data, qe.ctypes.data, rev.ctypes.data,
+                                tbuf.ctypes.data, toff.ctypes.data, tlen.ctypes.data, ts.ctypes.data, cig.ctypes.data, coff.ctypes.data,
+                                ncig.ctypes.data, int(out_tags), cs.ctypes.data, cs_cap if want_cs else 0, cs_off.ctypes.data,
+                                md.ctypes.data, md_cap if want_md else 0, md_off.ctypes.data, eqx.ctypes.data, eqx_cap if want_eqx else 0,
+                                eqx_off.ctypes.data)
+    _ffi.check(rc, 'mpn_aln_tags_batch')
+    res = []
+    for i in range(n):
+        res.append(dict(cs=cs[cs_off[i]:cs_off[i + 1]].tobytes().decode() if want_cs else None,
+                        md=md[md_off[i]:md_off[i + 1]].tobytes().decode() if want_md else None,
+                        eqx=[int(x) for x in eqx[eqx_off[i]:eqx_off[i + 1]]] if want_eqx else None))
+    return res
+
+
 STAT_NAMES = {0: 'bases', 1: 'minimizers', 2: 'anchors', 3: 'chains', 4: 'dp_jobs', 5: 'dp_cells', 6: 'alignments',
               7: 'dp_rounds', 8: 'second_pass_jobs', 10: 'ev_sketch_ns', 11: 'ev_seed_ns', 12: 'ev_sort_ns',
               13: 'ev_chain_dp_ns', 14: 'ev_chain_bt_ns', 15: 'ev_ext_dp_ns', 25: 'ev_ext_bt_ns', 26: 'ev_ext_ztest_ns',
@@ -625,7 +677,8 @@ STAT_NAMES = {0: 'bases', 1: 'minimizers', 2: 'anchors', 3: 'chains', 4: 'dp_job
               # stream (MPN_KERNEL_EVENTS on: two more events per extension group); ev_ext_dp_ns held this time before and no
               # longer does.  Where the side / tile work got leased streams the span is ~0 and their walks are in no slot.
               73: 'walk_wave_windows', 74: 'ev_ext_walk_long_ns',
-              75: 'walk_wave_failed'}   # gap fills the wave z-drop test failed (second pass or inversion probe)
+              75: 'walk_wave_failed',   # gap fills the wave z-drop test failed (second pass or inversion probe)
+              76: 'k_tags_ns'}          # aln_tags_wave_kernel: cs / MD / =X strings (0 unless out_tags asks for them in a text call)
 
 
 def last_stats():

@@ -2,7 +2,7 @@
 bin/lib/aligner.py:239-335) beside the mapping-only rate of the same reads, on a C1-shaped input (1 000 reads x 8 kb against
 5 genomes) and on a 100 000-read input.  Files are written to a scratch directory first (not timed).
 
-  python scripts/bench_align.py [--reads 1000,100000] [--genomes 5] [--genome-len 5000000] [--profile]
+  python scripts/bench_align.py [--reads 1000,100000] [--genomes 5] [--genome-len 5000000] [--profile] [--extra='--cs --MD']
 """
 import argparse
 import cProfile
@@ -63,11 +63,13 @@ def main():
     ap.add_argument('--genome-len', type=int, default=5000000)
     ap.add_argument('--mean-len', type=int, default=8000)
     ap.add_argument('--profile', action='store_true')
+    ap.add_argument('--extra', default='', help="further aligner options, e.g. --extra='--cs --MD' or --extra='--cs=long --eqx'")
     args = ap.parse_args()
     import pandas as pd
     from megapath_nano_amd import aligner, build
     build.build()
     opts = ['-t', '16', '-I', '8G', '-N', '50', '-p', '1', '-x', 'map-ont', '--split-prefix', 'tmp']   # megapath_nano.py:1270
+    opts += args.extra.split()
     go = {'min_alignment_score': 0}
     for n_reads in (int(x) for x in args.reads.split(',')):
         with tempfile.TemporaryDirectory(dir=os.environ.get('TMPDIR', '/tmp')) as d:
@@ -90,7 +92,7 @@ def main():
                 prof.disable()
             t_full = time.perf_counter() - t0
             sizes = {e: os.path.getsize(os.path.join(d, 'out.' + e)) for e in ('paf', 'sam', 'bam', 'bam.bai')}
-            print(json.dumps({'reads': n_reads, 'read_bases': bases, 'rows': int(table.shape[0]), 'rows_with_files': int(table2.shape[0]),
+            print(json.dumps({'extra': args.extra, 'reads': n_reads, 'read_bases': bases, 'rows': int(table.shape[0]), 'rows_with_files': int(table2.shape[0]),
                               'align_table_only_s': round(t_cols, 3), 'align_table_only_gbp_per_min': round(bases / t_cols * 60 / 1e9, 2),
                               'align_paf_sam_bam_s': round(t_full, 3), 'align_paf_sam_bam_gbp_per_min': round(bases / t_full * 60 / 1e9, 2),
                               'output_bytes': sizes}), flush=True)
