@@ -1,5 +1,5 @@
 /*
- * mpn_abundance.h -- C-ABI of the two data-parallel steps of the output formats / abundance statistic:
+ * mpn_abundance.h -- C-ABI of the data-parallel steps of the output formats / abundance statistic:
  *
  *   mpn_sort_order      the coordinate sort of `samtools sort` (reference, position, strand; ties in file order) that the
  *                       reference runs on the species-placement SAM   (/root/reference/bin/lib/aligner.py:246-252)
@@ -8,7 +8,12 @@
  *                       i.e. the covered base pairs of every assembly; the noise-BED variant (`covered_bed.subtract(noise_bed)`,
  *                       :516-518) is two calls: |A \ N| = |A u N| - |N| per sequence (megapath_nano_amd/abundance.py)
  *
- * Both run on the GPU (csrc/interval_kernels.hip: a stable LSD radix sort of 128-bit keys, a three-phase segmented sweep);
+ *   mpn_depth_by_key    `bedtools genomecov -bg` over the target intervals of an alignment table, the per-assembly depth
+ *                       threshold on the profile rows and `bedtools sort | merge` of the rows that pass, with their summed length
+ *                       per assembly (the reference's bin/megapath_nano.py:417-482: align_list_to_depth_bed, behind the spike and
+ *                       variable-region noise BEDs).  bedtools is restated here, not linked or run: see DESIGN.md section 2.
+ *
+ * All run on the GPU (csrc/interval_kernels.hip: a stable LSD radix sort of 128-bit keys, three-phase sweeps over the sorted list);
  * all pointers are HOST pointers, results are exact integers.  Return 0, or a negative error (mpn_last_error()).
  */
 #ifndef MPN_ABUNDANCE_H
@@ -27,6 +32,29 @@ int mpn_sort_order(int64_t n, const uint64_t *hi, const uint64_t *lo, int64_t *o
  * (group[i], seq[i]); 0 <= start <= end < 2^32. */
 int mpn_cover_by_group(int64_t n, const int32_t *group, const int32_t *seq, const int64_t *start, const int64_t *end,
                        int32_t n_groups, int64_t *covered);
+
+/* Events that one block of the depth sweep scans (a multiple of its 256 lanes); block partials are carried between such tiles. */
+#define MPN_DEPTH_TILE 2048
+
+/* Depth profile, depth BED and depth span of n intervals [start, end), 0 <= start, end < 2^32.  Interval i lies on key[i] in
+ * [0, n_keys): one (assembly, sequence) pair of length key_len[k] < 2^32 that belongs to group key_group[k] in [0, n_groups).
+ *   - an interval with start >= end or start >= key_len contributes nothing; an end beyond key_len is clipped to key_len;
+ *   - the depth of a position is the number of contributing intervals that cover it;
+ *   - profile: the maximal runs of constant non-zero depth of every key, ordered by (key, start) -- book-ended intervals do
+ *     not split a row;
+ *   - a row of group g passes iff depth_lo[g] <= depth <= depth_hi[g] (both NULL: every row passes);
+ *   - BED: the passing rows, rows of one key that touch merged, ordered by (key, start);
+ *   - span[g] (zeroed by the call): the summed length of the passing rows of group g.
+ * cap: the capacity of each output list, >= 2n when the profile or the BED is wanted.  The four row_* pointers and n_rows are
+ * all NULL (profile not wanted) or all given; likewise the three bed_* pointers and n_bed; span may be NULL.  n < 2^30.
+ * A record outside the domain or a cap below 2n returns -2 before anything is written. */
+int mpn_depth_by_key(int64_t n, const int32_t *key, const int64_t *start, const int64_t *end,
+                     int32_t n_keys, const int64_t *key_len, const int32_t *key_group,
+                     int32_t n_groups, const int32_t *depth_lo, const int32_t *depth_hi,
+                     int64_t cap,
+                     int32_t *row_key, int64_t *row_start, int64_t *row_end, int32_t *row_depth, int64_t *n_rows,
+                     int32_t *bed_key, int64_t *bed_start, int64_t *bed_end, int64_t *n_bed,
+                     int64_t *span);
 
 #ifdef __cplusplus
 }

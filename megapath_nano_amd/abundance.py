@@ -15,8 +15,16 @@ The interval union runs on the GPU (include/mpn_abundance.h: mpn_cover_by_group 
 `device=True`, the default when libmpn.so can reach a GPU); the numpy form below (`device=False`) is the host statement of
 the same sums and is what the CPU tests pin against plain loops.  `device_sort_order` is the same sort behind
 bam.sam_to_sorted_bam (`samtools sort`).
+
+Depth: `align_list_to_depth_bed` (the reference's bin/megapath_nano.py:417-482: `bedtools genomecov -bg` over the target
+intervals, a per-assembly depth threshold on the profile rows, `bedtools sort | merge` of the rows that pass and their summed
+length per assembly) is the source of every depth-based noise BED: `step_spike_filter` (:1759-1806), the closing spike filter
+(:2359), `step_variable_region` (:1729-1734).  Here it is mpn_depth_by_key (events, the same radix sort, two scans) behind
+`depth_profile`, `align_list_to_depth_bed` and `spike_noise`; `host_depth_by_key` is its numpy statement.  bedtools is restated,
+not run: DESIGN.md section 2 says what that restatement rests on.
 """
 import ctypes as ct
+import math
 
 import numpy as np
 import pandas
@@ -35,6 +43,8 @@ def _lib():
         lib.mpn_sort_order.restype = ct.c_int
         lib.mpn_cover_by_group.argtypes = [ct.c_int64, P, P, P, P, ct.c_int32, P]
         lib.mpn_cover_by_group.restype = ct.c_int
+        lib.mpn_depth_by_key.argtypes = [ct.c_int64, P, P, P, ct.c_int32, P, P, ct.c_int32, P, P, ct.c_int64, P, P, P, P, P, P, P, P, P, P]
+        lib.mpn_depth_by_key.restype = ct.c_int
         _bound = True
     return lib
 
@@ -184,3 +194,188 @@ def align_stat_by_assembly_id(align_list, assembly_length, assembly_tax=None, no
         out['adjusted_total_aligned_bp'] = np.round(clean(aad * L), 0).astype(np.int64)
         out['adjusted_average_depth'] = clean(aad)
     return out
+
+
+# ---- depth profile, depth BED, depth span -----------------------------------------------------------------------------------
+DEPTH_TILE = 2048   # MPN_DEPTH_TILE of include/mpn_abundance.h: the events one block of the device sweep scans (the tests put
+#                     their sizes around its multiples; tests/test_depth_bed.py checks that the two numbers agree)
+
+
+def _depth_args(key, start, end, key_len, key_group, depth_lo, depth_hi):
+    key = np.ascontiguousarray(key, dtype=np.int32)
+    start = np.ascontiguousarray(start, dtype=np.int64)
+    end = np.ascontiguousarray(end, dtype=np.int64)
+    key_len = np.ascontiguousarray(key_len, dtype=np.int64)
+    key_group = np.ascontiguousarray(key_group, dtype=np.int32)
+    if (depth_lo is None) != (depth_hi is None):
+        raise ValueError('depth_lo and depth_hi are given together or not at all')
+    if depth_lo is not None:
+        depth_lo, depth_hi = np.ascontiguousarray(depth_lo, dtype=np.int32), np.ascontiguousarray(depth_hi, dtype=np.int32)
+    return key, start, end, key_len, key_group, depth_lo, depth_hi
+
+
+def device_depth_by_key(key, start, end, key_len, key_group, n_groups, depth_lo=None, depth_hi=None):
+    """mpn_depth_by_key.  Interval i = [start[i], end[i]) on key[i]; key k has length key_len[k] and group key_group[k];
+    depth_lo / depth_hi: inclusive int32 depth range per group (both None: every row passes).
+    -> (row_key, row_start, row_end, row_depth), (bed_key, bed_start, bed_end), span[n_groups]: the whole, unfiltered
+    profile ordered by (key, start); the rows that pass with touching rows merged, in the same order; the summed length of the
+    passing rows per group."""
+    key, start, end, key_len, key_group, depth_lo, depth_hi = _depth_args(key, start, end, key_len, key_group, depth_lo, depth_hi)
+    n, cap = len(key), max(2 * len(key), 1)
+    rk, rs, re, rd = np.empty(cap, np.int32), np.empty(cap, np.int64), np.empty(cap, np.int64), np.empty(cap, np.int32)
+    bk, bs, be = np.empty(cap, np.int32), np.empty(cap, np.int64), np.empty(cap, np.int64)
+    n_rows, n_bed = ct.c_int64(0), ct.c_int64(0)
+    span = np.zeros(max(int(n_groups), 1), dtype=np.int64)
+    lo_p, hi_p = (None, None) if depth_lo is None else (depth_lo.ctypes.data, depth_hi.ctypes.data)
+    _ffi.check(_lib().mpn_depth_by_key(n, key.ctypes.data, start.ctypes.data, end.ctypes.data, len(key_len), key_len.ctypes.data, key_group.ctypes.data,
+                                       int(n_groups), lo_p, hi_p, cap, rk.ctypes.data, rs.ctypes.data, re.ctypes.data, rd.ctypes.data, ct.byref(n_rows),
+                                       bk.ctypes.data, bs.ctypes.data, be.ctypes.data, ct.byref(n_bed), span.ctypes.data), 'mpn_depth_by_key')
+    r, b = n_rows.value, n_bed.value
+    return (rk[:r], rs[:r], re[:r], rd[:r]), (bk[:b], bs[:b], be[:b]), span[:n_groups]
+
+
+def host_depth_by_key(key, start, end, key_len, key_group, n_groups, depth_lo=None, depth_hi=None):
+    """numpy statement of mpn_depth_by_key (same arguments, same result): +1 / -1 events sorted by (key, position), the net
+    change per position, positions without a change dropped, the depth as the running sum."""
+    key, start, end, key_len, key_group, depth_lo, depth_hi = _depth_args(key, start, end, key_len, key_group, depth_lo, depth_hi)
+    end = np.minimum(end, key_len[key]) if len(key) else end        # the clip; start >= key_len then has start >= end
+    on = start < end
+    key, start, end = key[on], start[on], end[on]
+    ek, ep = np.concatenate([key, key]).astype(np.int64), np.concatenate([start, end])
+    ed = np.concatenate([np.ones(len(key), dtype=np.int64), -np.ones(len(key), dtype=np.int64)])
+    order = np.lexsort((ep, ek))
+    ek, ep, ed = ek[order], ep[order], ed[order]
+    first = np.ones(len(ek), dtype=bool)
+    first[1:] = (ek[1:] != ek[:-1]) | (ep[1:] != ep[:-1])
+    net = np.add.reduceat(ed, np.flatnonzero(first)) if len(ek) else ed
+    change = net != 0                                             # equal-depth neighbours merge here
+    pk, pp, depth = ek[first][change], ep[first][change], np.cumsum(net[change])
+    opens = np.flatnonzero(depth > 0)                             # every key's events sum to 0: the next point is on the same key
+    rk, rs, re, rd = pk[opens].astype(np.int32), pp[opens], pp[opens + 1] if len(opens) else pp[opens], depth[opens].astype(np.int32)
+    g = key_group[rk]
+    ok = np.ones(len(rk), dtype=bool) if depth_lo is None else (depth_lo[g] <= rd) & (rd <= depth_hi[g])
+    span = np.bincount(g[ok], weights=(re - rs)[ok].astype(np.float64), minlength=int(n_groups)).astype(np.int64)[:n_groups]
+    fk, fs, fe = rk[ok], rs[ok], re[ok]
+    head = np.ones(len(fk), dtype=bool)
+    head[1:] = (fk[1:] != fk[:-1]) | (fs[1:] != fe[:-1])         # passing rows never overlap: touching is all `merge` can meet
+    tail = np.ones(len(fk), dtype=bool)
+    tail[:-1] = head[1:]
+    return (rk, rs, re, rd), (fk[head], fs[head], fe[tail]), span
+
+
+def depth_bound(threshold, comparison):
+    """The integer bound of a float depth threshold: comparison '<' -> hi = ceil(x) - 1, '<=' -> hi = floor(x),
+    '>' -> lo = floor(x) + 1, '>=' -> lo = ceil(x); clamped to int32."""
+    x = float(threshold)
+    if math.isinf(x):
+        v = x
+    else:
+        v = {'<': math.ceil(x) - 1, '<=': math.floor(x), '>': math.floor(x) + 1, '>=': math.ceil(x)}[comparison]
+    return int(min(max(v, -2 ** 31), 2 ** 31 - 1))
+
+
+def _depth_keys(align_list):
+    """(assembly, sequence) pairs coded in the byte order of assembly_id + ',' + sequence_id (`bedtools sort` on that chrom
+    column; numpy orders str by code point, which is the order of the UTF-8 bytes).
+    -> key[n], key_asm[n_keys] (str), key_seq[n_keys] (str), key_len[n_keys], assemblies (sorted, unique), key_group[n_keys]"""
+    asm = align_list['assembly_id'].to_numpy(dtype=object).astype(str)
+    seq = align_list['sequence_id'].to_numpy(dtype=object).astype(str)
+    code, pairs = pandas.MultiIndex.from_arrays([asm, seq]).factorize()
+    p_asm = np.array([p[0] for p in pairs], dtype=object).astype(str)
+    p_seq = np.array([p[1] for p in pairs], dtype=object).astype(str)
+    order = np.argsort(np.char.add(np.char.add(p_asm, ','), p_seq), kind='stable')
+    rank = np.empty(len(order), dtype=np.int64)
+    rank[order] = np.arange(len(order))
+    key = rank[code]
+    length = align_list['sequence_length'].to_numpy(dtype=np.int64)
+    key_len = np.zeros(len(order), dtype=np.int64)
+    key_len[key] = length
+    if not np.array_equal(key_len[key], length):
+        bad = int(key[np.flatnonzero(key_len[key] != length)[0]])
+        raise ValueError(f'sequence_length differs within ({p_asm[order][bad]}, {p_seq[order][bad]})')
+    assemblies, key_group = np.unique(p_asm[order], return_inverse=True)
+    return key.astype(np.int32), p_asm[order], p_seq[order], key_len, assemblies, key_group.astype(np.int32)
+
+
+def _depth_call(align_list, depth_lo, depth_hi, device):
+    if device is None:
+        device = True
+    key, key_asm, key_seq, key_len, assemblies, key_group = _depth_keys(align_list)
+    run = device_depth_by_key if device else host_depth_by_key
+    out = run(key, align_list['sequence_from'].to_numpy(dtype=np.int64), align_list['sequence_to'].to_numpy(dtype=np.int64), key_len, key_group,
+              len(assemblies), depth_lo(assemblies) if depth_lo else None, depth_hi(assemblies) if depth_hi else None)
+    return out, key_asm, key_seq, assemblies
+
+
+def depth_profile(align_list, device=None):
+    """The bedGraph of the alignments' target intervals (`bedtools genomecov -bg`): DataFrame(assembly_id, sequence_id, start,
+    end, depth), the maximal runs of constant non-zero depth, ordered like the depth BED.  align_list: assembly_id, sequence_id,
+    sequence_from, sequence_to, sequence_length.  device: as in covered_bp_by_assembly."""
+    cols = ['assembly_id', 'sequence_id', 'start', 'end', 'depth']
+    if align_list.shape[0] == 0:
+        return pandas.DataFrame({c: np.zeros(0, dtype=object if c.endswith('_id') else np.int64) for c in cols})
+    ((rk, rs, re, rd), _, _), key_asm, key_seq, _ = _depth_call(align_list, None, None, device)
+    return pandas.DataFrame({'assembly_id': key_asm[rk], 'sequence_id': key_seq[rk], 'start': rs, 'end': re, 'depth': rd.astype(np.int64)}, columns=cols)
+
+
+def _bounds(table, column, assemblies, nan_value, comparison, absent):
+    """int32 bound per assembly from a threshold table; an assembly the table lacks gets `absent` (it passes nothing: the
+    reference merges the table with how='inner')."""
+    ids = table['assembly_id'].astype(str).to_numpy()
+    if len(set(ids)) != len(ids):
+        raise ValueError(f'{column}: an assembly_id occurs twice')
+    out = np.full(len(assemblies), absent, dtype=np.int64)
+    where = pandas.Index(assemblies).get_indexer(ids)
+    for w, x in zip(where, table[column].to_numpy(dtype=np.float64)):
+        if w >= 0:
+            out[w] = depth_bound(nan_value if np.isnan(x) else x, comparison)
+    return out
+
+
+def align_list_to_depth_bed(*, align_list, min_depth=None, can_equal_to_min=True, max_depth=None, can_equal_to_max=True, temp_dir_name=None,
+                            device=None):
+    """The reference's align_list_to_depth_bed with its keyword arguments (temp_dir_name is accepted and ignored).
+    align_list: assembly_id, sequence_id, sequence_from, sequence_to, sequence_length (one length per (assembly, sequence):
+    ValueError otherwise).  min_depth / max_depth: DataFrame(assembly_id, min_depth) / (assembly_id, max_depth), floats; NaN is
+    -1 / 99999999; with a table given, an assembly it lacks passes nothing.
+    -> depth_bed: DataFrame(sequence_id, start, end, assembly_id) ordered by the bytes of assembly_id + ',' + sequence_id, then
+    start (what align_stat_by_assembly_id(noise_bed=...) takes); depth_span_bp: DataFrame(assembly_id, span_bp) of the
+    assemblies with at least one passing row."""
+    if align_list.shape[0] == 0:
+        return (pandas.DataFrame({'sequence_id': np.zeros(0, dtype=object), 'start': np.zeros(0, dtype=np.int64), 'end': np.zeros(0, dtype=np.int64),
+                                  'assembly_id': np.zeros(0, dtype=object)}),
+                pandas.DataFrame({'assembly_id': np.zeros(0, dtype=object), 'span_bp': np.zeros(0, dtype=np.int64)}))
+    lo = hi = None
+    if min_depth is not None or max_depth is not None:
+        # a table that is not given bounds nothing; an assembly absent from a given one gets an empty range from that side
+        def lo(assemblies):
+            if min_depth is None:
+                return np.zeros(len(assemblies), dtype=np.int64)
+            return _bounds(min_depth, 'min_depth', assemblies, -1, '>=' if can_equal_to_min else '>', 2 ** 31 - 1)
+
+        def hi(assemblies):
+            if max_depth is None:
+                return np.full(len(assemblies), 2 ** 31 - 1, dtype=np.int64)
+            return _bounds(max_depth, 'max_depth', assemblies, 99999999, '<=' if can_equal_to_max else '<', 0)
+    (_, (bk, bs, be), span), key_asm, key_seq, assemblies = _depth_call(align_list, lo, hi, device)
+    depth_bed = pandas.DataFrame({'sequence_id': key_seq[bk], 'start': bs, 'end': be, 'assembly_id': key_asm[bk]},
+                                 columns=['sequence_id', 'start', 'end', 'assembly_id'])
+    has = span > 0                                                # a passing row is never empty
+    return depth_bed, pandas.DataFrame({'assembly_id': assemblies[has], 'span_bp': span[has]}, columns=['assembly_id', 'span_bp'])
+
+
+def spike_noise(align_list, assembly_length, expected_max_depth_stdev=6, assembly_tax=None, device=None):
+    """step_spike_filter's computation (megapath_nano.py:1768-1798; the closing filter is the same with stdev 9): the statistic
+    without noise, expected_max_depth = max(1, int(aad + stdev * sqrt(aad))) per assembly with aad = adjusted_average_depth,
+    and the depth BED of the WHOLE table where depth > expected_max_depth.
+    -> noise_bed (as align_list_to_depth_bed), noise_stat: DataFrame(assembly_id, spike_span_bp, spike_span_percent) of the
+    assemblies that have a spike."""
+    stat = align_stat_by_assembly_id(align_list, assembly_length, assembly_tax, device=device)
+    aad = stat['adjusted_average_depth'].to_numpy(dtype=np.float64)
+    expected = np.maximum((aad + expected_max_depth_stdev * np.sqrt(aad)).astype(np.int64), 1)
+    noise_bed, span = align_list_to_depth_bed(align_list=align_list, min_depth=pandas.DataFrame({'assembly_id': stat['assembly_id'], 'min_depth': expected}),
+                                              can_equal_to_min=False, device=device)
+    noise_stat = stat[['assembly_id', 'assembly_length']].merge(span.rename(columns={'span_bp': 'spike_span_bp'}), on='assembly_id', how='inner')
+    with np.errstate(divide='ignore', invalid='ignore'):
+        noise_stat['spike_span_percent'] = noise_stat['spike_span_bp'].to_numpy(dtype=np.float64) / noise_stat['assembly_length'].to_numpy(dtype=np.float64)
+    return noise_bed, noise_stat[['assembly_id', 'spike_span_bp', 'spike_span_percent']]

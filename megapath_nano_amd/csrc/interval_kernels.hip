@@ -95,7 +95,8 @@ __global__ __launch_bounds__(256) void rs_order_kernel(const Rec3 *__restrict__ 
 }
 
 // sorts d_a in place by (hi, lo), stable; d_b: bounce buffer of the same size.  Returns the buffer that holds the result.
-static int radix_sort_rec3(Rec3 *d_a, Rec3 *d_b, int64_t n, Rec3 **result, hipStream_t st) {
+// skip: bit p set = the caller knows that digit p is the same in every record, so pass p is not even counted.
+static int radix_sort_rec3(Rec3 *d_a, Rec3 *d_b, int64_t n, Rec3 **result, hipStream_t st, uint32_t skip = 0) {
     *result = d_a;
     if (n < 2) return 0;
     const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 4095) / 4096));
@@ -108,6 +109,7 @@ static int radix_sort_rec3(Rec3 *d_a, Rec3 *d_b, int64_t n, Rec3 **result, hipSt
     Rec3 *src = d_a, *dst = d_b;
     int rc = 0;
     for (int pass = 0; pass < 16 && !rc; ++pass) {
+        if (skip >> pass & 1) continue;
         hipLaunchKernelGGL(rs_hist_kernel, dim3(n_blocks), dim3(RS_THREADS), 0, st, (const Rec3 *)src, n, chunk, pass, hist.p, n_blocks);
         hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, hist.p, n_blocks, n, flag.p);
         hipLaunchKernelGGL(rs_scatter_kernel, dim3(n_blocks), dim3(RS_THREADS), 0, st, (const Rec3 *)src, dst, n, chunk, pass, (const uint32_t *)hist.p, n_blocks,
@@ -187,6 +189,190 @@ __global__ __launch_bounds__(256) void cov_phase3_kernel(const Rec3 *__restrict_
     if (acc && acc_group < (uint32_t)n_groups) atomicAdd(&covered[acc_group], acc);
 }
 
+
+// ---- depth profile, depth BED and depth span per key (`bedtools genomecov -bg`, threshold, `sort | merge`) ------------------
+// Every contributing interval becomes two events {hi = key, lo = position, idx = +1 / -1}; an interval that contributes nothing
+// becomes two events of weight 0.  After the sort by (key, position) the sweep is two three-phase scans with a lane per element:
+//   A  events -> points: D = inclusive sum of the weights.  Every key's weights sum to zero, so the plain, unsegmented sum is the
+//      depth on the key.  The last event of a (key, position) run carries the depth after that position; these events are
+//      compacted, in order, into points (key, position, depth).
+//   B  points -> rows and BED: with a = depth after point j and b = depth before it (the depth of point j - 1; 0 at j = 0 and,
+//      by the zero sums, at the first point of every key), a row starts at j iff a > 0 and a != b and one ends there iff b > 0
+//      and a != b; a BED interval starts iff a passes the group's range and b does not, and ends iff b passes and a does not.
+//      Starts and ends pair up in order, so the k-th start and the k-th end fill the k-th output row from different lanes and no
+//      lane has to look for the other side of its row.  span[g] = sum of the BED ends - sum of the BED starts.
+// Each phase: per-tile totals (count), one block that turns them into tile bases (prefix), a rescan that writes (fill).
+constexpr int DP_THREADS = 256, DP_ITEMS = MPN_DEPTH_TILE / DP_THREADS;
+static_assert(MPN_DEPTH_TILE % DP_THREADS == 0 && MPN_DEPTH_TILE < 65536, "a tile is whole blocks of lanes, and two tile counts share an int");
+
+// inclusive prefix sums of a and b over the block's 256 lanes: the DPP ladder in a wave, the 4 wave totals through ws[2][4].
+// ta, tb: the block's sums.  One barrier; the caller alternates between two ws so that the next call needs no second one.
+__device__ __forceinline__ void block_scan_add2(int &a, int &b, int (*ws)[4], int &ta, int &tb) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    a = wave_scan_add(a);
+    b = wave_scan_add(b);
+    if (lane == 63) { ws[0][wv] = a; ws[1][wv] = b; }
+    __syncthreads();
+    int pa = 0, pb = 0;
+    ta = 0; tb = 0;
+#pragma unroll
+    for (int w = 0; w < DP_THREADS / 64; ++w) {
+        const int sa = ws[0][w], sb = ws[1][w];
+        if (w < wv) { pa += sa; pb += sb; }
+        ta += sa; tb += sb;
+    }
+    a += pa; b += pb;
+}
+
+__global__ __launch_bounds__(256) void dp_events_kernel(const int32_t *__restrict__ key, const int64_t *__restrict__ start, const int64_t *__restrict__ end,
+                                                        int64_t n, const int64_t *__restrict__ key_len, Rec3 *__restrict__ ev) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t k = key[i];
+        const int64_t len = key_len[k], s = start[i], e = end[i] < len ? end[i] : len;   // the clip; s >= len then gives s >= e
+        const bool on = s < e;
+        ev[2 * i] = Rec3{(uint64_t)(uint32_t)k, on ? (uint64_t)s : 0, on ? 1 : 0};
+        ev[2 * i + 1] = Rec3{(uint64_t)(uint32_t)k, on ? (uint64_t)e : 0, on ? -1 : 0};
+    }
+}
+
+// the last event of its (key, position) run
+__device__ __forceinline__ bool dp_run_ends(const Rec3 *__restrict__ ev, int64_t i, int64_t m, const Rec3 &r) {
+    if (i + 1 == m) return true;
+    return ev[i + 1].hi != r.hi || ev[i + 1].lo != r.lo;
+}
+
+// part[0 * nb + tile] = sum of the tile's weights, part[1 * nb + tile] = number of points the tile yields
+__global__ __launch_bounds__(DP_THREADS) void dp_point_count_kernel(const Rec3 *__restrict__ ev, int64_t m, int32_t *__restrict__ part, int nb) {
+    __shared__ int ws[2][4];
+    const int64_t base = (int64_t)blockIdx.x * MPN_DEPTH_TILE;
+    int d = 0, t = 0;
+#pragma unroll
+    for (int k = 0; k < DP_ITEMS; ++k) {
+        const int64_t i = base + k * DP_THREADS + threadIdx.x;
+        if (i < m) { const Rec3 r = ev[i]; d += (int)r.idx; t += dp_run_ends(ev, i, m, r); }
+    }
+    int td, tt;
+    block_scan_add2(d, t, ws, td, tt);
+    if (threadIdx.x == 0) { part[blockIdx.x] = td; part[(size_t)nb + blockIdx.x] = tt; }
+}
+
+// one block: exclusive scan, in place, of each of the nq rows of part[nq][nb]; total[q] = the sum of row q
+__global__ __launch_bounds__(1024) void dp_prefix_kernel(int32_t *__restrict__ part, int nb, int nq, int32_t *__restrict__ total) {
+    __shared__ int ws[2][16];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, per = (nb + 1023) / 1024, lo = min(nb, t * per), hi = min(nb, lo + per);
+    for (int q = 0; q < nq; ++q) {
+        int32_t *row = part + (size_t)q * nb;
+        int s = 0;
+        for (int k = lo; k < hi; ++k) s += row[k];
+        const int inc = wave_scan_add(s);
+        if (lane == 63) ws[q & 1][wv] = inc;
+        __syncthreads();
+        int o = inc - s, all = 0;
+        for (int w = 0; w < 16; ++w) { const int v = ws[q & 1][w]; if (w < wv) o += v; all += v; }
+        for (int k = lo; k < hi; ++k) { const int v = row[k]; row[k] = o; o += v; }
+        if (t == 0) total[q] = all;
+    }
+}
+
+__global__ __launch_bounds__(DP_THREADS) void dp_point_fill_kernel(const Rec3 *__restrict__ ev, int64_t m, const int32_t *__restrict__ part, int nb,
+                                                                   int32_t *__restrict__ pkey, uint32_t *__restrict__ ppos, int32_t *__restrict__ pdepth) {
+    __shared__ int ws[2][2][4];
+    const int64_t base = (int64_t)blockIdx.x * MPN_DEPTH_TILE;
+    int run_d = part[blockIdx.x], run_t = part[(size_t)nb + blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < DP_ITEMS; ++k) {
+        if (base + k * DP_THREADS >= m) break;   // (the whole block leaves together)
+        const int64_t i = base + k * DP_THREADS + threadIdx.x;
+        Rec3 r{0, 0, 0};
+        int ends = 0;
+        if (i < m) { r = ev[i]; ends = dp_run_ends(ev, i, m, r); }
+        int d = (int)r.idx, t = ends, td, tt;
+        block_scan_add2(d, t, ws[k & 1], td, tt);
+        if (ends) {
+            const int64_t o = (int64_t)(uint32_t)(run_t + t - 1);
+            pkey[o] = (int32_t)r.hi; ppos[o] = (uint32_t)r.lo; pdepth[o] = run_d + d;
+        }
+        run_d += td; run_t += tt;
+    }
+}
+
+struct DpPoint { int32_t a, g; bool row_start, row_end, bed_start, bed_end; };
+
+__device__ __forceinline__ DpPoint dp_classify(int64_t j, const int32_t *__restrict__ pkey, const int32_t *__restrict__ pdepth, const int32_t *__restrict__ key_group,
+                                               const int32_t *__restrict__ dlo, const int32_t *__restrict__ dhi) {
+    DpPoint p;
+    p.a = pdepth[j];
+    const int32_t b = j ? pdepth[j - 1] : 0;
+    p.g = key_group[pkey[j]];
+    const int32_t lo = dlo ? dlo[p.g] : 1, hi = dhi ? dhi[p.g] : 0x7fffffff;
+    const bool pa = p.a > 0 && lo <= p.a && p.a <= hi, pb = b > 0 && lo <= b && b <= hi;
+    p.row_start = p.a > 0 && p.a != b; p.row_end = b > 0 && p.a != b;
+    p.bed_start = pa && !pb; p.bed_end = pb && !pa;
+    return p;
+}
+
+// part[q * nb + tile], q = 0..3: row starts, row ends, BED starts, BED ends among the tile's points.  n_points: on the device
+__global__ __launch_bounds__(DP_THREADS) void dp_row_count_kernel(const int32_t *__restrict__ pkey, const int32_t *__restrict__ pdepth, const int32_t *__restrict__ n_points,
+                                                                  const int32_t *__restrict__ key_group, const int32_t *__restrict__ dlo, const int32_t *__restrict__ dhi,
+                                                                  int32_t *__restrict__ part, int nb) {
+    __shared__ int ws[2][4];
+    const int64_t np = (uint32_t)n_points[0], base = (int64_t)blockIdx.x * MPN_DEPTH_TILE;
+    int rows = 0, beds = 0;   // starts in the low half, ends in the high half: a tile has fewer than 2^16 of either
+#pragma unroll
+    for (int k = 0; k < DP_ITEMS; ++k) {
+        const int64_t j = base + k * DP_THREADS + threadIdx.x;
+        if (j < np) {
+            const DpPoint p = dp_classify(j, pkey, pdepth, key_group, dlo, dhi);
+            rows += (int)p.row_start | (int)p.row_end << 16;
+            beds += (int)p.bed_start | (int)p.bed_end << 16;
+        }
+    }
+    int tr, tb;
+    block_scan_add2(rows, beds, ws, tr, tb);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = tr & 0xffff; part[(size_t)nb + blockIdx.x] = (uint32_t)tr >> 16;
+        part[(size_t)2 * nb + blockIdx.x] = tb & 0xffff; part[(size_t)3 * nb + blockIdx.x] = (uint32_t)tb >> 16;
+    }
+}
+
+// the row_* / bed_* lists and span may be null (not wanted)
+__global__ __launch_bounds__(DP_THREADS) void dp_row_fill_kernel(const int32_t *__restrict__ pkey, const uint32_t *__restrict__ ppos, const int32_t *__restrict__ pdepth,
+                                                                 const int32_t *__restrict__ n_points, const int32_t *__restrict__ key_group,
+                                                                 const int32_t *__restrict__ dlo, const int32_t *__restrict__ dhi, const int32_t *__restrict__ part, int nb,
+                                                                 int32_t *__restrict__ row_key, int64_t *__restrict__ row_start, int64_t *__restrict__ row_end,
+                                                                 int32_t *__restrict__ row_depth, int32_t *__restrict__ bed_key, int64_t *__restrict__ bed_start,
+                                                                 int64_t *__restrict__ bed_end, unsigned long long *__restrict__ span) {
+    __shared__ int ws[2][2][4];
+    const int64_t np = (uint32_t)n_points[0], base = (int64_t)blockIdx.x * MPN_DEPTH_TILE;
+    const int64_t o_rs = (uint32_t)part[blockIdx.x], o_re = (uint32_t)part[(size_t)nb + blockIdx.x];
+    const int64_t o_bs = (uint32_t)part[(size_t)2 * nb + blockIdx.x], o_be = (uint32_t)part[(size_t)3 * nb + blockIdx.x];
+    int run_r = 0, run_b = 0;
+#pragma unroll
+    for (int k = 0; k < DP_ITEMS; ++k) {
+        if (base + k * DP_THREADS >= np) break;   // (the whole block leaves together)
+        const int64_t j = base + k * DP_THREADS + threadIdx.x;
+        DpPoint p{0, 0, false, false, false, false};
+        if (j < np) p = dp_classify(j, pkey, pdepth, key_group, dlo, dhi);
+        int rows = (int)p.row_start | (int)p.row_end << 16, beds = (int)p.bed_start | (int)p.bed_end << 16, tr, tb;
+        block_scan_add2(rows, beds, ws[k & 1], tr, tb);
+        rows += run_r; beds += run_b;
+        if (p.row_start | p.row_end | p.bed_start | p.bed_end) {
+            const int64_t pos = ppos[j];
+            if (row_key) {
+                if (p.row_start) { const int64_t o = o_rs + (rows & 0xffff) - 1; row_key[o] = pkey[j]; row_start[o] = pos; row_depth[o] = p.a; }
+                if (p.row_end) row_end[o_re + ((uint32_t)rows >> 16) - 1] = pos;
+            }
+            if (bed_key) {
+                if (p.bed_start) { const int64_t o = o_bs + (beds & 0xffff) - 1; bed_key[o] = pkey[j]; bed_start[o] = pos; }
+                if (p.bed_end) bed_end[o_be + ((uint32_t)beds >> 16) - 1] = pos;
+            }
+            // integer adds commute and wrap, so ends minus starts is exact in any order
+            if (span && (p.bed_start | p.bed_end)) atomicAdd(&span[p.g], (unsigned long long)(p.bed_end ? pos : -pos));
+        }
+        run_r += tr; run_b += tb;
+    }
+}
+
 }  // namespace mpn
 
 using namespace mpn;
@@ -247,5 +433,100 @@ extern "C" int mpn_cover_by_group(int64_t n, const int32_t *group, const int32_t
     MPN_HIP_CHECK(hipGetLastError());
     if (d_cov.download((unsigned long long *)covered, (size_t)n_groups, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int mpn_depth_by_key(int64_t n, const int32_t *key, const int64_t *start, const int64_t *end, int32_t n_keys, const int64_t *key_len,
+                                const int32_t *key_group, int32_t n_groups, const int32_t *depth_lo, const int32_t *depth_hi, int64_t cap,
+                                int32_t *row_key, int64_t *row_start, int64_t *row_end, int32_t *row_depth, int64_t *n_rows,
+                                int32_t *bed_key, int64_t *bed_start, int64_t *bed_end, int64_t *n_bed, int64_t *span) {
+    const int rows_given = !!row_key + !!row_start + !!row_end + !!row_depth + !!n_rows, bed_given = !!bed_key + !!bed_start + !!bed_end + !!n_bed;
+    if (n < 0 || n >= ((int64_t)1 << 30) || n_keys < 0 || n_groups < 0 || (rows_given != 0 && rows_given != 5) || (bed_given != 0 && bed_given != 4) ||
+        !depth_lo != !depth_hi || (n_keys > 0 && (!key_len || !key_group)) || (n > 0 && (!key || !start || !end))) {
+        set_error("mpn_depth_by_key: bad arguments");
+        return -2;
+    }
+    const bool want_rows = rows_given != 0, want_bed = bed_given != 0;
+    if ((want_rows || want_bed) && cap < 2 * n) { set_error("mpn_depth_by_key: cap %lld is below 2n = %lld", (long long)cap, (long long)(2 * n)); return -2; }
+    int64_t max_len = 0;
+    for (int32_t k = 0; k < n_keys; ++k) {
+        if (key_len[k] < 0 || key_len[k] > 0xffffffffLL || key_group[k] < 0 || key_group[k] >= n_groups) {
+            set_error("mpn_depth_by_key: key %d outside the domain (0 <= key_len < 2^32, key_group in [0, n_groups))", (int)k);
+            return -2;
+        }
+        max_len = std::max(max_len, key_len[k]);
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (key[i] < 0 || key[i] >= n_keys || start[i] < 0 || start[i] > 0xffffffffLL || end[i] < 0 || end[i] > 0xffffffffLL) {
+            set_error("mpn_depth_by_key: record %lld outside the domain (key in [0, n_keys), 0 <= start, end < 2^32)", (long long)i);
+            return -2;
+        }
+    if (n_rows) *n_rows = 0;
+    if (n_bed) *n_bed = 0;
+    if (span) for (int32_t g = 0; g < n_groups; ++g) span[g] = 0;
+    if (n == 0 || !(want_rows || want_bed || span)) return 0;
+
+    hipStream_t st = 0;
+    const int64_t m = 2 * n;
+    DevBuf<int32_t> d_key, d_group, d_lo, d_hi;
+    DevBuf<int64_t> d_start, d_end, d_len;
+    DevBuf<Rec3> a, b;
+    if (d_key.upload(key, (size_t)n, st) || d_start.upload(start, (size_t)n, st) || d_end.upload(end, (size_t)n, st) || d_len.upload(key_len, (size_t)n_keys, st) ||
+        d_group.upload(key_group, (size_t)n_keys, st) || a.alloc((size_t)m) || b.alloc((size_t)m)) return -1;
+    if (depth_lo && (d_lo.upload(depth_lo, (size_t)n_groups, st) || d_hi.upload(depth_hi, (size_t)n_groups, st))) return -1;
+    const int g = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16));
+    hipLaunchKernelGGL(dp_events_kernel, dim3(g), dim3(256), 0, st, (const int32_t *)d_key.p, (const int64_t *)d_start.p, (const int64_t *)d_end.p, n,
+                       (const int64_t *)d_len.p, a.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    // digits that no event has: the bytes of the position above the longest key, those of the key above n_keys - 1, and idx is no key
+    uint32_t skip = 0;
+    for (int p = 0; p < 8; ++p) {
+        if (((uint64_t)max_len >> (8 * p)) == 0) skip |= 1u << p;
+        if (((uint64_t)(n_keys - 1) >> (8 * p)) == 0) skip |= 1u << (8 + p);
+    }
+    Rec3 *ev = nullptr;
+    if (radix_sort_rec3(a.p, b.p, m, &ev, st, skip)) return -1;
+
+    // the points live in the sort's other buffer: 12 bytes a point in the room of 24 bytes an event
+    char *room = (char *)(ev == a.p ? b.p : a.p);
+    int32_t *pkey = (int32_t *)room, *pdepth = (int32_t *)(room + (size_t)8 * m);
+    uint32_t *ppos = (uint32_t *)(room + (size_t)4 * m);
+    const int nb = (int)((m + MPN_DEPTH_TILE - 1) / MPN_DEPTH_TILE);
+    DevBuf<int32_t> part, total;
+    if (part.alloc((size_t)4 * nb) || total.alloc(8)) return -1;
+    hipLaunchKernelGGL(dp_point_count_kernel, dim3(nb), dim3(DP_THREADS), 0, st, (const Rec3 *)ev, m, part.p, nb);
+    hipLaunchKernelGGL(dp_prefix_kernel, dim3(1), dim3(1024), 0, st, part.p, nb, 2, total.p);
+    hipLaunchKernelGGL(dp_point_fill_kernel, dim3(nb), dim3(DP_THREADS), 0, st, (const Rec3 *)ev, m, (const int32_t *)part.p, nb, pkey, ppos, pdepth);
+    const int32_t *n_points = total.p + 1, *lo_p = depth_lo ? d_lo.p : nullptr, *hi_p = depth_lo ? d_hi.p : nullptr;
+    hipLaunchKernelGGL(dp_row_count_kernel, dim3(nb), dim3(DP_THREADS), 0, st, (const int32_t *)pkey, (const int32_t *)pdepth, n_points, (const int32_t *)d_group.p,
+                       lo_p, hi_p, part.p, nb);
+    hipLaunchKernelGGL(dp_prefix_kernel, dim3(1), dim3(1024), 0, st, part.p, nb, 4, total.p + 4);
+    MPN_HIP_CHECK(hipGetLastError());
+    int32_t h_total[8];
+    if (total.download(h_total, 8, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    const int64_t nr = (uint32_t)h_total[4], nbed = (uint32_t)h_total[6];
+    if (nr != (int64_t)(uint32_t)h_total[5] || nbed != (int64_t)(uint32_t)h_total[7] || nr > m || nbed > m) {
+        set_error("mpn_depth_by_key: %lld row starts, %lld row ends, %lld BED starts, %lld BED ends do not pair up", (long long)nr,
+                  (long long)(uint32_t)h_total[5], (long long)nbed, (long long)(uint32_t)h_total[7]);
+        return -1;
+    }
+    DevBuf<int32_t> r_key, r_depth, b_key;
+    DevBuf<int64_t> r_start, r_end, b_start, b_end;
+    DevBuf<unsigned long long> d_span;
+    if (want_rows && (r_key.alloc((size_t)nr) || r_depth.alloc((size_t)nr) || r_start.alloc((size_t)nr) || r_end.alloc((size_t)nr))) return -1;
+    if (want_bed && (b_key.alloc((size_t)nbed) || b_start.alloc((size_t)nbed) || b_end.alloc((size_t)nbed))) return -1;
+    if (span && (d_span.alloc((size_t)n_groups) || d_span.zero(st))) return -1;
+    hipLaunchKernelGGL(dp_row_fill_kernel, dim3(nb), dim3(DP_THREADS), 0, st, (const int32_t *)pkey, (const uint32_t *)ppos, (const int32_t *)pdepth, n_points,
+                       (const int32_t *)d_group.p, lo_p, hi_p, (const int32_t *)part.p, nb, want_rows ? r_key.p : nullptr, r_start.p, r_end.p, r_depth.p,
+                       want_bed ? b_key.p : nullptr, b_start.p, b_end.p, span ? d_span.p : nullptr);
+    MPN_HIP_CHECK(hipGetLastError());
+    if (want_rows && (r_key.download(row_key, (size_t)nr, st) || r_start.download(row_start, (size_t)nr, st) || r_end.download(row_end, (size_t)nr, st) ||
+                      r_depth.download(row_depth, (size_t)nr, st))) return -1;
+    if (want_bed && (b_key.download(bed_key, (size_t)nbed, st) || b_start.download(bed_start, (size_t)nbed, st) || b_end.download(bed_end, (size_t)nbed, st))) return -1;
+    if (span && d_span.download((unsigned long long *)span, (size_t)n_groups, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    if (n_rows) *n_rows = nr;
+    if (n_bed) *n_bed = nbed;
     return 0;
 }
