@@ -153,6 +153,20 @@ int mpn_aln_tags_batch(int32_t n, const uint8_t *qcodes, const int64_t *q_off, c
                        char *cs, int64_t cs_cap, int64_t *cs_off, char *md, int64_t md_cap, int64_t *md_off,
                        uint32_t *eqx, int64_t eqx_cap, int64_t *eqx_off);
 
+/* ---- stage: the CIGAR finishing kernel on arbitrary alignments (tests) ------------------------------------------------------
+ * What every reported alignment passes through (minimap2's mm_fix_cigar + mm_update_extra), launched exactly as mpn_map_batch
+ * launches it.  Pairs as for mpn_aln_tags_batch, but ops of length 0 are allowed; scoring (a, b, sc_ambi, q, e) from opt.
+ * Validated on the host before any launch: only ops 0..2, exactly qe-qs read bases consumed, inside the target; else -1.
+ * force_class: 0 = the launch class by need as in the product, 1 / 2 / 3 = the 16 / 32 / 64 KB LDS class for every pair (-1 if a
+ * pair does not fit), 4 = the global-scratch instantiation for all.  out8[i*8..] = n_cigar, qshift, tshift, blen, mlen,
+ * n_ambi, dp_max, 0; the fixed CIGAR of pair i at cigar_out[cig_off[i] .. +n_cigar) (cigar_out as large as cigar).  A pair with
+ * n_cigar = 0 is not launched and returns zeros.  Returns 0, or -1 on bad arguments or a device error. */
+int mpn_aln_finish_batch(const mpn_map_opt *opt, int32_t n, const uint8_t *qcodes, const int64_t *q_off, const int32_t *q_len,
+                         const int32_t *qs, const int32_t *qe, const int32_t *rev,
+                         const uint8_t *tcodes, const int64_t *t_off, const int32_t *t_len, const int32_t *ts,
+                         const uint32_t *cigar, const int64_t *cig_off, const int32_t *n_cigar, int32_t force_class,
+                         int32_t *out8, uint32_t *cigar_out);
+
 /* ---- product call: map a batch of reads, PAF text out ----------------------------------------------------
  * names: n NUL-terminated read names.  paf receives the lines of all reads in input order (NUL terminated).
  * Returns the number of bytes written, or negative error (-3: paf_cap too small). */

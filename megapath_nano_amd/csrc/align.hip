@@ -1371,6 +1371,68 @@ template <typename Stream> static int tags_fetch(Slot &SL, TagRun &tr, Stream &s
     return 0;
 }
 
+// ---- the finishing kernel (fin_kernels.h): host side -----------------------------------------------------------------------
+// fin_enqueue builds the launch lists of aln_finish_wave_kernel by LDS need (CIGAR, shift table, both code arrays: three LDS
+// classes, the rest works in global scratch; a fourth class of 152 KB for the longest alignments runs them faster but blocks
+// whole CUs: -2 % under the full pipeline) and launches them on st.  dims: the alignments to finish (FinJob / CIGARs resident,
+// every one with at least one op); n_ops_total: the size of the CIGAR pool.  fr keeps the scratch the launches use: it must
+// outlive the caller's wait on the stream.  fr.order: the alignments in launch order.  force_class (tests): 0 by need, 1..3 that
+// LDS class for every alignment (refused if one does not fit), 4 the global-scratch instantiation for all.
+struct FinRun {
+    std::vector<int32_t> order;
+    DevBuf<uint32_t> d_aux;
+    DevBuf<uint8_t> d_codes;
+    DevBuf<int64_t> d_code_offs;
+    DevBuf<int32_t> d_list;
+};
+
+static int fin_enqueue(const std::vector<TagJobDim> &dims, int64_t n_ops_total, const mpn_map_opt *opt, const FinJob *d_fj, FinOut *d_fo,
+                       uint32_t *d_cig, const uint8_t *d_seqs, const int64_t *d_off, const int32_t *d_len, const RefView &rvw, int force_class,
+                       hipStream_t st, FinRun &fr, EvTimer *ev = nullptr) {
+    constexpr int NC = 3;
+    static const size_t kLds[NC] = {(size_t)16 << 10, (size_t)32 << 10, (size_t)64 << 10};
+    if (force_class < 0 || force_class > NC + 1) { set_error("finishing kernel: force_class %d is none of 0..%d", force_class, NC + 1); return -1; }
+    std::vector<int32_t> lists[NC + 1];
+    std::vector<int64_t> code_offs;
+    int64_t code_bytes = 0;
+    for (const TagJobDim &d : dims) {
+        const size_t codes = (size_t)((std::max(0, d.qspan) + 3) & ~3) + (size_t)((std::max(0, d.tspan) + 3) & ~3);
+        const size_t need = (size_t)d.n_ops * 8 + codes + 16;
+        int c = 0;
+        if (force_class == 0) { while (c < NC && need > kLds[c]) ++c; }
+        else {
+            c = force_class - 1;
+            if (c < NC && need > kLds[c]) { set_error("finishing kernel: alignment %d needs %zu bytes, more than the forced LDS class of %zu", d.id, need, kLds[c]); return -1; }
+        }
+        if (c == NC) { code_offs.push_back(code_bytes); code_bytes += (int64_t)codes; }
+        lists[c].push_back(d.id);
+    }
+    int base[NC + 1];
+    fr.order.clear();
+    for (int c = 0; c <= NC; ++c) { base[c] = (int)fr.order.size(); fr.order.insert(fr.order.end(), lists[c].begin(), lists[c].end()); }
+    if (fr.order.empty()) return 0;
+    if (!lists[NC].empty() && (fr.d_aux.alloc((size_t)n_ops_total + 1) || fr.d_codes.alloc((size_t)code_bytes + 16) || fr.d_code_offs.upload(code_offs.data(), code_offs.size(), st)))
+        return -1;
+    if (fr.d_list.upload(fr.order.data(), fr.order.size(), st)) return -1;
+    FinParams prm;
+    for (int i = 0; i < 4; ++i) { for (int j = 0; j < 4; ++j) prm.mat[i * 5 + j] = (int8_t)(i == j ? opt->a : -opt->b); prm.mat[i * 5 + 4] = (int8_t)-opt->sc_ambi; }
+    for (int i = 0; i < 5; ++i) prm.mat[20 + i] = (int8_t)-opt->sc_ambi;
+    prm.q = (int8_t)opt->q; prm.e = (int8_t)opt->e;
+    if (ev) ev->skip();   // (the span charged to the kernel holds its launches alone, not the uploads)
+    MPN_HIP_CHECK(hipFuncSetAttribute((const void *)aln_finish_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds[NC - 1]));
+    for (int c = 0; c < NC; ++c)
+        if (!lists[c].empty())
+            hipLaunchKernelGGL(aln_finish_wave_kernel<true>, dim3((unsigned)std::min<size_t>(lists[c].size(), 256 * 64)), dim3(64), kLds[c], st, d_fj,
+                               (const int32_t *)fr.d_list.p + base[c], (int)lists[c].size(), d_cig, (uint32_t *)nullptr, (uint8_t *)nullptr, d_seqs, d_off, d_len, rvw, prm, d_fo,
+                               (const int64_t *)nullptr);
+    if (!lists[NC].empty())
+        hipLaunchKernelGGL(aln_finish_wave_kernel<false>, dim3((unsigned)std::min<size_t>(lists[NC].size(), 256 * 64)), dim3(64), 0, st, d_fj,
+                           (const int32_t *)fr.d_list.p + base[NC], (int)lists[NC].size(), d_cig, fr.d_aux.p, fr.d_codes.p, d_seqs, d_off, d_len, rvw, prm, d_fo,
+                           (const int64_t *)fr.d_code_offs.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadState *rs, int n, const int32_t *seq_len, const DevRound &dv,
                              const RoundDev &rd, const std::vector<int32_t> &sr_base, const uint8_t *d_seqs, const int64_t *d_off, const int32_t *d_len,
                              int n_threads, StreamLease &st) {
@@ -1421,55 +1483,21 @@ static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadS
             if (has) { S.regs.insert(S.regs.begin() + k + 1, r2); ++shift; }
         }
     }, 4);
-    // launch lists of the finishing kernel by LDS need (CIGAR, shift table, both code arrays): three LDS classes, the rest works
-    // in global scratch (a fourth class of 152 KB for the longest alignments runs them faster but blocks whole CUs: -2 % under
-    // the full pipeline).  Hits without operations have nothing to fix (what update_extra leaves for an empty CIGAR).
-    constexpr int NC = 3;
-    static const size_t kLds[NC] = {(size_t)16 << 10, (size_t)32 << 10, (size_t)64 << 10};
-    std::vector<int32_t> lists[NC + 1];
-    std::vector<int64_t> code_offs;
-    int64_t code_bytes = 0;
+    // hits without operations have nothing to fix (what update_extra leaves for an empty CIGAR)
+    std::vector<TagJobDim> fin_dims;
     for (int j = 0; j < n_sr; ++j) {
         const StitchOut &so = h_so[j];
         if (so.n_ops == 0 || !so.has_p) continue;
-        const size_t codes = (size_t)((std::max(0, so.qe1 - so.qs1) + 3) & ~3) + (size_t)((std::max(0, so.re1 - so.rs1) + 3) & ~3);
-        const size_t need = (size_t)so.n_ops * 8 + codes + 16;
-        int c = 0;
-        while (c < NC && need > kLds[c]) ++c;
-        if (c == NC) { code_offs.push_back(code_bytes); code_bytes += (int64_t)codes; }
-        lists[c].push_back(j);
+        fin_dims.push_back({j, so.n_ops, so.qe1 - so.qs1, so.re1 - so.rs1});
     }
-    std::vector<int32_t> order;
-    int base[NC + 1];
-    for (int c = 0; c <= NC; ++c) { base[c] = (int)order.size(); order.insert(order.end(), lists[c].begin(), lists[c].end()); }
     const int out_tags = g_need_cigar ? norm_tags(opt->out_tags) : 0;   // nothing is launched, allocated or copied without them
     const bool want_tags = out_tags != 0, want_eqx = (out_tags & MPN_TAG_EQX) != 0;
     TagRun tr;
+    FinRun fr;
+    const RefView rvw{idx->d_seq2.p, idx->d_seq_off.p, idx->d_nrun_s.p, idx->d_nrun_e.p, idx->n_nruns};
+    if (fin_enqueue(fin_dims, n_ops, opt, d_fj, d_fo, d_cig, d_seqs, d_off, d_len, rvw, 0, st, fr, &ev)) return -1;
+    const std::vector<int32_t> &order = fr.order;
     if (!order.empty()) {
-        DevBuf<uint32_t> d_aux;
-        DevBuf<uint8_t> d_codes;
-        DevBuf<int64_t> d_code_offs;
-        DevBuf<int32_t> d_list;
-        if (!lists[NC].empty() && (d_aux.alloc((size_t)n_ops + 1) || d_codes.alloc((size_t)code_bytes + 16) || d_code_offs.upload(code_offs.data(), code_offs.size(), st)))
-            return -1;
-        if (d_list.upload(order.data(), order.size(), st)) return -1;
-        FinParams prm;
-        for (int i = 0; i < 4; ++i) { for (int j = 0; j < 4; ++j) prm.mat[i * 5 + j] = (int8_t)(i == j ? opt->a : -opt->b); prm.mat[i * 5 + 4] = (int8_t)-opt->sc_ambi; }
-        for (int i = 0; i < 5; ++i) prm.mat[20 + i] = (int8_t)-opt->sc_ambi;
-        prm.q = (int8_t)opt->q; prm.e = (int8_t)opt->e;
-        const RefView rvw{idx->d_seq2.p, idx->d_seq_off.p, idx->d_nrun_s.p, idx->d_nrun_e.p, idx->n_nruns};
-        ev.skip();
-        MPN_HIP_CHECK(hipFuncSetAttribute((const void *)aln_finish_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds[NC - 1]));
-        for (int c = 0; c < NC; ++c)
-            if (!lists[c].empty())
-                hipLaunchKernelGGL(aln_finish_wave_kernel<true>, dim3((unsigned)std::min<size_t>(lists[c].size(), 256 * 64)), dim3(64), kLds[c], st, (const FinJob *)d_fj,
-                                   (const int32_t *)d_list.p + base[c], (int)lists[c].size(), d_cig, (uint32_t *)nullptr, (uint8_t *)nullptr, d_seqs, d_off, d_len, rvw, prm, d_fo,
-                                   (const int64_t *)nullptr);
-        if (!lists[NC].empty())
-            hipLaunchKernelGGL(aln_finish_wave_kernel<false>, dim3((unsigned)std::min<size_t>(lists[NC].size(), 256 * 64)), dim3(64), 0, st, (const FinJob *)d_fj,
-                               (const int32_t *)d_list.p + base[NC], (int)lists[NC].size(), d_cig, d_aux.p, d_codes.p, d_seqs, d_off, d_len, rvw, prm, d_fo,
-                               (const int64_t *)d_code_offs.p);
-        MPN_HIP_CHECK(hipGetLastError());
         ev.mark(52);
         if (want_tags) {   // cs / MD / =X of the round's alignments, while their part of the target set is resident (tag_kernels.h)
             std::vector<TagJobDim> dims;
@@ -2726,6 +2754,74 @@ extern "C" int mpn_aln_tags_batch(int32_t n, const uint8_t *qcodes, const int64_
             if (to.n_eqx) memcpy(eqx + e_used, tr.h_eqx + to.eqx_off, (size_t)to.n_eqx * 4);
             e_used += to.n_eqx; eqx_off[i + 1] = e_used;
         }
+    }
+    return 0;
+}
+
+// stage entry point for the tests of the finishing kernel: aln_finish_wave_kernel, launched by fin_enqueue as the product
+// launches it, on arbitrary (read, target, CIGAR) triples
+extern "C" int mpn_aln_finish_batch(const mpn_map_opt *opt, int32_t n, const uint8_t *qcodes, const int64_t *q_off, const int32_t *q_len,
+                                    const int32_t *qs, const int32_t *qe, const int32_t *rev, const uint8_t *tcodes, const int64_t *t_off,
+                                    const int32_t *t_len, const int32_t *ts, const uint32_t *cigar, const int64_t *cig_off, const int32_t *n_cigar,
+                                    int32_t force_class, int32_t *out8, uint32_t *cigar_out) {
+    std::lock_guard<std::mutex> call_guard(g_call_mu);
+    hipStream_t st = 0;
+    if (n < 0) { set_error("mpn_aln_finish_batch: negative count"); return -1; }
+    if (n == 0) return 0;
+    if (!opt || !out8 || !cigar_out) { set_error("mpn_aln_finish_batch: options or an output array missing"); return -1; }
+    // everything is checked here, before any launch: only M/I/D ops (empty ones allowed), exactly the read interval, inside the target
+    int64_t qtot = 0, ttot = 0, ctot = 0;
+    std::vector<FinJob> jobs((size_t)n);
+    std::vector<TagJobDim> dims;
+    for (int i = 0; i < n; ++i) {
+        if (q_len[i] < 0 || t_len[i] < 0 || n_cigar[i] < 0 || qs[i] < 0 || qe[i] < qs[i] || qe[i] > q_len[i] || ts[i] < 0 || ts[i] > t_len[i] || cig_off[i] < 0) {
+            set_error("mpn_aln_finish_batch: pair %d: intervals outside the sequences", i); return -1;
+        }
+        int64_t ql = 0, tl = 0;
+        for (int k = 0; k < n_cigar[i]; ++k) {
+            const uint32_t c = cigar[cig_off[i] + k], op = c & 0xf, len = c >> 4;
+            if (op > 2) { set_error("mpn_aln_finish_batch: pair %d: op %d is not M, I or D", i, k); return -1; }
+            ql += op != 2 ? len : 0; tl += op != 1 ? len : 0;
+        }
+        if (ql != qe[i] - qs[i] || ts[i] + tl > t_len[i]) { set_error("mpn_aln_finish_batch: pair %d: the CIGAR does not consume its read interval or leaves the target", i); return -1; }
+        qtot = std::max<int64_t>(qtot, q_off[i] + q_len[i]); ttot = std::max<int64_t>(ttot, t_off[i] + t_len[i]);
+        ctot = std::max<int64_t>(ctot, cig_off[i] + n_cigar[i]);
+        FinJob &f = jobs[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        f.cig_off = cig_off[i]; f.n_cigar = n_cigar[i]; f.read = i; f.rid = i; f.rev = rev[i] ? 1 : 0;
+        f.qs1 = rev[i] ? q_len[i] - qe[i] : qs[i]; f.rs1 = ts[i]; f.qspan = (int32_t)ql; f.tspan = (int32_t)tl;
+        if (n_cigar[i] > 0) dims.push_back({i, n_cigar[i], (int32_t)ql, (int32_t)tl});   // (as in the product: no ops, no launch)
+    }
+    std::vector<uint8_t> ascii(((size_t)qtot + 19) & ~(size_t)3, 'N');
+    for (int64_t i = 0; i < qtot; ++i) ascii[(size_t)i] = (uint8_t)"ACGTN"[qcodes[i] > 4 ? 4 : qcodes[i]];
+    std::vector<uint32_t> words;
+    std::vector<int64_t> ns, ne;
+    pack_2bit(tcodes, ttot, words, ns, ne);
+    std::vector<FinOut> fouts((size_t)n);
+    memset(fouts.data(), 0, fouts.size() * sizeof(FinOut));
+    DevBuf<uint8_t> d_reads;
+    DevBuf<uint32_t> d_ref, d_cig;
+    DevBuf<int64_t> d_qoff, d_toff, d_ns, d_ne;
+    DevBuf<int32_t> d_qlen;
+    DevBuf<FinJob> d_fj;
+    DevBuf<FinOut> d_fo;
+    std::vector<uint32_t> cig_pad(cigar, cigar + ctot);
+    cig_pad.push_back(0);
+    if (d_reads.upload(ascii.data(), ascii.size(), st) || d_ref.upload(words.data(), words.size(), st) || d_ns.upload(ns.data(), ns.size(), st) ||
+        d_ne.upload(ne.data(), ne.size(), st) || d_qoff.upload(q_off, n, st) || d_qlen.upload(q_len, n, st) || d_toff.upload(t_off, n, st) ||
+        d_cig.upload(cig_pad.data(), cig_pad.size(), st) || d_fj.upload(jobs.data(), jobs.size(), st) || d_fo.upload(fouts.data(), fouts.size(), st))
+        return -1;
+    FinRun fr;
+    const RefView rvw{d_ref.p, d_toff.p, d_ns.p, d_ne.p, (int32_t)ns.size()};
+    if (fin_enqueue(dims, ctot, opt, d_fj.p, d_fo.p, d_cig.p, d_reads.p, d_qoff.p, d_qlen.p, rvw, force_class, st, fr)) return -1;
+    if (d_fo.download(fouts.data(), fouts.size(), st) || d_cig.download(cig_pad.data(), (size_t)ctot, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) {
+        const FinOut &f = fouts[(size_t)i];
+        if (f.n_cigar < 0 || f.n_cigar > n_cigar[i]) { set_error("mpn_aln_finish_batch: pair %d: the kernel returned %d ops for a CIGAR of %d", i, f.n_cigar, n_cigar[i]); return -1; }
+        int32_t *o = out8 + (size_t)i * 8;
+        o[0] = f.n_cigar; o[1] = f.qshift; o[2] = f.tshift; o[3] = f.blen; o[4] = f.mlen; o[5] = f.n_ambi; o[6] = f.dp_max; o[7] = f.pad;
+        if (f.n_cigar) memcpy(cigar_out + cig_off[i], cig_pad.data() + cig_off[i], (size_t)f.n_cigar * 4);
     }
     return 0;
 }

@@ -126,6 +126,8 @@ def _bind():
         lib.mpn_aln_tags_batch.argtypes = [ct.c_int32, P, P, P, P, P, P, P, P, P, P, P, P, P, ct.c_int32, P, ct.c_int64, P, P, ct.c_int64, P,
                                            P, ct.c_int64, P]
         lib.mpn_aln_tags_batch.restype = ct.c_int
+        lib.mpn_aln_finish_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, P, P, P, P, P, P, P, P, P, P, P, P, P, ct.c_int32, P, P]
+        lib.mpn_aln_finish_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
         lib.mpn_map_last_stats_ex.argtypes = [P, ct.c_int32]
@@ -656,6 +658,41 @@ def aln_tags_batch(queries, q_ivals, revs, targets, t_starts, cigars, out_tags, 
         res.append(dict(cs=cs[cs_off[i]:cs_off[i + 1]].tobytes().decode() if want_cs else None,
                         md=md[md_off[i]:md_off[i + 1]].tobytes().decode() if want_md else None,
                         eqx=[int(x) for x in eqx[eqx_off[i]:eqx_off[i + 1]]] if want_eqx else None))
+    return res
+
+
+
+def aln_finish_batch(opt, queries, q_ivals, revs, targets, t_starts, cigars, force_class=0):
+    """The CIGAR finishing kernel on arbitrary alignments (mpn_aln_finish_batch); arguments as for aln_tags_batch, ops of length
+    0 allowed, scoring from opt.  force_class: 0 the launch class as the mapper chooses it, 1..3 the 16 / 32 / 64 KB LDS class, 4
+    global scratch.  -> list of dict(n_cigar, qshift, tshift, blen, mlen, n_ambi, dp_max, cigar)."""
+    lib = _bind()
+    n = len(queries)
+    qbuf, qoff, qlen = pack_seqs([np.asarray(q, dtype=np.uint8) for q in queries])
+    tbuf, toff, tlen = pack_seqs([np.asarray(t, dtype=np.uint8) for t in targets])
+    qs = np.ascontiguousarray([iv[0] for iv in q_ivals], dtype=np.int32)
+    qe = np.ascontiguousarray([iv[1] for iv in q_ivals], dtype=np.int32)
+    rev = np.ascontiguousarray(np.broadcast_to(np.asarray(revs, dtype=np.int32), (n,)))
+    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(t_starts, dtype=np.int32), (n,)))
+    ncig = np.array([len(c) for c in cigars], dtype=np.int32)
+    coff = np.zeros(n, dtype=np.int64)
+    if n > 1:
+        coff[1:] = np.cumsum(ncig[:-1].astype(np.int64))
+    cig = np.zeros(int(ncig.astype(np.int64).sum()) + 1, dtype=np.uint32)
+    for c, o in zip(cigars, coff):
+        cig[o:o + len(c)] = np.asarray(c, dtype=np.uint32)
+    out = np.zeros((n, 8), dtype=np.int32)
+    fixed = np.zeros_like(cig)
+    rc = lib.mpn_aln_finish_batch(ct.byref(opt), n, qbuf.ctypes.data, qoff.ctypes.data, qlen.ctypes.data, qs.ctypes.data, qe.ctypes.data,
+                                  rev.ctypes.data, tbuf.ctypes.data, toff.ctypes.data, tlen.ctypes.data, ts.ctypes.data, cig.ctypes.data,
+                                  coff.ctypes.data, ncig.ctypes.data, int(force_class), out.ctypes.data, fixed.ctypes.data)
+    _ffi.check(rc, 'mpn_aln_finish_batch')
+    keys = ('n_cigar', 'qshift', 'tshift', 'blen', 'mlen', 'n_ambi', 'dp_max')
+    res = []
+    for i in range(n):
+        d = {k: int(out[i, j]) for j, k in enumerate(keys)}
+        d['cigar'] = fixed[coff[i]:coff[i] + d['n_cigar']].tolist()
+        res.append(d)
     return res
 
 

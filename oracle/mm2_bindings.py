@@ -77,6 +77,8 @@ def lib():
         L.mmo_map_read_split.restype = ct.POINTER(Reg)
         L.mmo_extd2.argtypes = [ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int8, ct.c_int8, ct.c_int8, ct.c_int8,
                                 ct.c_int8, ct.c_int8, ct.c_int8, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.POINTER(Ez)]
+        L.mmo_fix_update.argtypes = [ct.c_void_p, ct.c_int32, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p]
+        L.mmo_fix_update.restype = None
         _lib = L
     return _lib
 
@@ -232,4 +234,17 @@ def extd2(query, target, sc_mch=2, sc_mis=-4, sc_n=-1, q=4, e=2, q2=24, e2=1, w=
     d['cigar'] = [int(ez.cigar[k]) for k in range(ez.n_cigar)]
     if ez.cigar:
         lib().mmo_free(ez.cigar)
+    return d
+
+
+def fix_update(cigar, q, t, a=2, b=4, sc_ambi=1, q_=4, e=2):
+    """fix_cigar + update_extra of the oracle on one alignment: cigar words len << 4 | op, q / t 0..4 codes in alignment orientation
+    -> dict(n_cigar, qshift, tshift, blen, mlen, n_ambi, dp_max, cigar)"""
+    cig = np.ascontiguousarray(list(cigar) + [0], dtype=np.uint32)
+    qq = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint8), np.zeros(8, np.uint8)]))
+    tt = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.uint8), np.zeros(8, np.uint8)]))
+    out = np.zeros(8, dtype=np.int32)
+    lib().mmo_fix_update(cig.ctypes.data, len(cigar), qq.ctypes.data, tt.ctypes.data, a, b, sc_ambi, q_, e, out.ctypes.data)
+    d = {k: int(out[j]) for j, k in enumerate(('n_cigar', 'qshift', 'tshift', 'blen', 'mlen', 'n_ambi', 'dp_max'))}
+    d['cigar'] = cig[:d['n_cigar']].tolist()
     return d

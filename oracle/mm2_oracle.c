@@ -1068,6 +1068,23 @@ static void update_extra(mmo_reg *r, const uint8_t *qseq, const uint8_t *tseq, c
     r->dp_max = max;
 }
 
+/* fix_cigar + update_extra above on a caller's alignment (tests of the finishing kernel): cigar[n_cigar] is fixed in place; qseq / tseq
+ * are the 0..4 codes the CIGAR walks; out8 = n_cigar, qshift, tshift, blen, mlen, n_ambi, dp_max, 0 */
+void mmo_fix_update(uint32_t *cigar, int32_t n_cigar, const uint8_t *qseq, const uint8_t *tseq, int a, int b, int sc_ambi, int q, int e,
+                    int32_t *out8)
+{
+    mmo_reg r;
+    int8_t mat[25];
+    int i, j, qshift, tshift;
+    memset(&r, 0, sizeof(r));
+    r.cigar = cigar, r.n_cigar = n_cigar, r.has_p = 1;
+    for (i = 0; i < 4; ++i) { for (j = 0; j < 4; ++j) mat[i * 5 + j] = i == j ? a : -b; mat[i * 5 + 4] = -sc_ambi; }
+    for (i = 0; i < 5; ++i) mat[20 + i] = -sc_ambi;
+    update_extra(&r, qseq, tseq, mat, (int8_t)q, (int8_t)e);
+    qshift = r.qs, tshift = r.rs; /* (forward strand, both from 0: what fix_cigar moved) */
+    out8[0] = r.n_cigar, out8[1] = qshift, out8[2] = tshift, out8[3] = r.blen, out8[4] = r.mlen, out8[5] = r.n_ambi, out8[6] = r.dp_max, out8[7] = 0;
+}
+
 static void fix_bad_ends(const mmo_reg *r, const mm128 *a, int bw, int min_match, int32_t *as, int32_t *cnt)
 {
     int32_t i, l, m;

@@ -107,6 +107,11 @@ void mmo_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *target, 
                int8_t sc_n, int8_t q, int8_t e, int8_t q2, int8_t e2, int w, int zdrop, int end_bonus, int flag,
                mmo_ez *ez);
 
+/* the static fix_cigar + update_extra of the mapper on a caller's alignment: cigar is fixed in place, qseq / tseq are 0..4 codes in
+ * alignment orientation; out8 = n_cigar, qshift, tshift, blen, mlen, n_ambi, dp_max, 0 */
+void mmo_fix_update(uint32_t *cigar, int32_t n_cigar, const uint8_t *qseq, const uint8_t *tseq, int a, int b, int sc_ambi, int q, int e,
+                    int32_t *out8);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,26 @@ def small_world(seed=1, n_genomes=5, glen=120000, n_reads=40, mean_len=3000):
     return gen, reads
 
 
+def repeat_world(seed=21, n_genomes=3, glen=100000, n_reads=40, mean_len=3000):
+    """Genomes that carry a tandem-repeat tract of period 1..6 and 30..200 bases every couple of kb (a few bases of each tract
+    randomised), and ONT-like reads over them on both strands: the indels that fall into a tract can slide, which is what the
+    CIGAR finishing works on."""
+    rng = np.random.default_rng(seed)
+    gen = []
+    for i in range(n_genomes):
+        g = synth.random_genome(rng, glen, gc=float(rng.uniform(0.4, 0.6)))
+        pos = int(rng.integers(200, 1500))
+        while pos + 200 < glen:
+            period, ln = int(rng.integers(1, 7)), int(rng.integers(30, 201))
+            tract = np.resize(synth.ALPHA[rng.integers(0, 4, period)], ln)
+            hit = rng.random(ln) < 0.03
+            tract[hit] = synth.ALPHA[rng.integers(0, 4, int(hit.sum()))]
+            g[pos:pos + ln] = tract
+            pos += ln + int(rng.integers(1000, 3000))
+        gen.append(('NZ_REP%05d.1' % i, g))
+    return gen, synth.make_reads(seed + 1, gen, n_reads, mean_len=mean_len)
+
+
 def hard_reads(gen, seed=9):
     """Reads that force the rarely taken branches: z-drop inside a gap fill (second exact pass + split hit), chimeras,
     inversions, a long deletion (long-join, very wide DP window), a long read, N runs."""

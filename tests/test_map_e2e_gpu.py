@@ -143,6 +143,29 @@ def test_hard_reads_match_oracle(world):
     assert text.count('\n') >= len(reads)
 
 
+def test_repeat_rich_world_matches_oracle(libmpn, oracle_built):
+    """PAF with CIGAR on a world whose genomes carry tandem-repeat tracts of period 1..6 every couple of kb: the indels of the
+    reads slide there, gaps eat whole match runs and meet.  Parity only; test_aln_finish_gpu.py asserts that the mechanisms of
+    the finishing kernel are reached, on alignments made for them."""
+    from map_cases import repeat_world
+    from megapath_nano_amd import mapper
+    from oracle import mm2_bindings as mb
+    gen, reads = repeat_world()
+    gidx, oidx = mapper.Index(gen), mb.Index(gen)
+    try:
+        names = [r['name'] for r in reads]
+        gopt, oopt = mapper.default_opt(best_n=5, pri_ratio=0.8), mb.default_opt(best_n=5, pri_ratio=0.8)
+        got = split_by_read(mapper.map_batch(gidx, gopt, names, [r['seq'] for r in reads]), names)
+        want = oracle_paf(oidx, oopt, reads)
+        for r, g, w in zip(reads, got, want):
+            assert g == w, (r['name'], len(r['seq']))
+        lines = [l.split('\t') for l in ''.join(want).splitlines()]
+        assert len(lines) >= len(reads) * 3 // 4 and {f[4] for f in lines} == {'+', '-'} and all(any(x.startswith('cg:Z:') for x in f) for f in lines)
+    finally:
+        gidx.close()
+        oidx.close()
+
+
 def test_index_save_load_round_trip(world, tmp_path):
     """A saved index loaded back (SURVEY 8f1 / minimap2 -d) has the same keys, positions and targets, maps the hard reads
     (N runs included) to the same PAF, and the `--aligner` drop-in accepts it as the target."""
