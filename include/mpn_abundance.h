@@ -13,6 +13,12 @@
  *                       per assembly (the reference's bin/megapath_nano.py:417-482: align_list_to_depth_bed, behind the spike and
  *                       variable-region noise BEDs).  bedtools is restated here, not linked or run: see DESIGN.md section 2.
  *
+ *   mpn_bed_union       `bedtools sort | bedtools merge` with the merged intervals themselves as output: how the reference combines
+ *                       noise BEDs (bin/megapath_nano.py:362-382: merge_bed_with_assembly_id)
+ *   mpn_cover_by_bed    the counting half of `bedtools annotate`: the positions of every query interval that a BED covers, behind
+ *                       the reference's select_alignment_by_bed (bin/megapath_nano.py:666-717), which applies a noise BED to
+ *                       alignments.  Restated, not run, like the depth profile.
+ *
  * All run on the GPU (csrc/interval_kernels.hip: a stable LSD radix sort of 128-bit keys, three-phase sweeps over the sorted list);
  * all pointers are HOST pointers, results are exact integers.  Return 0, or a negative error (mpn_last_error()).
  */
@@ -55,6 +61,29 @@ int mpn_depth_by_key(int64_t n, const int32_t *key, const int64_t *start, const 
                      int32_t *row_key, int64_t *row_start, int64_t *row_end, int32_t *row_depth, int64_t *n_rows,
                      int32_t *bed_key, int64_t *bed_start, int64_t *bed_end, int64_t *n_bed,
                      int64_t *span);
+
+/* Records that one block of the union sweep scans (a multiple of its 256 lanes); the running maximum of `end`, the count of
+ * merged intervals and their summed length are carried between such tiles. */
+#define MPN_BED_TILE 2048
+
+/* The union of n intervals [start, end), 0 <= start, end < 2^32, per key[i] in [0, n_keys): intervals of one key that overlap
+ * or touch merge (bedtools merge, distance 0); an interval with start >= end contributes nothing.  The merged intervals come
+ * out ordered by (key, start) in out_key / out_start / out_end[0..*n_out), cap >= n entries each; span[g] (g < n_groups, zeroed
+ * by the call, may be NULL) = their summed length over the keys with key_group[k] == g.  n < 2^31.
+ * A record or key_group outside the domain or a cap below n returns -2 before anything is written. */
+int mpn_bed_union(int64_t n, const int32_t *key, const int64_t *start, const int64_t *end,
+                  int32_t n_keys, const int32_t *key_group, int32_t n_groups,
+                  int64_t cap, int32_t *out_key, int64_t *out_start, int64_t *out_end, int64_t *n_out, int64_t *span);
+
+/* covered[i], i < n_q = the number of positions of the query interval [q_start[i], q_end[i]) on q_key[i] that at least one of
+ * the n_bed BED intervals of the same key covers (both keyed into [0, n_keys)).  A BED interval counts through its clip to the
+ * query, max of the starts to min of the ends, and only where that is not empty: one that merely touches the query, or is
+ * itself empty (start >= end), adds nothing.  0 <= q_start <= q_end < 2^32; a query with q_start == q_end gets 0; BED records as
+ * in mpn_bed_union.  The BED is merged on the device and stays there; only covered[] comes back.
+ * A record outside the domain (a query with q_start > q_end included) returns -2 before anything is written. */
+int mpn_cover_by_bed(int64_t n_bed, const int32_t *bed_key, const int64_t *bed_start, const int64_t *bed_end,
+                     int64_t n_q, const int32_t *q_key, const int64_t *q_start, const int64_t *q_end,
+                     int32_t n_keys, int64_t *covered);
 
 #ifdef __cplusplus
 }

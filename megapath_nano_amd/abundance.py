@@ -22,6 +22,14 @@ length per assembly) is the source of every depth-based noise BED: `step_spike_f
 (:2359), `step_variable_region` (:1729-1734).  Here it is mpn_depth_by_key (events, the same radix sort, two scans) behind
 `depth_profile`, `align_list_to_depth_bed` and `spike_noise`; `host_depth_by_key` is its numpy statement.  bedtools is restated,
 not run: DESIGN.md section 2 says what that restatement rests on.
+
+Applying a noise BED: `select_alignment_by_bed` (the reference's :666-717: `bedtools annotate` of one row per alignment against
+the BED, then a threshold on the covered fraction) behind `step_noise_removal` (:2259-2272) and `step_closing_spike_filter`
+(:2353-2408), and `merge_bed_with_assembly_id` (:362-382: `bedtools sort | merge` of several BEDs on assembly_id + ',' +
+sequence_id).  Here they are mpn_cover_by_bed (the BED merged on the device, then two binary searches per alignment) and
+mpn_bed_union behind the functions of the same names, `noise_removal` and `closing_spike_filter`; `host_bed_union` and
+`host_cover_by_bed` are the numpy statements.  The covered base pairs are exact integers from either; the fraction they are
+compared through is bedtools' float32 quotient printed with six decimals, computed on the host.
 """
 import ctypes as ct
 import math
@@ -45,6 +53,10 @@ def _lib():
         lib.mpn_cover_by_group.restype = ct.c_int
         lib.mpn_depth_by_key.argtypes = [ct.c_int64, P, P, P, ct.c_int32, P, P, ct.c_int32, P, P, ct.c_int64, P, P, P, P, P, P, P, P, P, P]
         lib.mpn_depth_by_key.restype = ct.c_int
+        lib.mpn_bed_union.argtypes = [ct.c_int64, P, P, P, ct.c_int32, P, ct.c_int32, ct.c_int64, P, P, P, P, P]
+        lib.mpn_bed_union.restype = ct.c_int
+        lib.mpn_cover_by_bed.argtypes = [ct.c_int64, P, P, P, ct.c_int64, P, P, P, ct.c_int32, P]
+        lib.mpn_cover_by_bed.restype = ct.c_int
         _bound = True
     return lib
 
@@ -379,3 +391,206 @@ def spike_noise(align_list, assembly_length, expected_max_depth_stdev=6, assembl
     with np.errstate(divide='ignore', invalid='ignore'):
         noise_stat['spike_span_percent'] = noise_stat['spike_span_bp'].to_numpy(dtype=np.float64) / noise_stat['assembly_length'].to_numpy(dtype=np.float64)
     return noise_bed, noise_stat[['assembly_id', 'spike_span_bp', 'spike_span_percent']]
+
+
+# ---- union of BEDs, alignments selected by their overlap with a BED -----------------------------------------------------------
+BED_TILE = 2048   # MPN_BED_TILE of include/mpn_abundance.h: the records one block of the device's union sweep scans (the tests
+#                   put their sizes around its multiples; tests/test_bed_select.py checks that the two numbers agree)
+
+
+def _interval_args(key, start, end):
+    return np.ascontiguousarray(key, dtype=np.int32), np.ascontiguousarray(start, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+
+
+def device_bed_union(key, start, end, n_keys, key_group=None, n_groups=1):
+    """mpn_bed_union.  Interval i = [start[i], end[i]) on key[i] in [0, n_keys); key_group (default: all 0) maps a key to one of
+    n_groups.  -> (out_key int32, out_start int64, out_end int64), span int64[n_groups]: the merged intervals ordered by (key,
+    start) -- overlapping and touching ones merged, empty ones (start >= end) dropped -- and their summed length per group."""
+    key, start, end = _interval_args(key, start, end)
+    key_group = np.zeros(int(n_keys), dtype=np.int32) if key_group is None else np.ascontiguousarray(key_group, dtype=np.int32)
+    if len(key_group) != int(n_keys):
+        raise ValueError('key_group has one entry per key')
+    n, cap = len(key), max(len(key), 1)
+    ok, os_, oe = np.empty(cap, np.int32), np.empty(cap, np.int64), np.empty(cap, np.int64)
+    n_out = ct.c_int64(0)
+    span = np.zeros(max(int(n_groups), 1), dtype=np.int64)
+    _ffi.check(_lib().mpn_bed_union(n, key.ctypes.data, start.ctypes.data, end.ctypes.data, int(n_keys), key_group.ctypes.data, int(n_groups), cap,
+                                    ok.ctypes.data, os_.ctypes.data, oe.ctypes.data, ct.byref(n_out), span.ctypes.data), 'mpn_bed_union')
+    m = n_out.value
+    return (ok[:m], os_[:m], oe[:m]), span[:n_groups]
+
+
+def host_bed_union(key, start, end, n_keys, key_group=None, n_groups=1):
+    """numpy statement of mpn_bed_union (same arguments, same result): sorted by (key, start), the running maximum of
+    (key + 1) << 32 | end is the running maximum of `end` on the current key."""
+    key, start, end = _interval_args(key, start, end)
+    key_group = np.zeros(int(n_keys), dtype=np.int32) if key_group is None else np.ascontiguousarray(key_group, dtype=np.int32)
+    on = start < end
+    key, start, end = key[on], start[on], end[on]
+    order = np.lexsort((start, key))
+    key, start, end = key[order], start[order], end[order]
+    k1 = key.astype(np.uint64) + np.uint64(1)
+    incl = np.maximum.accumulate(k1 << np.uint64(32) | end.astype(np.uint64)) if len(key) else np.zeros(0, dtype=np.uint64)
+    before = np.concatenate([np.zeros(1, dtype=np.uint64), incl[:-1]]) if len(key) else incl
+    head = (before >> np.uint64(32) != k1) | (start.astype(np.uint64) > (before & np.uint64(0xffffffff)))   # touching merges
+    tail = np.ones(len(key), dtype=bool)
+    tail[:-1] = head[1:]
+    ok, os_, oe = key[head], start[head], (incl[tail] & np.uint64(0xffffffff)).astype(np.int64)
+    span = np.bincount(key_group[ok], weights=(oe - os_).astype(np.float64), minlength=int(n_groups)).astype(np.int64)[:n_groups]
+    return (ok, os_, oe), span
+
+
+def device_cover_by_bed(bed_key, bed_start, bed_end, q_key, q_start, q_end, n_keys):
+    """mpn_cover_by_bed -> int64[n_q]: the positions of query i = [q_start[i], q_end[i]) on q_key[i] that a BED interval of the
+    same key covers.  q_start <= q_end; BED intervals with start >= end count for nothing."""
+    bed_key, bed_start, bed_end = _interval_args(bed_key, bed_start, bed_end)
+    q_key, q_start, q_end = _interval_args(q_key, q_start, q_end)
+    covered = np.zeros(max(len(q_key), 1), dtype=np.int64)
+    _ffi.check(_lib().mpn_cover_by_bed(len(bed_key), bed_key.ctypes.data, bed_start.ctypes.data, bed_end.ctypes.data, len(q_key), q_key.ctypes.data,
+                                       q_start.ctypes.data, q_end.ctypes.data, int(n_keys), covered.ctypes.data), 'mpn_cover_by_bed')
+    return covered[:len(q_key)]
+
+
+def host_cover_by_bed(bed_key, bed_start, bed_end, q_key, q_start, q_end, n_keys):
+    """numpy statement of mpn_cover_by_bed: the union, the summed length before every merged interval, and per query the first
+    merged interval that ends after q_start and the last that starts before q_end, both found on (key, coordinate)."""
+    q_key, q_start, q_end = _interval_args(q_key, q_start, q_end)
+    if len(q_key) and (q_start > q_end).any():
+        raise ValueError(f'query {int(np.flatnonzero(q_start > q_end)[0])}: start > end')
+    (mk, ms, me), _ = host_bed_union(bed_key, bed_start, bed_end, n_keys)
+    if len(mk) == 0 or len(q_key) == 0:
+        return np.zeros(len(q_key), dtype=np.int64)
+    before = np.concatenate([[0], np.cumsum(me - ms)])              # before[r] = summed length of the merged intervals < r
+    kk, qk = mk.astype(np.int64) << 32, q_key.astype(np.int64) << 32
+    a = np.searchsorted(kk | me, qk | q_start, side='right')         # the intervals of a key are disjoint: ends ascend like starts
+    b = np.searchsorted(kk | ms, qk | q_end, side='left') - 1
+    some = a <= b                                                   # then a..b all lie on the query's key
+    a, b = np.where(some, a, 0), np.where(some, b, 0)
+    inner = before[b + 1] - before[a] - np.maximum(q_start - ms[a], 0) - np.maximum(me[b] - q_end, 0)
+    return np.where(some, inner, 0).astype(np.int64)
+
+
+_BED_COLUMNS = ['sequence_id', 'start', 'end', 'assembly_id']
+
+
+def _empty_bed():
+    return pandas.DataFrame({'sequence_id': np.zeros(0, dtype=object), 'start': np.zeros(0, dtype=np.int64), 'end': np.zeros(0, dtype=np.int64),
+                             'assembly_id': np.zeros(0, dtype=object)})
+
+
+def _str_objects(col):
+    """a column of ids as an object array of str (what pandas.factorize hashes fastest); anything but str is converted"""
+    arr = col.to_numpy(dtype=object)
+    return arr if pandas.api.types.infer_dtype(arr, skipna=False) == 'string' else arr.astype(str).astype(object)
+
+
+def _bed_ids(bed):
+    """(assembly_id, sequence_id) of a BED as object arrays of str; a BED without assembly_id has '' (megapath_nano.py:370-371)."""
+    seq = _str_objects(bed['sequence_id'])
+    asm = _str_objects(bed['assembly_id']) if 'assembly_id' in bed.columns else np.full(len(seq), '', dtype=object)
+    return asm, seq
+
+
+def _pair_codes(asm, seq):
+    """int32 code per row of its (assembly, sequence) pair, and the number of pairs; the codes carry no order."""
+    ac, a_names = pandas.factorize(asm)
+    sc, s_names = pandas.factorize(seq)
+    code, pairs = pandas.factorize(ac.astype(np.int64) * max(len(s_names), 1) + sc)
+    return code.astype(np.int32), len(pairs)
+
+
+def merge_bed_with_assembly_id(bed_list, device=None):
+    """The reference's merge_bed_with_assembly_id: the union of several BEDs per (assembly_id, sequence_id).  A BED is a
+    DataFrame(sequence_id, start, end[, assembly_id]); without the last column every row has assembly_id ''; None and empty BEDs
+    are skipped.  -> DataFrame(sequence_id, start, end, assembly_id) ordered by the bytes of assembly_id + ',' + sequence_id,
+    then start: intervals that overlap or touch merged, empty ones dropped.  device: as in covered_bp_by_assembly."""
+    beds = [b for b in bed_list if b is not None and b.shape[0] > 0]
+    if not beds:
+        return _empty_bed()
+    if device is None:
+        device = True
+    ids = [_bed_ids(b) for b in beds]
+    asm, seq = np.concatenate([i[0] for i in ids]), np.concatenate([i[1] for i in ids])
+    code, n_pairs = _pair_codes(asm, seq)
+    first = np.zeros(n_pairs, dtype=np.int64)
+    first[code[::-1]] = np.arange(len(code))[::-1]                   # a row of every pair
+    p_asm, p_seq = asm[first].astype(str), seq[first].astype(str)
+    order = np.argsort(np.char.add(np.char.add(p_asm, ','), p_seq), kind='stable')
+    rank = np.empty(n_pairs, dtype=np.int32)
+    rank[order] = np.arange(n_pairs, dtype=np.int32)
+    start = np.concatenate([b['start'].to_numpy(dtype=np.int64) for b in beds])
+    end = np.concatenate([b['end'].to_numpy(dtype=np.int64) for b in beds])
+    (mk, ms, me), _ = (device_bed_union if device else host_bed_union)(rank[code], start, end, n_pairs)
+    return pandas.DataFrame({'sequence_id': p_seq[order][mk], 'start': ms, 'end': me, 'assembly_id': p_asm[order][mk]}, columns=_BED_COLUMNS)
+
+
+def overlap_fraction(covered, length):
+    """The fraction that `bedtools annotate` prints for `covered` of `length` positions, as the float64 pandas reads back: the
+    float32 quotient, written with '%f' (six decimals) and parsed.  float32 * 10^6 is exact in float64, so rounding there to an
+    integer (ties to even, like printf) and dividing by 10^6 gives the same double as the text.  length 0 -> NaN."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        f = np.asarray(covered).astype(np.float32) / np.asarray(length).astype(np.float32)
+    return np.round(f.astype(np.float64), 6)
+
+
+def select_alignment_by_bed(*, align_list, bed, max_overlap=100, can_equal_to_max=True, min_overlap=0, can_equal_to_min=True, temp_dir_name=None,
+                            device=None):
+    """The reference's select_alignment_by_bed with its keyword arguments (temp_dir_name is accepted and ignored): the rows of
+    align_list whose target interval [sequence_from, sequence_to) is covered by `bed` to a fraction x with
+    min_overlap / 100 <[=] x <[=] max_overlap / 100.  A BED row and an alignment match iff assembly_id and sequence_id are both
+    equal (a BED without assembly_id has ''); strand plays no part.  x: overlap_fraction of the exact covered base pairs; an
+    alignment of length 0 has x = NaN and is never selected; sequence_to < sequence_from raises ValueError.  bed None or empty:
+    align_list itself iff the range admits 0, otherwise none of it.
+    -> the selected rows in input order, columns and index as in align_list.  device: as in covered_bp_by_assembly."""
+    if bed is None or bed.shape[0] == 0:
+        if min_overlap == 0 and can_equal_to_min and (max_overlap != 0 or can_equal_to_max):
+            return align_list
+        return align_list.iloc[0:0]
+    if align_list.shape[0] == 0:
+        return align_list
+    if device is None:
+        device = True
+    q_start, q_end = align_list['sequence_from'].to_numpy(dtype=np.int64), align_list['sequence_to'].to_numpy(dtype=np.int64)
+    if (q_end < q_start).any():
+        raise ValueError(f'row {int(np.flatnonzero(q_end < q_start)[0])}: sequence_to < sequence_from')
+    b_asm, b_seq = _bed_ids(bed)
+    n_bed = len(b_asm)
+    code, n_pairs = _pair_codes(np.concatenate([b_asm, _str_objects(align_list['assembly_id'])]),
+                                np.concatenate([b_seq, _str_objects(align_list['sequence_id'])]))
+    covered = (device_cover_by_bed if device else host_cover_by_bed)(code[:n_bed], bed['start'].to_numpy(dtype=np.int64), bed['end'].to_numpy(dtype=np.int64),
+                                                                     code[n_bed:], q_start, q_end, n_pairs)
+    x = overlap_fraction(covered, q_end - q_start)
+    hi, lo = max_overlap / 100, min_overlap / 100
+    with np.errstate(invalid='ignore'):
+        keep = ((x <= hi) if can_equal_to_max else (x < hi)) & ((x >= lo) if can_equal_to_min else (x > lo))
+    return align_list[keep]
+
+
+def noise_removal(*, align_list, noise_bed, non_zero_assembly_ids, max_align_noise_overlap, device=None):
+    """step_noise_removal (megapath_nano.py:2257-2278): the alignments that noise_bed covers to at most max_align_noise_overlap
+    percent, of the assemblies in non_zero_assembly_ids (ids, or a DataFrame with an assembly_id column; an id twice raises
+    ValueError, as the reference's m:1 merge does), in input order.  -> align_list, num_align_before, num_align_after"""
+    ids = non_zero_assembly_ids['assembly_id'] if isinstance(non_zero_assembly_ids, pandas.DataFrame) else non_zero_assembly_ids
+    ids = [str(i) for i in ids]
+    if len(set(ids)) != len(ids):
+        raise ValueError('non_zero_assembly_ids: an assembly_id occurs twice')
+    out = select_alignment_by_bed(align_list=align_list, bed=noise_bed, max_overlap=max_align_noise_overlap, device=device)
+    out = out[out['assembly_id'].astype(str).isin(ids).to_numpy()]
+    return out, align_list.shape[0], out.shape[0]
+
+
+def closing_spike_filter(*, align_list, best_align_list, best_align_list_with_short_alignment, noise_bed, assembly_length, max_align_noise_overlap,
+                         expected_max_depth_stdev=9, assembly_tax=None, device=None):
+    """step_closing_spike_filter (megapath_nano.py:2353-2408).  The two best-alignment tables are inputs (the reference draws
+    them with align_list_to_best_align_list): spikes are sought in best_align_list_with_short_alignment, their BED joins
+    noise_bed, and every read whose row of best_align_list is covered by the joint BED to MORE than max_align_noise_overlap
+    percent leaves align_list with all its alignments.
+    -> align_list, noise_bed (the joint one), closing_spike_noise_bed, noise_stat: DataFrame(assembly_id, closing_spike_span_bp,
+    closing_spike_span_percent), num_read_before (rows of best_align_list), num_read_after (distinct reads left)"""
+    spike_bed, noise_stat = spike_noise(best_align_list_with_short_alignment, assembly_length, expected_max_depth_stdev, assembly_tax, device=device)
+    noise_stat = noise_stat.rename(columns={'spike_span_bp': 'closing_spike_span_bp', 'spike_span_percent': 'closing_spike_span_percent'})
+    noise_bed_out = merge_bed_with_assembly_id([noise_bed, spike_bed], device=device)
+    gone = select_alignment_by_bed(align_list=best_align_list, bed=noise_bed_out, min_overlap=max_align_noise_overlap, can_equal_to_min=False,
+                                   device=device)['read_id']
+    out = align_list[~align_list['read_id'].isin(gone).to_numpy()]
+    return out, noise_bed_out, spike_bed, noise_stat, best_align_list.shape[0], int(out['read_id'].nunique())

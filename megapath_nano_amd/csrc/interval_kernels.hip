@@ -373,6 +373,266 @@ __global__ __launch_bounds__(DP_THREADS) void dp_row_fill_kernel(const int32_t *
     }
 }
 
+// ---- union of a BED with the merged intervals as output, and the covered length of query intervals ---------------------------
+// (`bedtools sort | merge`, and the counting half of `bedtools annotate`).  Records {hi = key + 1, lo = start << 32 | end} of the
+// non-empty intervals, sorted by (key, start).  With v = (key + 1) << 32 | end, the plain running maximum of v is the running
+// maximum of `end` on the current key, because the key field dominates and never decreases; P = that maximum over the records
+// before record i (0: none), Q = max(P, v_i).  Record i heads a merged interval iff P is of another key or start_i > end(P)
+// (touching merges); it is the tail of one iff record i + 1 is a head or there is none, and then end(Q) is the interval's end.
+// Heads and tails alternate, so the k-th head and the k-th tail fill the k-th output row from their own lanes.  The same scan
+// carries c = (tail ? end : 0) - (head ? start : 0): its sum over the records before a head is the summed length of the merged
+// intervals before this one -- the exclusive prefix that the search below needs -- and its sum per group is span[g].
+// Phases, a lane per record over tiles of MPN_BED_TILE: tile maxima; one block turns them into the maximum that enters each
+// tile; heads and c per tile; one block turns those into tile bases; the rescan that writes.
+constexpr int BU_THREADS = 256, BU_ITEMS = MPN_BED_TILE / BU_THREADS;
+static_assert(MPN_BED_TILE % BU_THREADS == 0, "a tile is whole blocks of lanes");
+
+__device__ __forceinline__ uint64_t wave_scan_max64(uint64_t v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)v, d);
+        if (lane >= d && o > v) v = o;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_scan_add64(uint64_t v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)v, d);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint64_t bu_value(const Rec3 &r) { return r.hi << 32 | (uint32_t)r.lo; }
+
+__global__ __launch_bounds__(BU_THREADS) void bu_tile_max_kernel(const Rec3 *__restrict__ rec, int64_t n, uint64_t *__restrict__ tmax) {
+    __shared__ uint64_t ws[4];
+    const int64_t base = (int64_t)blockIdx.x * MPN_BED_TILE;
+    uint64_t v = 0;
+#pragma unroll
+    for (int k = 0; k < BU_ITEMS; ++k) {
+        const int64_t i = base + k * BU_THREADS + threadIdx.x;
+        if (i < n) { const uint64_t x = bu_value(rec[i]); v = x > v ? x : v; }
+    }
+    v = wave_scan_max64(v);
+    if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t m = 0;
+        for (int w = 0; w < BU_THREADS / 64; ++w) m = ws[w] > m ? ws[w] : m;
+        tmax[blockIdx.x] = m;
+    }
+}
+
+// one block, in place: exclusive scans over the nb tiles.  is_max: the running maximum (identity 0); otherwise nq rows of sums,
+// total[q] = the sum of row q
+__global__ __launch_bounds__(1024) void bu_prefix_kernel(uint64_t *__restrict__ part, int nb, int nq, int is_max, uint64_t *__restrict__ total) {
+    __shared__ uint64_t sh[1024];
+    const int t = threadIdx.x, per = (nb + 1023) / 1024, lo = min(nb, t * per), hi = min(nb, lo + per);
+    for (int q = 0; q < nq; ++q) {
+        uint64_t *row = part + (size_t)q * nb;
+        uint64_t s = 0;
+        for (int k = lo; k < hi; ++k) s = is_max ? (row[k] > s ? row[k] : s) : s + row[k];
+        sh[t] = s;
+        __syncthreads();
+        if (t == 0) {
+            uint64_t acc = 0;
+            for (int k = 0; k < 1024; ++k) { const uint64_t v = sh[k]; sh[k] = acc; acc = is_max ? (v > acc ? v : acc) : acc + v; }
+            if (total) total[q] = acc;
+        }
+        __syncthreads();
+        uint64_t o = sh[t];
+        for (int k = lo; k < hi; ++k) { const uint64_t v = row[k]; row[k] = o; o = is_max ? (v > o ? v : o) : o + v; }
+        __syncthreads();
+    }
+}
+
+struct BuItem { bool head, tail; uint32_t key, start, end; };   // end: the end of the merged interval (meaningful at a tail)
+
+// One step of the running maximum over the block's 256 records i = first + lane; run: the maximum over everything before
+// `first`, moved on to include these records.  Every lane of the block calls it (one barrier); ws alternates between steps.
+__device__ __forceinline__ BuItem bu_step(const Rec3 *__restrict__ rec, int64_t i, int64_t n, uint64_t &run, uint64_t *ws) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool act = i < n;
+    Rec3 r{0, 0, 0};
+    if (act) r = rec[i];
+    const uint64_t v = act ? bu_value(r) : 0;
+    const uint64_t inc = wave_scan_max64(v);
+    if (lane == 63) ws[wv] = inc;
+    uint64_t p = (uint64_t)__shfl_up((unsigned long long)inc, 1);
+    if (lane == 0) p = 0;
+    __syncthreads();
+    uint64_t before = run, all = run;
+#pragma unroll
+    for (int w = 0; w < BU_THREADS / 64; ++w) {
+        const uint64_t t = ws[w];
+        if (w < wv && t > before) before = t;
+        if (t > all) all = t;
+    }
+    run = all;
+    p = before > p ? before : p;
+    const uint64_t q = v > p ? v : p;
+    BuItem it{false, false, (uint32_t)r.hi - 1, (uint32_t)(r.lo >> 32), (uint32_t)q};
+    if (act) {
+        it.head = (p >> 32) != r.hi || it.start > (uint32_t)p;
+        it.tail = true;
+        if (i + 1 < n) { const Rec3 nx = rec[i + 1]; it.tail = nx.hi != r.hi || (uint32_t)(nx.lo >> 32) > it.end; }
+    }
+    return it;
+}
+
+__device__ __forceinline__ uint64_t bu_contribution(const BuItem &it) { return (it.tail ? (uint64_t)it.end : 0) - (it.head ? (uint64_t)it.start : 0); }
+
+// part[0 * nb + tile] = heads in the tile, part[1 * nb + tile] = sum of c over the tile (wrapping; the prefixes are exact)
+__global__ __launch_bounds__(BU_THREADS) void bu_count_kernel(const Rec3 *__restrict__ rec, int64_t n, const uint64_t *__restrict__ tmax,
+                                                              uint64_t *__restrict__ part, int nb) {
+    __shared__ uint64_t wsm[2][4], wsa[2][4];
+    const int64_t base = (int64_t)blockIdx.x * MPN_BED_TILE;
+    uint64_t run = tmax[blockIdx.x], heads = 0, c = 0;
+#pragma unroll
+    for (int k = 0; k < BU_ITEMS; ++k) {
+        if (base + k * BU_THREADS >= n) break;   // (the whole block leaves together)
+        const BuItem it = bu_step(rec, base + k * BU_THREADS + threadIdx.x, n, run, wsm[k & 1]);
+        heads += it.head; c += bu_contribution(it);
+    }
+    heads = wave_scan_add64(heads); c = wave_scan_add64(c);
+    if ((threadIdx.x & 63) == 63) { wsa[0][threadIdx.x >> 6] = heads; wsa[1][threadIdx.x >> 6] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = wsa[0][0] + wsa[0][1] + wsa[0][2] + wsa[0][3];
+        part[(size_t)nb + blockIdx.x] = wsa[1][0] + wsa[1][1] + wsa[1][2] + wsa[1][3];
+    }
+}
+
+// m_key / m_start / m_end / m_before: the merged intervals and the summed length of those before each; span may be null
+__global__ __launch_bounds__(BU_THREADS) void bu_fill_kernel(const Rec3 *__restrict__ rec, int64_t n, const uint64_t *__restrict__ tmax,
+                                                             const uint64_t *__restrict__ part, int nb, const int32_t *__restrict__ key_group,
+                                                             int32_t *__restrict__ m_key, uint32_t *__restrict__ m_start, uint32_t *__restrict__ m_end,
+                                                             uint64_t *__restrict__ m_before, unsigned long long *__restrict__ span) {
+    __shared__ uint64_t wsm[2][4], wsa[2][2][4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t base = (int64_t)blockIdx.x * MPN_BED_TILE;
+    uint64_t run = tmax[blockIdx.x], run_heads = part[blockIdx.x], run_c = part[(size_t)nb + blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < BU_ITEMS; ++k) {
+        if (base + k * BU_THREADS >= n) break;   // (the whole block leaves together)
+        const BuItem it = bu_step(rec, base + k * BU_THREADS + threadIdx.x, n, run, wsm[k & 1]);
+        const uint64_t c = bu_contribution(it);
+        uint64_t heads = wave_scan_add64(it.head), sum = wave_scan_add64(c);
+        if (lane == 63) { wsa[k & 1][0][wv] = heads; wsa[k & 1][1][wv] = sum; }
+        __syncthreads();
+        uint64_t th = 0, tc = 0;
+#pragma unroll
+        for (int w = 0; w < BU_THREADS / 64; ++w) {
+            const uint64_t a = wsa[k & 1][0][w], b = wsa[k & 1][1][w];
+            if (w < wv) { heads += a; sum += b; }
+            th += a; tc += b;
+        }
+        heads += run_heads; sum += run_c;          // inclusive, over the whole list
+        if (it.head) { const uint64_t o = heads - 1; m_key[o] = (int32_t)it.key; m_start[o] = it.start; m_before[o] = sum - c; }
+        if (it.tail) m_end[heads - 1] = it.end;
+        // integer adds commute and wrap, so ends minus starts is exact in any order
+        if (span && c) atomicAdd(&span[key_group[it.key]], (unsigned long long)c);
+        run_heads += th; run_c += tc;
+    }
+}
+
+// key_off[k], k in [0, n_keys]: the first merged interval whose key is >= k (the merged list is ordered by key)
+__global__ __launch_bounds__(256) void bu_key_offsets_kernel(const int32_t *__restrict__ m_key, const uint64_t *__restrict__ n_merged, int32_t n_keys,
+                                                             uint32_t *__restrict__ key_off) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > n_keys) return;
+    uint32_t lo = 0, hi = (uint32_t)n_merged[0];
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (m_key[mid] < k) lo = mid + 1; else hi = mid; }
+    key_off[k] = lo;
+}
+
+// A lane per query, two binary searches inside the key's segment of the merged list: a = the first interval that ends after
+// q_start, b = the last that starts before q_end.  The intervals of a key are disjoint and do not touch, so ends and starts are
+// both ascending and a..b are exactly the intervals that meet the query; only a and b can stick out of it.
+// Each step is a dependent read that misses the caches for a large BED: the kernel holds a handful of registers and no LDS, so
+// a SIMD keeps its 8 waves and the latency is hidden by the other waves' searches.
+__global__ __launch_bounds__(256) void bu_cover_kernel(const int32_t *__restrict__ q_key, const int64_t *__restrict__ q_start, const int64_t *__restrict__ q_end, int64_t n_q,
+                                                       const uint32_t *__restrict__ key_off, const uint32_t *__restrict__ m_start, const uint32_t *__restrict__ m_end,
+                                                       const uint64_t *__restrict__ m_before, int64_t *__restrict__ covered) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_q; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t k = q_key[i];
+        const uint32_t qs = (uint32_t)q_start[i], qe = (uint32_t)q_end[i];
+        const uint32_t seg_lo = key_off[k], seg_hi = key_off[k + 1];
+        uint32_t lo = seg_lo, hi = seg_hi;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (m_end[mid] <= qs) lo = mid + 1; else hi = mid; }
+        const uint32_t a = lo;
+        hi = seg_hi;                                   // the first interval at or after a that starts at or after q_end
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (m_start[mid] < qe) lo = mid + 1; else hi = mid; }
+        int64_t c = 0;
+        if (lo > a) {
+            const uint32_t b = lo - 1, sa = m_start[a], sb = m_start[b], eb = m_end[b];
+            c = (int64_t)(m_before[b] + (eb - sb) - m_before[a]) - (qs > sa ? qs - sa : 0) - (eb > qe ? eb - qe : 0);
+        }
+        covered[i] = c;
+    }
+}
+
+// The merged list of a BED on the device.
+struct BedUnion {
+    DevBuf<Rec3> a, b;
+    DevBuf<uint64_t> tmax, part, total;   // total[0] = the number of merged intervals, total[1] = their summed length
+    DevBuf<int32_t> m_key;
+    DevBuf<uint32_t> m_start, m_end;
+    DevBuf<uint64_t> m_before;
+};
+
+// hi / lo: the packed records of the n >= 1 non-empty intervals; skip: as in radix_sort_rec3.  Everything is queued on st.
+static int bed_union_on_device(BedUnion &u, const std::vector<uint64_t> &hi, const std::vector<uint64_t> &lo, uint32_t skip, const int32_t *d_key_group,
+                               unsigned long long *d_span, hipStream_t st) {
+    const int64_t n = (int64_t)hi.size();
+    DevBuf<uint64_t> d_hi, d_lo;
+    if (d_hi.upload(hi.data(), (size_t)n, st) || d_lo.upload(lo.data(), (size_t)n, st) || u.a.alloc((size_t)n) || u.b.alloc((size_t)n)) return -1;
+    const int g = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16));
+    hipLaunchKernelGGL(rs_fill_kernel, dim3(g), dim3(256), 0, st, (const uint64_t *)d_hi.p, (const uint64_t *)d_lo.p, n, u.a.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    Rec3 *rec = nullptr;
+    if (radix_sort_rec3(u.a.p, u.b.p, n, &rec, st, skip)) return -1;
+    const int nb = (int)((n + MPN_BED_TILE - 1) / MPN_BED_TILE);
+    if (u.tmax.alloc((size_t)nb) || u.part.alloc((size_t)2 * nb) || u.total.alloc(2) || u.m_key.alloc((size_t)n) || u.m_start.alloc((size_t)n) ||
+        u.m_end.alloc((size_t)n) || u.m_before.alloc((size_t)n)) return -1;
+    hipLaunchKernelGGL(bu_tile_max_kernel, dim3(nb), dim3(BU_THREADS), 0, st, (const Rec3 *)rec, n, u.tmax.p);
+    hipLaunchKernelGGL(bu_prefix_kernel, dim3(1), dim3(1024), 0, st, u.tmax.p, nb, 1, 1, (uint64_t *)nullptr);
+    hipLaunchKernelGGL(bu_count_kernel, dim3(nb), dim3(BU_THREADS), 0, st, (const Rec3 *)rec, n, (const uint64_t *)u.tmax.p, u.part.p, nb);
+    hipLaunchKernelGGL(bu_prefix_kernel, dim3(1), dim3(1024), 0, st, u.part.p, nb, 2, 0, u.total.p);
+    hipLaunchKernelGGL(bu_fill_kernel, dim3(nb), dim3(BU_THREADS), 0, st, (const Rec3 *)rec, n, (const uint64_t *)u.tmax.p, (const uint64_t *)u.part.p, nb, d_key_group,
+                       u.m_key.p, u.m_start.p, u.m_end.p, u.m_before.p, d_span);
+    MPN_HIP_CHECK(hipGetLastError());
+    // d_hi / d_lo are read by the fill kernel queued above: they must outlive it
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Checks the n intervals and packs the non-empty ones; returns 0, or -2 with the error set.  skip: the digits no record has --
+// the bytes of the start above the largest one, those of the key above n_keys, and all of `end`, which the sweep does not need
+// in order.
+static int bed_pack(const char *who, int64_t n, const int32_t *key, const int64_t *start, const int64_t *end, int32_t n_keys, std::vector<uint64_t> &hi,
+                    std::vector<uint64_t> &lo, uint32_t *skip) {
+    int64_t max_start = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (key[i] < 0 || key[i] >= n_keys || start[i] < 0 || start[i] > 0xffffffffLL || end[i] < 0 || end[i] > 0xffffffffLL) {
+            set_error("%s: record %lld outside the domain (key in [0, n_keys), 0 <= start, end < 2^32)", who, (long long)i);
+            return -2;
+        }
+        if (start[i] >= end[i]) continue;
+        hi.push_back((uint64_t)key[i] + 1);
+        lo.push_back((uint64_t)start[i] << 32 | (uint64_t)end[i]);
+        max_start = std::max(max_start, start[i]);
+    }
+    *skip = 0xf;
+    for (int p = 0; p < 4; ++p) if (((uint64_t)max_start >> (8 * p)) == 0) *skip |= 1u << (4 + p);
+    for (int p = 0; p < 8; ++p) if (((uint64_t)n_keys >> (8 * p)) == 0) *skip |= 1u << (8 + p);
+    return 0;
+}
+
 }  // namespace mpn
 
 using namespace mpn;
@@ -528,5 +788,79 @@ extern "C" int mpn_depth_by_key(int64_t n, const int32_t *key, const int64_t *st
     MPN_HIP_CHECK(hipStreamSynchronize(st));
     if (n_rows) *n_rows = nr;
     if (n_bed) *n_bed = nbed;
+    return 0;
+}
+
+extern "C" int mpn_bed_union(int64_t n, const int32_t *key, const int64_t *start, const int64_t *end, int32_t n_keys, const int32_t *key_group, int32_t n_groups,
+                             int64_t cap, int32_t *out_key, int64_t *out_start, int64_t *out_end, int64_t *n_out, int64_t *span) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || n_keys < 0 || n_groups < 0 || !out_key || !out_start || !out_end || !n_out || (n_keys > 0 && !key_group) ||
+        (n > 0 && (!key || !start || !end))) {
+        set_error("mpn_bed_union: bad arguments");
+        return -2;
+    }
+    if (cap < n) { set_error("mpn_bed_union: cap %lld is below n = %lld", (long long)cap, (long long)n); return -2; }
+    for (int32_t k = 0; k < n_keys; ++k)
+        if (key_group[k] < 0 || key_group[k] >= n_groups) { set_error("mpn_bed_union: key %d outside the domain (key_group in [0, n_groups))", (int)k); return -2; }
+    std::vector<uint64_t> hi, lo;
+    uint32_t skip = 0;
+    if (bed_pack("mpn_bed_union", n, key, start, end, n_keys, hi, lo, &skip)) return -2;
+    *n_out = 0;
+    if (span) for (int32_t g = 0; g < n_groups; ++g) span[g] = 0;
+    if (hi.empty()) return 0;
+
+    hipStream_t st = 0;
+    DevBuf<int32_t> d_group;
+    DevBuf<unsigned long long> d_span;
+    if (d_group.upload(key_group, (size_t)n_keys, st)) return -1;
+    if (span && (d_span.alloc((size_t)n_groups) || d_span.zero(st))) return -1;
+    BedUnion u;
+    if (bed_union_on_device(u, hi, lo, skip, d_group.p, span ? d_span.p : nullptr, st)) return -1;
+    uint64_t h_total[2];
+    if (u.total.download(h_total, 2, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    const int64_t m = (int64_t)h_total[0];
+    if (m < 1 || m > (int64_t)hi.size()) { set_error("mpn_bed_union: %lld merged intervals out of %zu", (long long)m, hi.size()); return -1; }
+    std::vector<uint32_t> h_start((size_t)m), h_end((size_t)m);
+    if (u.m_key.download(out_key, (size_t)m, st) || u.m_start.download(h_start.data(), (size_t)m, st) || u.m_end.download(h_end.data(), (size_t)m, st)) return -1;
+    if (span && d_span.download((unsigned long long *)span, (size_t)n_groups, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    for (int64_t r = 0; r < m; ++r) { out_start[r] = h_start[(size_t)r]; out_end[r] = h_end[(size_t)r]; }
+    *n_out = m;
+    return 0;
+}
+
+extern "C" int mpn_cover_by_bed(int64_t n_bed, const int32_t *bed_key, const int64_t *bed_start, const int64_t *bed_end,
+                                int64_t n_q, const int32_t *q_key, const int64_t *q_start, const int64_t *q_end, int32_t n_keys, int64_t *covered) {
+    if (n_bed < 0 || n_bed >= ((int64_t)1 << 31) || n_q < 0 || n_keys < 0 || (n_bed > 0 && (!bed_key || !bed_start || !bed_end)) ||
+        (n_q > 0 && (!q_key || !q_start || !q_end || !covered))) {
+        set_error("mpn_cover_by_bed: bad arguments");
+        return -2;
+    }
+    std::vector<uint64_t> hi, lo;
+    uint32_t skip = 0;
+    if (bed_pack("mpn_cover_by_bed", n_bed, bed_key, bed_start, bed_end, n_keys, hi, lo, &skip)) return -2;
+    for (int64_t i = 0; i < n_q; ++i)
+        if (q_key[i] < 0 || q_key[i] >= n_keys || q_start[i] < 0 || q_start[i] > q_end[i] || q_end[i] > 0xffffffffLL) {
+            set_error("mpn_cover_by_bed: query %lld outside the domain (key in [0, n_keys), 0 <= start <= end < 2^32)", (long long)i);
+            return -2;
+        }
+    if (n_q == 0) return 0;
+    if (hi.empty()) { for (int64_t i = 0; i < n_q; ++i) covered[i] = 0; return 0; }
+
+    hipStream_t st = 0;
+    BedUnion u;
+    if (bed_union_on_device(u, hi, lo, skip, nullptr, nullptr, st)) return -1;
+    DevBuf<int32_t> d_qk;
+    DevBuf<int64_t> d_qs, d_qe, d_cov;
+    DevBuf<uint32_t> key_off;
+    if (d_qk.upload(q_key, (size_t)n_q, st) || d_qs.upload(q_start, (size_t)n_q, st) || d_qe.upload(q_end, (size_t)n_q, st) || d_cov.alloc((size_t)n_q) ||
+        key_off.alloc((size_t)n_keys + 1)) return -1;
+    hipLaunchKernelGGL(bu_key_offsets_kernel, dim3((n_keys + 256) / 256), dim3(256), 0, st, (const int32_t *)u.m_key.p, (const uint64_t *)u.total.p, n_keys, key_off.p);
+    const int g = (int)std::max<int64_t>(1, std::min<int64_t>((n_q + 255) / 256, 256 * 32));
+    hipLaunchKernelGGL(bu_cover_kernel, dim3(g), dim3(256), 0, st, (const int32_t *)d_qk.p, (const int64_t *)d_qs.p, (const int64_t *)d_qe.p, n_q,
+                       (const uint32_t *)key_off.p, (const uint32_t *)u.m_start.p, (const uint32_t *)u.m_end.p, (const uint64_t *)u.m_before.p, d_cov.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    if (d_cov.download(covered, (size_t)n_q, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
     return 0;
 }
