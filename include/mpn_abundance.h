@@ -19,8 +19,14 @@
  *                       the reference's select_alignment_by_bed (bin/megapath_nano.py:666-717), which applies a noise BED to
  *                       alignments.  Restated, not run, like the depth profile.
  *
- * All run on the GPU (csrc/interval_kernels.hip: a stable LSD radix sort of 128-bit keys, three-phase sweeps over the sorted list);
- * all pointers are HOST pointers, results are exact integers.  Return 0, or a negative error (mpn_last_error()).
+ *   mpn_best_candidates      the rows that can be a read's best alignment: the best row per (read, assembly), of those the ones with
+ *   mpn_pick_weighted        their read's largest score; the abundance-weighted random draw among them (the reference's
+ *   mpn_second_best_by_read  bin/megapath_nano.py:244-310: align_list_to_best_align_list); the largest score of a read off its best
+ *                            row's assembly (:2553-2593: step_unique_alignment).  The random numbers are an input.
+ *
+ * All run on the GPU (csrc/interval_kernels.hip: a stable LSD radix sort of 128-bit keys, three-phase sweeps and segmented scans over
+ * the sorted list); all pointers are HOST pointers, results are exact integers -- and, in mpn_pick_weighted, float64 values that one
+ * IEEE division and one multiplication define.  Return 0, or a negative error (mpn_last_error()).
  */
 #ifndef MPN_ABUNDANCE_H
 #define MPN_ABUNDANCE_H
@@ -84,6 +90,42 @@ int mpn_bed_union(int64_t n, const int32_t *key, const int64_t *start, const int
 int mpn_cover_by_bed(int64_t n_bed, const int32_t *bed_key, const int64_t *bed_start, const int64_t *bed_end,
                      int64_t n_q, const int32_t *q_key, const int64_t *q_start, const int64_t *q_end,
                      int32_t n_keys, int64_t *covered);
+
+/* Rows that one block of the best-alignment scans covers (a multiple of its 256 lanes); the running arg-max, maximum, count and
+ * sum are carried between such tiles, so a read or a (read, assembly) group may run through any number of them. */
+#define MPN_BEST_TILE 2048
+
+/* The candidates of every read for its best alignment (the reference's bin/megapath_nano.py:250-273, the part of
+ * align_list_to_best_align_list before the abundance).  Row i is an alignment of read[i] in [0, n_reads) on assembly[i] in
+ * [0, n_assemblies) with score[i] (any int64 but the smallest one) and tiebreak[i] (a finite double; -0.0 counts as 0.0).
+ *   - per (read, assembly) the row with the largest (score, tiebreak) is kept, the LAST in input order among equal ones;
+ *   - a kept row is a candidate iff its score equals the largest score of its read: one candidate per assembly at most.
+ * cand_row / cand_read[0..*n_cand), room for n entries each: the candidates' row indices and read codes, ordered by (read,
+ * assembly).  read_count[r] / read_first[r], r < n_reads: the number of candidates of read r and the position of its first one in
+ * that list (a read without rows has count 0 and the position where its candidates would stand).  n < 2^31.
+ * A record outside the domain returns -2 before anything is written. */
+int mpn_best_candidates(int64_t n, const int32_t *read, const int32_t *assembly, const int64_t *score, const double *tiebreak,
+                        int32_t n_reads, int32_t n_assemblies,
+                        int64_t *cand_row, int32_t *cand_read, int64_t *n_cand, int64_t *read_count, int64_t *read_first);
+
+/* The abundance-weighted draw among the candidates of every read (bin/megapath_nano.py:283-310).  Candidate j < m belongs to
+ * read[j] in [0, n_reads), non-decreasing in j, has weight[j] >= 0 (the abundance of its assembly; the weights of one read sum to
+ * less than 2^53), its own tiebreak[j] and the random number draw[j], both finite.  With s = the summed weight of the read:
+ *   - a read with ONE candidate keeps it: new_tiebreak[j] = tiebreak[j], draw[j] is not looked at;
+ *   - otherwise new_tiebreak[j] = draw[j] * (s <= 0 ? 1.0 : (double)weight[j] / (double)s): one IEEE float64 division and one
+ *     multiplication (the conversions are exact in this domain), and tiebreak[j] is not looked at;
+ *   - winner[r], r < n_reads = the candidate of read r with the largest new_tiebreak, the LAST one among equal ones; -1 for a read
+ *     without candidates.  (The candidates of a read share one score, so the score plays no part here.)
+ * m < 2^31.  A record outside the domain returns -2 before anything is written. */
+int mpn_pick_weighted(int64_t m, const int32_t *read, const int64_t *weight, const double *tiebreak, const double *draw,
+                      int32_t n_reads, double *new_tiebreak, int64_t *winner);
+
+/* second[r], r < n_reads = the largest score[i] over the rows with read[i] == r and assembly[i] != excluded[r], or 0 if there is
+ * no such row (the reference's step_unique_alignment, bin/megapath_nano.py:2563-2584, where a missing second best is filled
+ * with 0).  read[i] in [0, n_reads); assembly[i] >= 0; excluded[r] is an assembly code or -1 (nothing excluded); score[i] is any
+ * int64 but the smallest one.  A record outside the domain returns -2 before anything is written. */
+int mpn_second_best_by_read(int64_t n, const int32_t *read, const int32_t *assembly, const int64_t *score,
+                            int32_t n_reads, const int32_t *excluded, int64_t *second);
 
 #ifdef __cplusplus
 }

@@ -30,9 +30,19 @@ sequence_id).  Here they are mpn_cover_by_bed (the BED merged on the device, the
 mpn_bed_union behind the functions of the same names, `noise_removal` and `closing_spike_filter`; `host_bed_union` and
 `host_cover_by_bed` are the numpy statements.  The covered base pairs are exact integers from either; the fraction they are
 compared through is bedtools' float32 quotient printed with six decimals, computed on the host.
+
+The best alignment of every read: `align_list_to_best_align_list` (the reference's :244-310) keeps the best row per (read,
+assembly), takes the rows that reach their read's largest score as candidates, and decides a read with several candidates by a
+random draw weighted with the abundance of the candidates' assemblies among the reads that have one candidate only.  Behind it
+are mpn_best_candidates (the radix sort by (read, assembly), segmented scans) and mpn_pick_weighted; mpn_second_best_by_read is the
+device half of `unique_alignment` (step_unique_alignment, :2553-2593).  `short_alignment_removal` (:2293-2327), `closing_spike_step`
+(:2330-2422 with its two draws) and `combine_with_human_and_decoy` (:2425-2446) complete the steps that stand on it.  The random
+numbers come from the host, one `rng()` per candidate of a read with several, in the order of (read_id, assembly_id): the number
+and order of the calls are the reference's.
 """
 import ctypes as ct
 import math
+import random
 
 import numpy as np
 import pandas
@@ -57,6 +67,12 @@ def _lib():
         lib.mpn_bed_union.restype = ct.c_int
         lib.mpn_cover_by_bed.argtypes = [ct.c_int64, P, P, P, ct.c_int64, P, P, P, ct.c_int32, P]
         lib.mpn_cover_by_bed.restype = ct.c_int
+        lib.mpn_best_candidates.argtypes = [ct.c_int64, P, P, P, P, ct.c_int32, ct.c_int32, P, P, P, P, P]
+        lib.mpn_best_candidates.restype = ct.c_int
+        lib.mpn_pick_weighted.argtypes = [ct.c_int64, P, P, P, P, ct.c_int32, P, P]
+        lib.mpn_pick_weighted.restype = ct.c_int
+        lib.mpn_second_best_by_read.argtypes = [ct.c_int64, P, P, P, ct.c_int32, P, P]
+        lib.mpn_second_best_by_read.restype = ct.c_int
         _bound = True
     return lib
 
@@ -594,3 +610,235 @@ def closing_spike_filter(*, align_list, best_align_list, best_align_list_with_sh
                                    device=device)['read_id']
     out = align_list[~align_list['read_id'].isin(gone).to_numpy()]
     return out, noise_bed_out, spike_bed, noise_stat, best_align_list.shape[0], int(out['read_id'].nunique())
+
+
+# ---- the best alignment of every read -----------------------------------------------------------------------------------------
+BEST_TILE = 2048   # MPN_BEST_TILE of include/mpn_abundance.h: the rows one block of the device's segmented scans covers (the tests
+#                    put their sizes around its multiples; tests/test_best_align.py checks that the two numbers agree)
+_NO_SCORE = np.iinfo(np.int64).min
+
+
+def _best_args(read, assembly, score, tiebreak, n_reads, n_assemblies):
+    read, assembly = np.ascontiguousarray(read, dtype=np.int32), np.ascontiguousarray(assembly, dtype=np.int32)
+    score, tiebreak = np.ascontiguousarray(score, dtype=np.int64), np.ascontiguousarray(tiebreak, dtype=np.float64)
+    if not (len(read) == len(assembly) == len(score) == len(tiebreak)):
+        raise ValueError('read, assembly, score and tiebreak have one entry per row')
+    return read, assembly, score, tiebreak, int(n_reads), int(n_assemblies)
+
+
+def device_best_candidates(read, assembly, score, tiebreak, n_reads, n_assemblies):
+    """mpn_best_candidates.  Row i: read[i] in [0, n_reads), assembly[i] in [0, n_assemblies), score[i] (int64 above -2^63),
+    tiebreak[i] (finite).  -> cand_row int64[m], cand_read int32[m], read_count int64[n_reads], read_first int64[n_reads]: per
+    (read, assembly) the row with the largest (score, tiebreak), the last in input order among equal ones; of those the ones with
+    their read's largest score, ordered by (read, assembly); per read their number and the position of the first."""
+    read, assembly, score, tiebreak, n_reads, n_assemblies = _best_args(read, assembly, score, tiebreak, n_reads, n_assemblies)
+    n = len(read)
+    cand_row, cand_read, n_cand = np.empty(max(n, 1), np.int64), np.empty(max(n, 1), np.int32), ct.c_int64(0)
+    count, first = np.zeros(max(n_reads, 1), np.int64), np.zeros(max(n_reads, 1), np.int64)
+    _ffi.check(_lib().mpn_best_candidates(n, read.ctypes.data, assembly.ctypes.data, score.ctypes.data, tiebreak.ctypes.data, n_reads, n_assemblies,
+                                          cand_row.ctypes.data, cand_read.ctypes.data, ct.byref(n_cand), count.ctypes.data, first.ctypes.data),
+               'mpn_best_candidates')
+    m = n_cand.value
+    return cand_row[:m].copy(), cand_read[:m].copy(), count[:n_reads], first[:n_reads]
+
+
+def host_best_candidates(read, assembly, score, tiebreak, n_reads, n_assemblies):
+    """numpy statement of mpn_best_candidates (same arguments, same result)."""
+    read, assembly, score, tiebreak, n_reads, n_assemblies = _best_args(read, assembly, score, tiebreak, n_reads, n_assemblies)
+    n = len(read)
+    bad = (read < 0) | (read >= n_reads) | (assembly < 0) | (assembly >= n_assemblies) | (score == _NO_SCORE) | ~np.isfinite(tiebreak)
+    if bad.any():
+        raise ValueError(f'record {int(np.flatnonzero(bad)[0])} outside the domain')
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(n_reads, np.int64), np.zeros(n_reads, np.int64)
+    order = np.lexsort((np.arange(n), tiebreak, score, assembly, read))    # the input order decides among equal rows; -0.0 == 0.0
+    r, a = read[order], assembly[order]
+    last = np.ones(n, dtype=bool)
+    last[:-1] = (r[1:] != r[:-1]) | (a[1:] != a[:-1])
+    kept = order[last]                                                     # ordered by (read, assembly)
+    k_read, k_score = read[kept], score[kept]
+    head = np.ones(len(kept), dtype=bool)
+    head[1:] = k_read[1:] != k_read[:-1]
+    read_max = np.full(n_reads, _NO_SCORE, dtype=np.int64)
+    read_max[k_read[head]] = np.maximum.reduceat(k_score, np.flatnonzero(head))
+    cand = k_score == read_max[k_read]
+    count = np.bincount(k_read[cand], minlength=n_reads).astype(np.int64)
+    first = np.cumsum(count) - count
+    return kept[cand].astype(np.int64), k_read[cand].astype(np.int32), count, first
+
+
+def _pick_args(read, weight, tiebreak, draw, n_reads):
+    read, weight = np.ascontiguousarray(read, dtype=np.int32), np.ascontiguousarray(weight, dtype=np.int64)
+    tiebreak, draw = np.ascontiguousarray(tiebreak, dtype=np.float64), np.ascontiguousarray(draw, dtype=np.float64)
+    if not (len(read) == len(weight) == len(tiebreak) == len(draw)):
+        raise ValueError('read, weight, tiebreak and draw have one entry per candidate')
+    return read, weight, tiebreak, draw, int(n_reads)
+
+
+def device_pick_weighted(read, weight, tiebreak, draw, n_reads):
+    """mpn_pick_weighted.  Candidate j: read[j] in [0, n_reads), non-decreasing; weight[j] >= 0, sums per read below 2^53;
+    tiebreak[j] and draw[j] finite.  -> new_tiebreak float64[m], winner int64[n_reads]: a read with one candidate keeps that
+    candidate's tiebreak; in the others new = draw * (1.0 if the read's summed weight s <= 0 else weight / s) in float64; winner[r] =
+    the candidate of read r with the largest new tiebreak, the last among equal ones, -1 for a read without candidates."""
+    read, weight, tiebreak, draw, n_reads = _pick_args(read, weight, tiebreak, draw, n_reads)
+    m = len(read)
+    new, winner = np.empty(max(m, 1), np.float64), np.full(max(n_reads, 1), -1, np.int64)
+    _ffi.check(_lib().mpn_pick_weighted(m, read.ctypes.data, weight.ctypes.data, tiebreak.ctypes.data, draw.ctypes.data, n_reads, new.ctypes.data,
+                                        winner.ctypes.data), 'mpn_pick_weighted')
+    return new[:m], winner[:n_reads]
+
+
+def host_pick_weighted(read, weight, tiebreak, draw, n_reads):
+    """numpy statement of mpn_pick_weighted (same arguments, same result)."""
+    read, weight, tiebreak, draw, n_reads = _pick_args(read, weight, tiebreak, draw, n_reads)
+    m = len(read)
+    total = np.zeros(n_reads, dtype=np.int64)
+    bad = (read < 0) | (read >= n_reads) | (weight < 0) | (weight >= 2 ** 53) | ~np.isfinite(tiebreak) | ~np.isfinite(draw)
+    bad[1:] |= read[1:] < read[:-1]
+    if not bad.any():
+        np.add.at(total, read, weight)
+        bad |= total[read] >= 2 ** 53
+    if bad.any():
+        raise ValueError(f'candidate {int(np.flatnonzero(bad)[0])} outside the domain')
+    count = np.bincount(read, minlength=n_reads)
+    s = total[read]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        relative = np.where(s <= 0, 1.0, weight.astype(np.float64) / s.astype(np.float64))
+    new = np.where(count[read] == 1, tiebreak, draw * relative)
+    winner = np.full(n_reads, -1, dtype=np.int64)
+    order = np.lexsort((np.arange(m), new, read))
+    last = np.ones(m, dtype=bool)
+    last[:-1] = read[order][1:] != read[order][:-1]
+    winner[read[order[last]]] = order[last]
+    return new, winner
+
+
+def _second_args(read, assembly, score, n_reads, excluded):
+    read, assembly = np.ascontiguousarray(read, dtype=np.int32), np.ascontiguousarray(assembly, dtype=np.int32)
+    score, excluded = np.ascontiguousarray(score, dtype=np.int64), np.ascontiguousarray(excluded, dtype=np.int32)
+    if not (len(read) == len(assembly) == len(score)) or len(excluded) != int(n_reads):
+        raise ValueError('read, assembly and score have one entry per row, excluded one per read')
+    return read, assembly, score, int(n_reads), excluded
+
+
+def device_second_best_by_read(read, assembly, score, n_reads, excluded):
+    """mpn_second_best_by_read -> int64[n_reads]: the largest score[i] over the rows of read r with assembly[i] != excluded[r]
+    (-1: nothing is excluded), 0 for a read without such a row.  assembly >= 0, score above -2^63."""
+    read, assembly, score, n_reads, excluded = _second_args(read, assembly, score, n_reads, excluded)
+    second = np.zeros(max(n_reads, 1), np.int64)
+    _ffi.check(_lib().mpn_second_best_by_read(len(read), read.ctypes.data, assembly.ctypes.data, score.ctypes.data, n_reads, excluded.ctypes.data,
+                                              second.ctypes.data), 'mpn_second_best_by_read')
+    return second[:n_reads]
+
+
+def host_second_best_by_read(read, assembly, score, n_reads, excluded):
+    """numpy statement of mpn_second_best_by_read (same arguments, same result)."""
+    read, assembly, score, n_reads, excluded = _second_args(read, assembly, score, n_reads, excluded)
+    bad = (read < 0) | (read >= n_reads) | (assembly < 0) | (score == _NO_SCORE)
+    if bad.any() or (excluded < -1).any():
+        raise ValueError('a record outside the domain')
+    second = np.full(n_reads, _NO_SCORE, dtype=np.int64)
+    on = assembly != excluded[read]
+    np.maximum.at(second, read[on], score[on])
+    second[second == _NO_SCORE] = 0
+    return second
+
+
+def align_list_to_best_align_list(*, align_list, assembly_length, assembly_tax=None, noise_bed=None, rng=None, device=None):
+    """The reference's align_list_to_best_align_list: one row per read, its best alignment.  align_list: the Align() table with
+    read_id and assembly_id as strings; assembly_length / assembly_tax / noise_bed: as in align_stat_by_assembly_id (they stand for
+    the reference's assembly_metadata).  Per (read, assembly) the row with the largest (alignment_score, tiebreaker) is kept, the
+    last in table order among equal ones; the kept rows with their read's largest score are its candidates.  A read with one
+    candidate keeps it and its tiebreaker.  For the others, assembly_abundance = adjusted_total_aligned_bp of
+    align_stat_by_assembly_id over the one-candidate reads' rows (0 for an assembly that has none), and every candidate, in the order
+    of (read_id, assembly_id), gets the tiebreaker rng() * (abundance of its assembly / summed abundance of the read's candidates; 1
+    where that sum is 0); the largest wins, the last one among equal ones.
+    rng: a callable without arguments, default random.random; called once per candidate of a read with several, in that order, and
+    never otherwise.  -> the winning rows with their index labels and columns, ordered by read_id, alignment_score_tiebreaker
+    replaced in the drawn reads.  An empty table comes back empty, without a draw.  device: as in covered_bp_by_assembly."""
+    if align_list.shape[0] == 0:
+        return align_list.copy()
+    if device is None:
+        device = True
+    if rng is None:
+        rng = random.random
+    reads, rc = _codes(align_list['read_id'])              # np.unique orders str like pandas' sort_values: the order of the draws
+    asms, ac = _codes(align_list['assembly_id'])
+    tiebreak = align_list['alignment_score_tiebreaker'].to_numpy(dtype=np.float64)
+    cand_row, cand_read, count, _ = (device_best_candidates if device else host_best_candidates)(
+        rc, ac, align_list['alignment_score'].to_numpy(dtype=np.int64), tiebreak, len(reads), len(asms))
+    alone = count[cand_read] == 1
+    weight = np.zeros(len(cand_row), dtype=np.int64)
+    if alone.any() and not alone.all():
+        stat = align_stat_by_assembly_id(align_list.iloc[cand_row[alone]], assembly_length, assembly_tax, noise_bed=noise_bed, device=device)
+        abundance = np.zeros(len(asms), dtype=np.int64)
+        abundance[pandas.Index(asms).get_indexer(stat['assembly_id'].to_numpy())] = stat['adjusted_total_aligned_bp'].to_numpy(dtype=np.int64)
+        weight = abundance[ac[cand_row]]
+    draw = np.zeros(len(cand_row), dtype=np.float64)
+    draw[~alone] = [rng() for _ in range(int((~alone).sum()))]
+    new, winner = (device_pick_weighted if device else host_pick_weighted)(cand_read, weight, tiebreak[cand_row], draw, len(reads))
+    out = align_list.iloc[cand_row[winner]].copy()
+    out['alignment_score_tiebreaker'] = new[winner]
+    return out
+
+
+def short_alignment_removal(*, align_list, min_align_length, assembly_length, assembly_tax=None, rng=None, device=None):
+    """step_short_alignment_removal (megapath_nano.py:2302-2321): every read whose best alignment (align_list_to_best_align_list,
+    without a noise BED) spans fewer than min_align_length target positions leaves with all its alignments.
+    -> align_list (input order), num_read_before (reads), num_read_after"""
+    best = align_list_to_best_align_list(align_list=align_list, assembly_length=assembly_length, assembly_tax=assembly_tax, rng=rng, device=device)
+    gone = best['read_id'][((best['sequence_to'] - best['sequence_from']) < min_align_length).to_numpy()]
+    out = align_list[~align_list['read_id'].isin(gone).to_numpy()]
+    return out, best.shape[0], best.shape[0] - gone.shape[0]
+
+
+def unique_alignment(*, align_list, best_align_list, human_best_align_list=None, decoy_best_align_list=None, unique_align_threshold, device=None):
+    """step_unique_alignment (megapath_nano.py:2561-2590): the rows of best_align_list (one per read; ValueError otherwise) whose
+    score stands clear of the read's second best -- the largest alignment_score among the read's rows of align_list on OTHER
+    assemblies than the best row's and its rows in the human and decoy tables (read_id, alignment_score), 0 if there is none:
+    kept iff float64(alignment_score) * (unique_align_threshold / 100) > second best.
+    -> best_align_list with the column second_best_alignment_score, num_read_before, num_read_after"""
+    if device is None:
+        device = True
+    if best_align_list['read_id'].duplicated().any():
+        raise ValueError('best_align_list: a read_id occurs twice')
+    extra = [t for t in (human_best_align_list, decoy_best_align_list) if t is not None and t.shape[0] > 0]
+    n_al, n_best = align_list.shape[0], best_align_list.shape[0]
+    reads, rc = _codes(pandas.concat([t['read_id'] for t in [align_list, best_align_list] + extra], ignore_index=True))
+    asms, ac = _codes(pandas.concat([align_list['assembly_id'], best_align_list['assembly_id']], ignore_index=True))
+    excluded = np.full(len(reads), -1, dtype=np.int32)
+    excluded[rc[n_al:n_al + n_best]] = ac[n_al:]
+    # the human and decoy rows count whatever their assembly: they go under a code of their own
+    row_read = np.concatenate([rc[:n_al], rc[n_al + n_best:]])
+    row_asm = np.concatenate([ac[:n_al], np.full(len(rc) - n_al - n_best, len(asms), dtype=ac.dtype)])
+    row_score = np.concatenate([t['alignment_score'].to_numpy(dtype=np.int64) for t in [align_list] + extra])
+    second = (device_second_best_by_read if device else host_second_best_by_read)(row_read, row_asm, row_score, len(reads), excluded)
+    out = best_align_list.copy()
+    out['second_best_alignment_score'] = second[rc[n_al:n_al + n_best]]
+    keep = out['alignment_score'].to_numpy(dtype=np.float64) * (unique_align_threshold / 100) > out['second_best_alignment_score'].to_numpy(dtype=np.float64)
+    out = out[keep].copy()
+    return out, n_best, out.shape[0]
+
+
+def closing_spike_step(*, align_list, align_list_with_short_alignment, noise_bed, assembly_length, max_align_noise_overlap, expected_max_depth_stdev=9,
+                       assembly_tax=None, rng=None, device=None):
+    """The whole step_closing_spike_filter (megapath_nano.py:2330-2422): the best table of align_list is drawn first, that of
+    align_list_with_short_alignment second, as the reference draws them, and both go to closing_spike_filter.  -> its result"""
+    kw = dict(assembly_length=assembly_length, assembly_tax=assembly_tax, rng=rng, device=device)
+    best = align_list_to_best_align_list(align_list=align_list, **kw)
+    best_with_short = align_list_to_best_align_list(align_list=align_list_with_short_alignment, **kw)
+    return closing_spike_filter(align_list=align_list, best_align_list=best, best_align_list_with_short_alignment=best_with_short, noise_bed=noise_bed,
+                                assembly_length=assembly_length, max_align_noise_overlap=max_align_noise_overlap,
+                                expected_max_depth_stdev=expected_max_depth_stdev, assembly_tax=assembly_tax, device=device)
+
+
+def combine_with_human_and_decoy(*, align_list, human_and_decoy_best_align_list):
+    """step_combine_with_human_and_decoy (megapath_nano.py:2432-2441): the rows of align_list that score above their read's row of
+    human_and_decoy_best_align_list (one row per read; a read it lacks has 0 there), followed by that table's own rows; the columns
+    in sorted order (pandas.concat(sort=True))."""
+    other = human_and_decoy_best_align_list
+    if other['read_id'].duplicated().any():
+        raise ValueError('human_and_decoy_best_align_list: a read_id occurs twice')
+    best = pandas.Series(other['alignment_score'].to_numpy(), index=other['read_id'].to_numpy())
+    bar = align_list['read_id'].map(best).fillna(0).to_numpy()
+    return pandas.concat([align_list[align_list['alignment_score'].to_numpy() > bar], other], axis=0, sort=True)

@@ -5,6 +5,8 @@
 #include "mpn_common.h"
 #include "../../include/mpn_abundance.h"
 
+#include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace mpn {
@@ -633,6 +635,221 @@ static int bed_pack(const char *who, int64_t n, const int32_t *key, const int64_
     return 0;
 }
 
+// ---- the best alignment of every read: candidates, the abundance-weighted draw, the second best ------------------------------
+// (align_list_to_best_align_list and step_unique_alignment of the reference.)  Everything here is a segmented inclusive scan over
+// a list ordered by read: element i carries a value and `head` = 1 where its segment starts; join(a, b) = b if b.head, else
+// merge(a, b), and head = a.head | b.head -- associative whenever merge is.  A pass P names the value type V, identity(), merge(),
+// load(i) and store(i, inclusive value).  Three launches a pass, a lane per element over tiles of MPN_BEST_TILE, like the bu_*
+// kernels: the joined value of every tile; one block that turns those into what enters each tile; the rescan that stores.
+constexpr int BA_THREADS = 256, BA_ITEMS = MPN_BEST_TILE / BA_THREADS;
+static_assert(MPN_BEST_TILE % BA_THREADS == 0, "a tile is whole blocks of lanes");
+
+template <class V>
+__device__ __forceinline__ V ba_shfl_up(const V &v, int d) {
+    static_assert(sizeof(V) % 4 == 0, "moved lane to lane as 32-bit words");
+    int w[sizeof(V) / 4];
+    __builtin_memcpy(w, &v, sizeof(V));
+#pragma unroll
+    for (unsigned k = 0; k < sizeof(V) / 4; ++k) w[k] = __shfl_up(w[k], d);
+    V o;
+    __builtin_memcpy(&o, w, sizeof(V));
+    return o;
+}
+
+template <class P>
+__device__ __forceinline__ typename P::V ba_join(const typename P::V &a, const typename P::V &b) {
+    typename P::V r = b.head ? b : P::merge(a, b);
+    r.head = a.head | b.head;
+    return r;
+}
+
+// One step over the block's 256 elements: v -> its inclusive value over the whole list; run: the joined value of everything before
+// these 256, moved on to include them.  Every lane of the block calls it (one barrier); ws alternates between steps.
+template <class P>
+__device__ __forceinline__ typename P::V ba_step(typename P::V v, typename P::V &run, typename P::V *ws) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const typename P::V o = ba_shfl_up(v, d);
+        if (lane >= d) v = ba_join<P>(o, v);
+    }
+    if (lane == 63) ws[wv] = v;
+    __syncthreads();
+    typename P::V before = run, all = run;
+#pragma unroll
+    for (int w = 0; w < BA_THREADS / 64; ++w) {
+        const typename P::V t = ws[w];
+        if (w < wv) before = ba_join<P>(before, t);
+        all = ba_join<P>(all, t);
+    }
+    run = all;
+    return ba_join<P>(before, v);
+}
+
+// APPLY = false: tiles[tile] = the joined value of the tile.  APPLY = true: tiles[tile] is what enters the tile; store everything.
+template <class P, bool APPLY>
+__global__ __launch_bounds__(BA_THREADS) void ba_scan_kernel(P p, int64_t n, typename P::V *__restrict__ tiles) {
+    __shared__ typename P::V ws[2][BA_THREADS / 64];
+    const int64_t base = (int64_t)blockIdx.x * MPN_BEST_TILE;
+    typename P::V run = P::identity();
+    if (APPLY) run = tiles[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < BA_ITEMS; ++k) {
+        if (base + k * BA_THREADS >= n) break;   // (the whole block leaves together)
+        const int64_t i = base + k * BA_THREADS + threadIdx.x;
+        typename P::V v = P::identity();
+        if (i < n) v = p.load(i);
+        const typename P::V inc = ba_step<P>(v, run, ws[k & 1]);
+        if (APPLY && i < n) p.store(i, inc);
+    }
+    if (!APPLY && threadIdx.x == 0) tiles[blockIdx.x] = run;
+}
+
+// one block, in place: tiles[t] = the joined value of the tiles before t
+template <class P>
+__global__ __launch_bounds__(BA_THREADS) void ba_carry_kernel(typename P::V *__restrict__ tiles, int nb) {
+    __shared__ typename P::V sh[BA_THREADS];
+    const int t = threadIdx.x, per = (nb + BA_THREADS - 1) / BA_THREADS, lo = min(nb, t * per), hi = min(nb, lo + per);
+    typename P::V s = P::identity();
+    for (int k = lo; k < hi; ++k) s = ba_join<P>(s, tiles[k]);
+    sh[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        typename P::V acc = P::identity();
+        for (int k = 0; k < BA_THREADS; ++k) { const typename P::V v = sh[k]; sh[k] = acc; acc = ba_join<P>(acc, v); }
+    }
+    __syncthreads();
+    typename P::V o = sh[t];
+    for (int k = lo; k < hi; ++k) { const typename P::V v = tiles[k]; tiles[k] = o; o = ba_join<P>(o, v); }
+}
+
+template <class P>
+static int ba_scan(const P &p, int64_t n, hipStream_t st) {
+    const int nb = (int)((n + MPN_BEST_TILE - 1) / MPN_BEST_TILE);
+    DevBuf<typename P::V> tiles;
+    if (tiles.alloc((size_t)nb)) return -1;
+    hipLaunchKernelGGL((ba_scan_kernel<P, false>), dim3(nb), dim3(BA_THREADS), 0, st, p, n, tiles.p);
+    hipLaunchKernelGGL((ba_carry_kernel<P>), dim3(1), dim3(BA_THREADS), 0, st, tiles.p, nb);
+    hipLaunchKernelGGL((ba_scan_kernel<P, true>), dim3(nb), dim3(BA_THREADS), 0, st, p, n, tiles.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    MPN_HIP_CHECK(hipStreamSynchronize(st));   // `tiles` is read by the kernels queued above: it must outlive them
+    return 0;
+}
+
+constexpr int64_t BA_MIN = INT64_MIN;   // no score: the domain leaves it out
+
+// the bits of a finite double as an unsigned integer of the same order
+static inline uint64_t ba_ordered_bits(double x) {
+    uint64_t u;
+    memcpy(&u, &x, 8);
+    return u >> 63 ? ~u : u | 0x8000000000000000ULL;
+}
+
+// Rows sorted by lo = read << 32 | assembly, input order kept among equal keys.  A segment is one (read, assembly); the scan is the
+// arg-max of (score, tiebreak), the later row winning among equal ones.  The last row of a segment then knows the segment's kept
+// row: w_idx[i] = that row (-1 on every other i), w_score[i] = its score.
+struct BaGroupPass {
+    struct V { int64_t score; uint64_t tb; int64_t idx; int32_t head, pad; };
+    const Rec3 *rec; const int64_t *score; const uint64_t *tb; int64_t n; int64_t *w_idx, *w_score;
+    __device__ static V identity() { return V{BA_MIN, 0, -1, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return (b.score > a.score || (b.score == a.score && b.tb >= a.tb)) ? b : a; }
+    __device__ V load(int64_t i) const {
+        const Rec3 r = rec[i];
+        return V{score[r.idx], tb[r.idx], r.idx, i == 0 || rec[i - 1].lo != r.lo, 0};
+    }
+    __device__ void store(int64_t i, const V &inc) const {
+        const bool tail = i + 1 == n || rec[i + 1].lo != rec[i].lo;
+        w_idx[i] = tail ? inc.idx : -1;
+        w_score[i] = inc.score;
+    }
+};
+
+// A segment is one read; over its kept rows: the largest score and how many have it.  The last row of a read stores both.
+struct BaReadPass {
+    struct V { int64_t mx, cnt; int32_t head, pad; };
+    const Rec3 *rec; const int64_t *w_idx, *w_score; int64_t n; int64_t *r_max, *r_cnt;
+    __device__ static V identity() { return V{BA_MIN, 0, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return a.mx > b.mx ? a : b.mx > a.mx ? b : V{a.mx, a.cnt + b.cnt, 0, 0}; }
+    __device__ V load(int64_t i) const {
+        const bool kept = w_idx[i] >= 0;
+        return V{kept ? w_score[i] : BA_MIN, kept ? 1 : 0, i == 0 || (rec[i - 1].lo >> 32) != (rec[i].lo >> 32), 0};
+    }
+    __device__ void store(int64_t i, const V &inc) const {
+        const uint64_t r = rec[i].lo >> 32;
+        if (i + 1 == n || (rec[i + 1].lo >> 32) != r) { r_max[r] = inc.mx; r_cnt[r] = inc.cnt; }
+    }
+};
+
+// No segments: the running count of candidates (kept rows with their read's largest score) puts each into its place in the list.
+struct BaCompactPass {
+    struct V { int64_t c; int32_t head, pad; };
+    const Rec3 *rec; const int64_t *w_idx, *w_score, *r_max; int64_t n; int64_t *cand_row; int32_t *cand_read; int64_t *n_cand;
+    __device__ static V identity() { return V{0, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return V{a.c + b.c, 0, 0}; }
+    __device__ bool candidate(int64_t i) const { return w_idx[i] >= 0 && w_score[i] == r_max[rec[i].lo >> 32]; }
+    __device__ V load(int64_t i) const { return V{candidate(i) ? 1 : 0, 0, 0}; }
+    __device__ void store(int64_t i, const V &inc) const {
+        if (candidate(i)) { cand_row[inc.c - 1] = w_idx[i]; cand_read[inc.c - 1] = (int32_t)(rec[i].lo >> 32); }
+        if (i + 1 == n) n_cand[0] = inc.c;
+    }
+};
+
+// A segment is one read of the candidate list: its summed weight and its number of candidates, stored by its last candidate.
+struct BaWeightPass {
+    struct V { int64_t sum, cnt; int32_t head, pad; };
+    const int32_t *read; const int64_t *weight; int64_t m; int64_t *r_sum, *r_cnt;
+    __device__ static V identity() { return V{0, 0, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return V{a.sum + b.sum, a.cnt + b.cnt, 0, 0}; }
+    __device__ V load(int64_t j) const { return V{weight[j], 1, j == 0 || read[j - 1] != read[j], 0}; }
+    __device__ void store(int64_t j, const V &inc) const {
+        if (j + 1 == m || read[j + 1] != read[j]) { r_sum[read[j]] = inc.sum; r_cnt[read[j]] = inc.cnt; }
+    }
+};
+
+// The new tiebreaker of every candidate.  One division and one multiplication in float64, as numpy does them: the file is built
+// without fast-math, and a product of a quotient leaves nothing to contract.
+__global__ __launch_bounds__(256) void ba_tiebreak_kernel(const int32_t *__restrict__ read, const int64_t *__restrict__ weight, const double *__restrict__ tiebreak,
+                                                          const double *__restrict__ draw, int64_t m, const int64_t *__restrict__ r_sum,
+                                                          const int64_t *__restrict__ r_cnt, double *__restrict__ out) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t r = read[j];
+        if (r_cnt[r] == 1) { out[j] = tiebreak[j]; continue; }
+        const int64_t s = r_sum[r];
+        const double relative = s <= 0 ? 1.0 : (double)weight[j] / (double)s;
+        out[j] = draw[j] * relative;
+    }
+}
+
+// A segment is one read of the candidate list: the arg-max of the new tiebreaker, the later candidate winning among equal ones.
+struct BaPickPass {
+    struct V { double tb; int64_t idx; int32_t head, pad; };
+    const int32_t *read; const double *tb; int64_t m; int64_t *winner;
+    __device__ static V identity() { return V{-__builtin_huge_val(), -1, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return b.tb >= a.tb ? b : a; }
+    __device__ V load(int64_t j) const { return V{tb[j], j, j == 0 || read[j - 1] != read[j], 0}; }
+    __device__ void store(int64_t j, const V &inc) const {
+        if (j + 1 == m || read[j + 1] != read[j]) winner[read[j]] = inc.idx;
+    }
+};
+
+__global__ __launch_bounds__(256) void ba_fill_kernel(int64_t *__restrict__ out, int64_t n, int64_t value) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = value;
+}
+
+// second[r] = max(second[r], score) over the rows of read r off its excluded assembly.  The plain read first: the value only grows,
+// so a row that cannot raise it needs no atomic -- a read with many rows would otherwise queue them all on one address.
+__global__ __launch_bounds__(256) void ba_second_kernel(const int32_t *__restrict__ read, const int32_t *__restrict__ assembly, const int64_t *__restrict__ score,
+                                                        int64_t n, const int32_t *__restrict__ excluded, long long *second) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t r = read[i];
+        if (assembly[i] == excluded[r]) continue;
+        const long long s = score[i];
+        if (__atomic_load_n(&second[r], __ATOMIC_RELAXED) < s) atomicMax(&second[r], s);
+    }
+}
+
+static int ba_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
+
 }  // namespace mpn
 
 using namespace mpn;
@@ -862,5 +1079,130 @@ extern "C" int mpn_cover_by_bed(int64_t n_bed, const int32_t *bed_key, const int
     MPN_HIP_CHECK(hipGetLastError());
     if (d_cov.download(covered, (size_t)n_q, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int mpn_best_candidates(int64_t n, const int32_t *read, const int32_t *assembly, const int64_t *score, const double *tiebreak, int32_t n_reads,
+                                   int32_t n_assemblies, int64_t *cand_row, int32_t *cand_read, int64_t *n_cand, int64_t *read_count, int64_t *read_first) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || n_reads < 0 || n_assemblies < 0 || !n_cand || (n_reads > 0 && (!read_count || !read_first)) ||
+        (n > 0 && (!read || !assembly || !score || !tiebreak || !cand_row || !cand_read))) {
+        set_error("mpn_best_candidates: bad arguments");
+        return -2;
+    }
+    std::vector<uint64_t> hi((size_t)n, 0), lo((size_t)n), tb((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (read[i] < 0 || read[i] >= n_reads || assembly[i] < 0 || assembly[i] >= n_assemblies || score[i] == BA_MIN || !std::isfinite(tiebreak[i])) {
+            set_error("mpn_best_candidates: record %lld outside the domain (read in [0, n_reads), assembly in [0, n_assemblies), score > -2^63, finite tiebreak)",
+                      (long long)i);
+            return -2;
+        }
+        lo[(size_t)i] = (uint64_t)read[i] << 32 | (uint64_t)assembly[i];
+        tb[(size_t)i] = ba_ordered_bits(tiebreak[i] == 0.0 ? 0.0 : tiebreak[i]);
+    }
+    *n_cand = 0;
+    for (int32_t r = 0; r < n_reads; ++r) read_count[r] = read_first[r] = 0;
+    if (n == 0) return 0;
+
+    hipStream_t st = 0;
+    DevBuf<uint64_t> d_hi, d_lo, d_tb;
+    DevBuf<int64_t> d_score, w_idx, w_score, r_max, r_cnt, d_row, d_n;
+    DevBuf<int32_t> d_read;
+    DevBuf<Rec3> a, b;
+    if (d_hi.upload(hi.data(), (size_t)n, st) || d_lo.upload(lo.data(), (size_t)n, st) || d_tb.upload(tb.data(), (size_t)n, st) ||
+        d_score.upload(score, (size_t)n, st) || a.alloc((size_t)n) || b.alloc((size_t)n) || w_idx.alloc((size_t)n) || w_score.alloc((size_t)n) ||
+        r_max.alloc((size_t)n_reads) || r_cnt.alloc((size_t)n_reads) || r_cnt.zero(st) || d_row.alloc((size_t)n) || d_read.alloc((size_t)n) || d_n.alloc(1)) return -1;
+    hipLaunchKernelGGL(rs_fill_kernel, dim3(ba_grid(n)), dim3(256), 0, st, (const uint64_t *)d_hi.p, (const uint64_t *)d_lo.p, n, a.p);
+    hipLaunchKernelGGL(ba_fill_kernel, dim3(ba_grid(n_reads)), dim3(256), 0, st, r_max.p, (int64_t)n_reads, BA_MIN);
+    MPN_HIP_CHECK(hipGetLastError());
+    // digits that no record has: all of hi, the bytes of the assembly above n_assemblies - 1 and those of the read above n_reads - 1
+    uint32_t skip = 0xff00;
+    for (int p = 0; p < 4; ++p) {
+        if (((uint64_t)(n_assemblies - 1) >> (8 * p)) == 0) skip |= 1u << p;
+        if (((uint64_t)(n_reads - 1) >> (8 * p)) == 0) skip |= 1u << (4 + p);
+    }
+    Rec3 *rec = nullptr;
+    if (radix_sort_rec3(a.p, b.p, n, &rec, st, skip)) return -1;
+    if (ba_scan(BaGroupPass{rec, d_score.p, d_tb.p, n, w_idx.p, w_score.p}, n, st) ||
+        ba_scan(BaReadPass{rec, w_idx.p, w_score.p, n, r_max.p, r_cnt.p}, n, st) ||
+        ba_scan(BaCompactPass{rec, w_idx.p, w_score.p, r_max.p, n, d_row.p, d_read.p, d_n.p}, n, st)) return -1;
+    int64_t m = 0;
+    if (d_n.download(&m, 1, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    if (m < 1 || m > n) { set_error("mpn_best_candidates: %lld candidates out of %lld rows", (long long)m, (long long)n); return -1; }
+    if (d_row.download(cand_row, (size_t)m, st) || d_read.download(cand_read, (size_t)m, st) || r_cnt.download(read_count, (size_t)n_reads, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    int64_t first = 0;
+    for (int32_t r = 0; r < n_reads; ++r) { read_first[r] = first; first += read_count[r]; }
+    if (first != m) { set_error("mpn_best_candidates: the counts per read sum to %lld, the list holds %lld", (long long)first, (long long)m); return -1; }
+    *n_cand = m;
+    return 0;
+}
+
+extern "C" int mpn_pick_weighted(int64_t m, const int32_t *read, const int64_t *weight, const double *tiebreak, const double *draw, int32_t n_reads,
+                                 double *new_tiebreak, int64_t *winner) {
+    if (m < 0 || m >= ((int64_t)1 << 31) || n_reads < 0 || (n_reads > 0 && !winner) || (m > 0 && (!read || !weight || !tiebreak || !draw || !new_tiebreak))) {
+        set_error("mpn_pick_weighted: bad arguments");
+        return -2;
+    }
+    int64_t sum = 0;
+    for (int64_t j = 0; j < m; ++j) {
+        const bool head = j == 0 || read[j] != read[j - 1];
+        if (head) sum = 0;
+        if (read[j] < 0 || read[j] >= n_reads || (j > 0 && read[j] < read[j - 1]) || weight[j] < 0 || weight[j] >= ((int64_t)1 << 53) ||
+            (sum += weight[j]) >= ((int64_t)1 << 53) || !std::isfinite(tiebreak[j]) || !std::isfinite(draw[j])) {
+            set_error("mpn_pick_weighted: candidate %lld outside the domain (read in [0, n_reads) and non-decreasing, weight >= 0 with sums below 2^53 per read, "
+                      "finite tiebreak and draw)", (long long)j);
+            return -2;
+        }
+    }
+    for (int32_t r = 0; r < n_reads; ++r) winner[r] = -1;
+    if (m == 0) return 0;
+
+    hipStream_t st = 0;
+    DevBuf<int32_t> d_read;
+    DevBuf<int64_t> d_weight, r_sum, r_cnt, d_winner;
+    DevBuf<double> d_tb, d_draw, d_out;
+    if (d_read.upload(read, (size_t)m, st) || d_weight.upload(weight, (size_t)m, st) || d_tb.upload(tiebreak, (size_t)m, st) || d_draw.upload(draw, (size_t)m, st) ||
+        r_sum.alloc((size_t)n_reads) || r_cnt.alloc((size_t)n_reads) || r_sum.zero(st) || r_cnt.zero(st) || d_winner.alloc((size_t)n_reads) || d_out.alloc((size_t)m)) return -1;
+    hipLaunchKernelGGL(ba_fill_kernel, dim3(ba_grid(n_reads)), dim3(256), 0, st, d_winner.p, (int64_t)n_reads, (int64_t)-1);
+    MPN_HIP_CHECK(hipGetLastError());
+    if (ba_scan(BaWeightPass{d_read.p, d_weight.p, m, r_sum.p, r_cnt.p}, m, st)) return -1;
+    hipLaunchKernelGGL(ba_tiebreak_kernel, dim3(ba_grid(m)), dim3(256), 0, st, (const int32_t *)d_read.p, (const int64_t *)d_weight.p, (const double *)d_tb.p,
+                       (const double *)d_draw.p, m, (const int64_t *)r_sum.p, (const int64_t *)r_cnt.p, d_out.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    if (ba_scan(BaPickPass{d_read.p, d_out.p, m, d_winner.p}, m, st)) return -1;
+    if (d_out.download(new_tiebreak, (size_t)m, st) || d_winner.download(winner, (size_t)n_reads, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int mpn_second_best_by_read(int64_t n, const int32_t *read, const int32_t *assembly, const int64_t *score, int32_t n_reads, const int32_t *excluded,
+                                       int64_t *second) {
+    if (n < 0 || n_reads < 0 || (n_reads > 0 && (!excluded || !second)) || (n > 0 && (!read || !assembly || !score))) {
+        set_error("mpn_second_best_by_read: bad arguments");
+        return -2;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (read[i] < 0 || read[i] >= n_reads || assembly[i] < 0 || score[i] == BA_MIN) {
+            set_error("mpn_second_best_by_read: record %lld outside the domain (read in [0, n_reads), assembly >= 0, score > -2^63)", (long long)i);
+            return -2;
+        }
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (excluded[r] < -1) { set_error("mpn_second_best_by_read: read %d outside the domain (excluded >= -1)", (int)r); return -2; }
+    for (int32_t r = 0; r < n_reads; ++r) second[r] = 0;
+    if (n == 0 || n_reads == 0) return 0;
+
+    hipStream_t st = 0;
+    DevBuf<int32_t> d_read, d_asm, d_excl;
+    DevBuf<int64_t> d_score, d_second;
+    if (d_read.upload(read, (size_t)n, st) || d_asm.upload(assembly, (size_t)n, st) || d_score.upload(score, (size_t)n, st) ||
+        d_excl.upload(excluded, (size_t)n_reads, st) || d_second.alloc((size_t)n_reads)) return -1;
+    hipLaunchKernelGGL(ba_fill_kernel, dim3(ba_grid(n_reads)), dim3(256), 0, st, d_second.p, (int64_t)n_reads, BA_MIN);
+    hipLaunchKernelGGL(ba_second_kernel, dim3(ba_grid(n)), dim3(256), 0, st, (const int32_t *)d_read.p, (const int32_t *)d_asm.p, (const int64_t *)d_score.p, n,
+                       (const int32_t *)d_excl.p, (long long *)d_second.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    if (d_second.download(second, (size_t)n_reads, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    for (int32_t r = 0; r < n_reads; ++r) if (second[r] == BA_MIN) second[r] = 0;   // no row off the excluded assembly
     return 0;
 }
