@@ -167,6 +167,26 @@ int mpn_aln_finish_batch(const mpn_map_opt *opt, int32_t n, const uint8_t *qcode
                          const uint32_t *cigar, const int64_t *cig_off, const int32_t *n_cigar, int32_t force_class,
                          int32_t *out8, uint32_t *cigar_out);
 
+/* ---- stage: hits from chains on arbitrary chains (tests) ---------------------------------------------------------------------
+ * What mpn_map_batch does between chaining and the alignment rounds (minimap2's mm_gen_regs, mm_set_parent, mm_select_sub,
+ * mm_squeeze_a, mm_join_long), run by the same function with the same launches.  Arrays are CSR over reads.  Per chain, in pool
+ * order (arbitrary; chain c's anchors follow those of the read's chains before it): u = score << 32 | cnt and the chain record
+ * fx, fy, lx, ly, mlen, blen as the backtracking kernel leaves it.  anchors: (x, y) word pairs.  names[i] (may be NULL) is hashed
+ * as the mapper hashes it; min_diff = 2k.
+ * path: 0 = the mapper's dispatch (small / large kernel instantiation by chain count, host above max_chains), 1 = the large
+ * instantiation for every read of at most max_chains chains, 2 = the host functions for every read.  max_chains: 0 = 384, else
+ * 1..384.  grid_cap: 0 = the mapper's grids, else at most that many blocks per launch.
+ * Validated on the host before any launch (-1): q_len > 0, every cnt >= 1 and the counts add up to the read's anchors, every
+ * record equal to its chain's first and last anchor, the x words of the first anchors distinct within a read.
+ * Out: n_regs[n], n_a[n]; hits: 15 words per hit, read after read in hit order (room for one per chain): fx, fy, lx, ly, score,
+ * score0, cnt, as, parent, subsc, n_sub, mlen, blen, hash, sam_pri; with opt->with_cigar sq_anchors: the squeezed anchor lists,
+ * read after read, as (x, y) pairs (room for every anchor), else untouched.  Returns 0, or -1. */
+int mpn_hit_select_batch(const mpn_map_opt *opt, int32_t k, int32_t n, const int32_t *q_len, const char *const *names,
+                         const int64_t *chain_off, const uint64_t *u, const uint64_t *fx, const uint64_t *fy, const uint64_t *lx,
+                         const uint64_t *ly, const int32_t *mlen, const int32_t *blen, const int64_t *anchor_off, const uint64_t *anchors,
+                         int32_t path, int32_t max_chains, int32_t grid_cap, int32_t *n_regs, int32_t *n_a, int64_t *hits,
+                         uint64_t *sq_anchors);
+
 /* ---- product call: map a batch of reads, PAF text out ----------------------------------------------------
  * names: n NUL-terminated read names.  paf receives the lines of all reads in input order (NUL terminated).
  * Returns the number of bytes written, or negative error (-3: paf_cap too small). */

@@ -1539,6 +1539,152 @@ static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadS
     return 0;
 }
 
+// What the chain stage leaves on the device for the hit stage: per read the number of its chains and where they and their
+// anchors start in the compact pools, the (score, count) words, the chain records and the chained anchors.
+struct HitChainsDev {
+    const int32_t *n_chain; const int64_t *u_pos, *b_pos; const uint64_t *u; const ChainRec *recs; const u128 *chained;
+};
+// Device buffers of the hit stage that its caller reads afterwards: the squeezed anchor lists (a, sq_off) serve the alignment rounds.
+struct HitStageBufs {
+    DevBuf<HitRec> regs;
+    DevBuf<SqueezeSeg> segs;
+    DevBuf<unsigned char> reads;   // [counters (4 x 8 bytes) | HitRead[n]]
+    DevBuf<u128> a;
+    DevBuf<int64_t> sq_off;
+};
+
+// The hit stage of n reads: fills rs[i].regs / rs[i].n_a, sq_off (pinned, [n + 1]) and, with opt->with_cigar, the squeezed lists B.a.
+// path 0: the mapper's dispatch (both instantiations of hit_select_kernel, the host above max_chains); 1: the large instantiation
+// for every read of at most max_chains chains; 2: the host functions for every read (h holds the chain records then).
+// o: where the records of the reads left to the host are fetched from; null when h holds them already.
+// grid_cap > 0 bounds the blocks of every launch (the stage test makes a block take many reads).
+static int hits_from_chains(const mpn_map_opt *opt, int k, int n, const HitChainsDev &dc, HostChains &h, SeedChainOut *o, const int32_t *seq_len,
+                            const int32_t *d_len, const uint32_t *d_name_hash, const char *const *names, int path, int max_chains, int grid_cap,
+                            int n_threads, StreamLease &st, ReadState *rs, HitStageBufs &B, int64_t *&sq_off, WallTimer &wt) {
+    const bool gpu_hits = path != 2;
+    // Hits from chains.  hit_select_kernel (hit_kernels.h) makes them on the GPU from the chain records and leaves the squeeze
+    // segments there too; the host receives the selected hits (72 bytes each) and 24 bytes per read.  The chained anchors never
+    // leave HBM.  Reads with more chains than the kernel stages (and every read under path 2) take the host path: the same
+    // functions of hit.c on the downloaded records, their segments uploaded behind the kernel's.
+    Slot &SL = *tl_slot;
+    const int64_t n_chains_all = h.chain_off[(size_t)n];
+    if (SL.pin_segs.ensure((size_t)n_chains_all * sizeof(SqueezeSeg) + (size_t)(n + 1) * 8 + 64)) return -1;
+    sq_off = SL.pin_segs.as<int64_t>();                                     // [n + 1] start of every read's squeezed list
+    SqueezeSeg *h_segs = reinterpret_cast<SqueezeSeg *>(sq_off + n + 1);
+    const HitRead *h_reads = nullptr;
+    const HitRec *h_hregs = nullptr;
+    unsigned long long hit_counters[4] = {0, 0, 0, 0};
+    if (B.segs.alloc((size_t)n_chains_all + 1)) return -1;
+    if (gpu_hits && n_chains_all > 0) {
+        const size_t reads_bytes = 32 + (size_t)n * sizeof(HitRead);
+        if (B.regs.alloc((size_t)n_chains_all + 1) || B.reads.alloc(reads_bytes) || SL.pin_hits.ensure(reads_bytes + (size_t)n_chains_all * sizeof(HitRec) + 64)) return -1;
+        MPN_HIP_CHECK(hipMemsetAsync(B.reads.p, 0, 32, st));
+        HitSelParams hp;
+        hp.mask_level = opt->mask_level; hp.pri_ratio = opt->pri_ratio; hp.min_join_flank_ratio = opt->min_join_flank_ratio;
+        hp.min_diff = k * 2; hp.best_n = opt->best_n; hp.max_join_long = opt->max_join_long; hp.max_join_short = opt->max_join_short;
+        hp.min_join_flank_sc = opt->min_join_flank_sc; hp.min_cnt = opt->min_cnt; hp.with_cigar = opt->with_cigar; hp.seed_mix = wang32(opt->seed);
+        hp.max_chains = std::max(0, std::min(HIT_MAX_CHAINS, max_chains));
+        EvTimer evh(st);
+        // two instantiations: reads with few chains (nearly all reads of a random target set) need little LDS, so many waves per CU
+#define MPN_HIT_LAUNCH(NN, LO, GRID)                                                                                                      \
+        hipLaunchKernelGGL(hit_select_kernel<NN>, dim3((unsigned)std::max(1, std::min(n, grid_cap > 0 ? std::min(grid_cap, GRID) : GRID))), dim3(64), 0, st, hp, LO, n, dc.n_chain, \
+                           dc.u_pos, dc.b_pos, dc.u, dc.recs, d_len, \
+                           d_name_hash, B.regs.p, B.segs.p, reinterpret_cast<unsigned long long *>(B.reads.p),                \
+                           reinterpret_cast<HitRead *>(B.reads.p + 32))
+        if (path == 0) {
+            MPN_HIT_LAUNCH(HIT_SMALL_CHAINS, 0, 256 * 16);
+            MPN_HIT_LAUNCH(HIT_MAX_CHAINS, HIT_SMALL_CHAINS, 256 * 3);
+        } else {   // (the stage test: the large instantiation takes the reads of the small one too)
+            MPN_HIT_LAUNCH(HIT_MAX_CHAINS, 0, 256 * 3);
+        }
+#undef MPN_HIT_LAUNCH
+        MPN_HIP_CHECK(hipGetLastError());
+        evh.mark(62);
+        unsigned char *pin = SL.pin_hits.as<unsigned char>();
+        MPN_HIP_CHECK(hipMemcpyAsync(pin, B.reads.p, reads_bytes, hipMemcpyDeviceToHost, st));
+        MPN_HIP_CHECK(stream_sync(st));
+        evh.resolve();
+        memcpy(hit_counters, pin, 32);
+        h_reads = reinterpret_cast<const HitRead *>(pin + 32);
+        HitRec *dst = reinterpret_cast<HitRec *>(pin + ((reads_bytes + 15) & ~(size_t)15));
+        if (hit_counters[0]) MPN_HIP_CHECK(hipMemcpyAsync(dst, B.regs.p, (size_t)hit_counters[0] * sizeof(HitRec), hipMemcpyDeviceToHost, st));
+        if (hit_counters[2] && o && download_chain_records(*o, h, SL.pin_chain_u, st)) return -1;   // reads left to the host
+        MPN_HIP_CHECK(stream_sync(st));
+        h_hregs = dst;
+        g_stats[63] += (int64_t)hit_counters[2];
+    } else if (!gpu_hits) {   // every read with chains takes the host path
+        int64_t with_chains = 0;
+        for (int i = 0; i < n; ++i) with_chains += h.n_chain[i] > 0;
+        g_stats[63] += with_chains;
+    }
+    // (every pool thread stages the segments of its reads in a list of its own: a shared cursor is a hot cache line)
+    std::vector<std::vector<SqueezeSeg>> &stage = SL.seg_stage;
+    if ((int)stage.size() < std::max(1, n_threads)) stage.resize((size_t)std::max(1, n_threads));
+    for (auto &v : stage) v.clear();
+    parallel_for(n, n_threads, [&](int i, int slot) {
+        ReadState &S = rs[i];
+        const int nc = h.n_chain[i];
+        if (nc == 0) return;
+        const int qlen = seq_len[i];
+        if (h_reads && h_reads[i].n_regs >= 0) {
+            // the kernel's hits: the rest of the record follows from the first and last anchor (mm_reg_set_coor)
+            const HitRead &hr = h_reads[i];
+            const HitRec *src = h_hregs + hr.reg_pos;
+            S.regs.assign((size_t)hr.n_regs, Reg());
+            for (int k = 0; k < hr.n_regs; ++k) {
+                Reg &r = S.regs[(size_t)k];
+                const HitRec &x = src[k];
+                r.id = k; r.parent = x.parent; r.score = x.score; r.score0 = x.score0; r.hash = x.hash; r.cnt = x.cnt; r.as = x.as;
+                r.subsc = x.subsc; r.n_sub = x.n_sub; r.mlen = x.mlen; r.blen = x.blen;
+                r.fx = x.fx; r.fy = x.fy; r.lx = x.lx; r.ly = x.ly;
+                reg_set_coor(r, qlen);
+            }
+            if (hr.flags & 1) set_sam_pri(S.regs);
+            S.n_a = hr.n_a;
+            return;
+        }
+        CpuSect sect(g_cpu_on);
+        static thread_local std::vector<ChainIn> cin;
+        std::vector<int32_t> &order = tl_hs.order;
+        std::vector<int64_t> &src = tl_hs.src;
+        order.resize((size_t)nc); src.resize((size_t)nc); cin.resize((size_t)nc);
+        h.chain_order(i, order.data(), src.data());
+        for (int c = 0; c < nc; ++c) cin[c] = ChainIn{h.u_all[h.u_pos[i] + order[c]], h.rec_all + h.u_pos[i] + order[c], src[c]};
+        sect.lap(3);
+        uint32_t hash = names && names[i] ? x31_hash(names[i]) : 0;
+        hash ^= wang32((uint32_t)qlen) + wang32(opt->seed);
+        hash = wang32(hash);
+        gen_regs(hash, qlen, nc, cin.data(), S.regs);
+        set_parent(opt->mask_level, S.regs, opt->a * 2 + opt->b);
+        select_sub(opt->pri_ratio, k * 2, opt->best_n, S.regs);
+        sect.lap(4);
+        std::vector<SqueezeSeg> &segs = stage[(size_t)slot % stage.size()];
+        const size_t seg0 = segs.size();
+        S.n_a = squeeze_a(S.regs, i, h.b_pos[i], segs);
+        join_long(opt, qlen, S.regs, segs);
+        if (!opt->with_cigar) segs.resize(seg0);
+        sect.lap(5);
+    }, 1, 128);
+    int64_t n_host_segs = 0;
+    for (auto &v : stage) { if (!v.empty()) memcpy(h_segs + n_host_segs, v.data(), v.size() * sizeof(SqueezeSeg)); n_host_segs += (int64_t)v.size(); }
+    const int64_t n_dev_segs = (int64_t)hit_counters[1], n_segs = n_dev_segs + n_host_segs;
+    wt.stop_into(g_stats[19]);
+    sq_off[0] = 0;
+    for (int i = 0; i < n; ++i) sq_off[i + 1] = sq_off[i] + rs[i].n_a;
+    const int64_t n_sq = sq_off[n];
+    if (opt->with_cigar && n_sq > 0) {
+        if (B.a.alloc((size_t)n_sq) || B.sq_off.alloc((size_t)n + 1)) return -1;
+        MPN_HIP_CHECK(hipMemcpyAsync(B.sq_off.p, sq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+        // (the host's segments go behind the kernel's in the device list)
+        if (n_host_segs) MPN_HIP_CHECK(hipMemcpyAsync(B.segs.p + n_dev_segs, h_segs, (size_t)n_host_segs * sizeof(SqueezeSeg), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(anchor_squeeze_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_segs + 3) / 4, grid_cap > 0 ? std::min(grid_cap, 256 * 16) : 256 * 16))), dim3(256), 0, st,
+                           (const SqueezeSeg *)B.segs.p, (int)n_segs, dc.chained, (const int64_t *)B.sq_off.p, B.a.p);
+        MPN_HIP_CHECK(hipGetLastError());
+        g_stats[59] += n_sq;
+    }
+    return 0;
+}
+
 // One contiguous range [lo, hi) of the batch through the whole path, on the calling worker's stream and arena.
 // Fills rs[lo..hi) (the final hits of every read) and rep_len[lo..hi).
 static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *const *names, const char *seqs,
@@ -1580,127 +1726,19 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
     }
     g_stats[3] += h.chain_off[n];
     for (int i = 0; i < n; ++i) rep_len_all[lo + i] = h.rep_len[i];
-    // Hits from chains.  hit_select_kernel (hit_kernels.h) makes them on the GPU from the chain records and leaves the squeeze
-    // segments there too; the host receives the selected hits (72 bytes each) and 24 bytes per read.  The chained anchors never
-    // leave HBM.  Reads with more chains than the kernel stages (and every read under MPN_HOST_HITS=1) take the host path: the same
-    // functions of hit.c on the downloaded records, their segments uploaded behind the kernel's.
     Slot &SL = *tl_slot;
-    const int64_t n_chains_all = h.chain_off[(size_t)n];
-    if (SL.pin_segs.ensure((size_t)n_chains_all * sizeof(SqueezeSeg) + (size_t)(n + 1) * 8 + 64)) return -1;
-    int64_t *sq_off = SL.pin_segs.as<int64_t>();                                     // [n + 1] start of every read's squeezed list
-    SqueezeSeg *h_segs = reinterpret_cast<SqueezeSeg *>(sq_off + n + 1);
-    DevBuf<HitRec> d_hregs;
-    DevBuf<SqueezeSeg> d_hsegs;
-    DevBuf<unsigned char> d_hreads;   // [counters (4 x 8 bytes) | HitRead[n]]
-    const HitRead *h_reads = nullptr;
-    const HitRec *h_hregs = nullptr;
-    unsigned long long hit_counters[4] = {0, 0, 0, 0};
-    if (d_hsegs.alloc((size_t)n_chains_all + 1)) return -1;
-    if (gpu_hits && n_chains_all > 0) {
-        const size_t reads_bytes = 32 + (size_t)n * sizeof(HitRead);
-        if (d_hregs.alloc((size_t)n_chains_all + 1) || d_hreads.alloc(reads_bytes) || SL.pin_hits.ensure(reads_bytes + (size_t)n_chains_all * sizeof(HitRec) + 64)) return -1;
-        MPN_HIP_CHECK(hipMemsetAsync(d_hreads.p, 0, 32, st));
-        HitSelParams hp;
-        hp.mask_level = opt->mask_level; hp.pri_ratio = opt->pri_ratio; hp.min_join_flank_ratio = opt->min_join_flank_ratio;
-        hp.min_diff = idx->k * 2; hp.best_n = opt->best_n; hp.max_join_long = opt->max_join_long; hp.max_join_short = opt->max_join_short;
-        hp.min_join_flank_sc = opt->min_join_flank_sc; hp.min_cnt = opt->min_cnt; hp.with_cigar = opt->with_cigar; hp.seed_mix = wang32(opt->seed);
+    HitStageBufs hb;
+    int64_t *sq_off = nullptr;   // [n + 1] start of every read's squeezed list
+    {
         static const int hit_max = []() { const char *e = getenv("MPN_HIT_MAX_CHAINS"); return e ? std::max(0, std::min(HIT_MAX_CHAINS, atoi(e))) : HIT_MAX_CHAINS; }();
-        hp.max_chains = hit_max;
-        EvTimer evh(st);
-        // two instantiations: reads with few chains (nearly all reads of a random target set) need little LDS, so many waves per CU
-#define MPN_HIT_LAUNCH(NN, LO, GRID)                                                                                                      \
-        hipLaunchKernelGGL(hit_select_kernel<NN>, dim3((unsigned)std::max(1, std::min(n, GRID))), dim3(64), 0, st, hp, LO, n, (const int32_t *)o.n_chain.p, \
-                           (const int64_t *)o.u_pos.p, (const int64_t *)o.b_pos.p, (const uint64_t *)o.u_compact.p, (const ChainRec *)o.recs.p, d_len.p, \
-                           d_name_hash_all + lo, d_hregs.p, d_hsegs.p, reinterpret_cast<unsigned long long *>(d_hreads.p),                \
-                           reinterpret_cast<HitRead *>(d_hreads.p + 32))
-        MPN_HIT_LAUNCH(HIT_SMALL_CHAINS, 0, 256 * 16);
-        MPN_HIT_LAUNCH(HIT_MAX_CHAINS, HIT_SMALL_CHAINS, 256 * 3);
-#undef MPN_HIT_LAUNCH
-        MPN_HIP_CHECK(hipGetLastError());
-        evh.mark(62);
-        unsigned char *pin = SL.pin_hits.as<unsigned char>();
-        MPN_HIP_CHECK(hipMemcpyAsync(pin, d_hreads.p, reads_bytes, hipMemcpyDeviceToHost, st));
-        MPN_HIP_CHECK(stream_sync(st));
-        evh.resolve();
-        memcpy(hit_counters, pin, 32);
-        h_reads = reinterpret_cast<const HitRead *>(pin + 32);
-        HitRec *dst = reinterpret_cast<HitRec *>(pin + ((reads_bytes + 15) & ~(size_t)15));
-        if (hit_counters[0]) MPN_HIP_CHECK(hipMemcpyAsync(dst, d_hregs.p, (size_t)hit_counters[0] * sizeof(HitRec), hipMemcpyDeviceToHost, st));
-        if (hit_counters[2] && download_chain_records(o, h, SL.pin_chain_u, st)) return -1;   // reads left to the host
-        MPN_HIP_CHECK(stream_sync(st));
-        h_hregs = dst;
-        g_stats[63] += (int64_t)hit_counters[2];
-    } else if (!gpu_hits) {   // MPN_HOST_HITS=1: every read with chains takes the host path
-        int64_t with_chains = 0;
-        for (int i = 0; i < n; ++i) with_chains += h.n_chain[i] > 0;
-        g_stats[63] += with_chains;
+        const HitChainsDev dc{o.n_chain.p, o.u_pos.p, o.b_pos.p, o.u_compact.p, o.recs.p, o.chained.p};
+        if (hits_from_chains(opt, idx->k, n, dc, h, &o, seq_len, d_len.p, d_name_hash_all + lo, names ? names + lo : nullptr, gpu_hits ? 0 : 2, hit_max, 0,
+                             n_threads, st, rs, hb, sq_off, wt))
+            return -1;
     }
-    // (every pool thread stages the segments of its reads in a list of its own: a shared cursor is a hot cache line)
-    std::vector<std::vector<SqueezeSeg>> &stage = SL.seg_stage;
-    if ((int)stage.size() < std::max(1, n_threads)) stage.resize((size_t)std::max(1, n_threads));
-    for (auto &v : stage) v.clear();
-    parallel_for(n, n_threads, [&](int i, int slot) {
-        ReadState &S = rs[i];
-        const int nc = h.n_chain[i];
-        if (nc == 0) return;
-        const int qlen = seq_len[i];
-        if (h_reads && h_reads[i].n_regs >= 0) {
-            // the kernel's hits: the rest of the record follows from the first and last anchor (mm_reg_set_coor)
-            const HitRead &hr = h_reads[i];
-            const HitRec *src = h_hregs + hr.reg_pos;
-            S.regs.assign((size_t)hr.n_regs, Reg());
-            for (int k = 0; k < hr.n_regs; ++k) {
-                Reg &r = S.regs[(size_t)k];
-                const HitRec &x = src[k];
-                r.id = k; r.parent = x.parent; r.score = x.score; r.score0 = x.score0; r.hash = x.hash; r.cnt = x.cnt; r.as = x.as;
-                r.subsc = x.subsc; r.n_sub = x.n_sub; r.mlen = x.mlen; r.blen = x.blen;
-                r.fx = x.fx; r.fy = x.fy; r.lx = x.lx; r.ly = x.ly;
-                reg_set_coor(r, qlen);
-            }
-            if (hr.flags & 1) set_sam_pri(S.regs);
-            S.n_a = hr.n_a;
-            return;
-        }
-        CpuSect sect(g_cpu_on);
-        static thread_local std::vector<ChainIn> cin;
-        std::vector<int32_t> &order = tl_hs.order;
-        std::vector<int64_t> &src = tl_hs.src;
-        order.resize((size_t)nc); src.resize((size_t)nc); cin.resize((size_t)nc);
-        h.chain_order(i, order.data(), src.data());
-        for (int c = 0; c < nc; ++c) cin[c] = ChainIn{h.u_all[h.u_pos[i] + order[c]], h.rec_all + h.u_pos[i] + order[c], src[c]};
-        sect.lap(3);
-        uint32_t hash = names && names[lo + i] ? x31_hash(names[lo + i]) : 0;
-        hash ^= wang32((uint32_t)qlen) + wang32(opt->seed);
-        hash = wang32(hash);
-        gen_regs(hash, qlen, nc, cin.data(), S.regs);
-        set_parent(opt->mask_level, S.regs, opt->a * 2 + opt->b);
-        select_sub(opt->pri_ratio, idx->k * 2, opt->best_n, S.regs);
-        sect.lap(4);
-        std::vector<SqueezeSeg> &segs = stage[(size_t)slot % stage.size()];
-        const size_t seg0 = segs.size();
-        S.n_a = squeeze_a(S.regs, i, h.b_pos[i], segs);
-        join_long(opt, qlen, S.regs, segs);
-        if (!opt->with_cigar) segs.resize(seg0);
-        sect.lap(5);
-    }, 1, 128);
-    int64_t n_host_segs = 0;
-    for (auto &v : stage) { if (!v.empty()) memcpy(h_segs + n_host_segs, v.data(), v.size() * sizeof(SqueezeSeg)); n_host_segs += (int64_t)v.size(); }
-    const int64_t n_dev_segs = (int64_t)hit_counters[1], n_segs = n_dev_segs + n_host_segs;
-    wt.stop_into(g_stats[19]);
-    sq_off[0] = 0;
-    for (int i = 0; i < n; ++i) sq_off[i + 1] = sq_off[i] + rs[i].n_a;
     const int64_t n_sq = sq_off[n];
     if (opt->with_cigar && n_sq > 0) {
-        DevBuf<u128> d_a;
-        DevBuf<int64_t> d_sq_off;
-        if (d_a.alloc((size_t)n_sq) || d_sq_off.alloc((size_t)n + 1)) return -1;
-        MPN_HIP_CHECK(hipMemcpyAsync(d_sq_off.p, sq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-        // (the host's segments go behind the kernel's in the device list)
-        if (n_host_segs) MPN_HIP_CHECK(hipMemcpyAsync(d_hsegs.p + n_dev_segs, h_segs, (size_t)n_host_segs * sizeof(SqueezeSeg), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(anchor_squeeze_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_segs + 3) / 4, 256 * 16))), dim3(256), 0, st,
-                           (const SqueezeSeg *)d_hsegs.p, (int)n_segs, (const u128 *)o.chained.p, (const int64_t *)d_sq_off.p, d_a.p);
-        MPN_HIP_CHECK(hipGetLastError());
-        g_stats[59] += n_sq;
+        DevBuf<u128> &d_a = hb.a;
         PlanOpt po;
         po.bw = opt->bw; po.bw15 = (int)(opt->bw * 1.5 + 1.); po.min_chain_score = opt->min_chain_score; po.max_gap = opt->max_gap;
         po.min_cnt = opt->min_cnt; po.a = opt->a; po.q = opt->q; po.e = opt->e; po.zdrop = opt->zdrop; po.zdrop_inv = opt->zdrop_inv;
@@ -2822,6 +2860,105 @@ extern "C" int mpn_aln_finish_batch(const mpn_map_opt *opt, int32_t n, const uin
         int32_t *o = out8 + (size_t)i * 8;
         o[0] = f.n_cigar; o[1] = f.qshift; o[2] = f.tshift; o[3] = f.blen; o[4] = f.mlen; o[5] = f.n_ambi; o[6] = f.dp_max; o[7] = f.pad;
         if (f.n_cigar) memcpy(cigar_out + cig_off[i], cig_pad.data() + cig_off[i], (size_t)f.n_cigar * 4);
+    }
+    return 0;
+}
+
+// stage entry point for the tests of the hit stage: hit_select_kernel, the host functions and anchor_squeeze_kernel, run by
+// hits_from_chains as the mapper runs them, on arbitrary chains.  Arrays are CSR over reads; chains and anchors in pool order
+// (chain c's anchors follow those of chains 0..c-1 of its read).  hits: 15 words per hit, in hit order: fx, fy, lx, ly, score,
+// score0, cnt, as, parent, subsc, n_sub, mlen, blen, hash, sam_pri; room for one hit per chain.  sq_anchors (with opt->with_cigar):
+// the squeezed lists as (x, y) pairs, read after read; room for every anchor.
+extern "C" int mpn_hit_select_batch(const mpn_map_opt *opt, int32_t k, int32_t n, const int32_t *q_len, const char *const *names,
+                                    const int64_t *chain_off, const uint64_t *u, const uint64_t *fx, const uint64_t *fy, const uint64_t *lx,
+                                    const uint64_t *ly, const int32_t *mlen, const int32_t *blen, const int64_t *anchor_off, const uint64_t *anchors,
+                                    int32_t path, int32_t max_chains, int32_t grid_cap, int32_t *n_regs, int32_t *n_a, int64_t *hits,
+                                    uint64_t *sq_anchors) {
+    std::lock_guard<std::mutex> call_guard(g_call_mu);
+    if (n < 0) { set_error("mpn_hit_select_batch: negative count"); return -1; }
+    if (n == 0) return 0;
+    if (!opt || !q_len || !chain_off || !anchor_off || !n_regs || !n_a || !hits || (opt->with_cigar && !sq_anchors)) {
+        set_error("mpn_hit_select_batch: options or an array missing"); return -1;
+    }
+    if (path < 0 || path > 2 || max_chains < 0 || max_chains > HIT_MAX_CHAINS || grid_cap < 0 || k < 1) {
+        set_error("mpn_hit_select_batch: path, max_chains, grid_cap or k out of range"); return -1;
+    }
+    // everything is checked here, before any launch
+    if (chain_off[0] != 0 || anchor_off[0] != 0) { set_error("mpn_hit_select_batch: offsets do not start at 0"); return -1; }
+    for (int i = 0; i < n; ++i) {
+        if (chain_off[i + 1] < chain_off[i] || anchor_off[i + 1] < anchor_off[i] || chain_off[i + 1] - chain_off[i] > 0x3fffffff ||
+            anchor_off[i + 1] - anchor_off[i] > 0x3fffffff) {
+            set_error("mpn_hit_select_batch: read %d: offsets out of order", i); return -1;
+        }
+        if (q_len[i] <= 0) { set_error("mpn_hit_select_batch: read %d: no length", i); return -1; }
+    }
+    const int64_t n_chains = chain_off[n], n_anch = anchor_off[n];
+    if (n_chains > 0 && (!u || !fx || !fy || !lx || !ly || !mlen || !blen || !anchors)) { set_error("mpn_hit_select_batch: a chain array missing"); return -1; }
+    std::vector<ChainRec> recs((size_t)n_chains + 1);
+    {
+        std::vector<uint64_t> firsts;
+        for (int i = 0; i < n; ++i) {
+            int64_t a = anchor_off[i];
+            firsts.clear();
+            for (int64_t c = chain_off[i]; c < chain_off[i + 1]; ++c) {
+                const int32_t cnt = (int32_t)u[c];
+                if (cnt < 1 || a + cnt > anchor_off[i + 1]) { set_error("mpn_hit_select_batch: read %d: a chain without anchors, or more than the read has", i); return -1; }
+                const uint64_t *f = anchors + 2 * a, *l = anchors + 2 * (a + cnt - 1);
+                if (fx[c] != f[0] || fy[c] != f[1] || lx[c] != l[0] || ly[c] != l[1]) {
+                    set_error("mpn_hit_select_batch: read %d: a chain record differs from its first or last anchor", i); return -1;
+                }
+                recs[(size_t)c] = ChainRec{fx[c], fy[c], lx[c], ly[c], mlen[c], blen[c]};
+                firsts.push_back(fx[c]);
+                a += cnt;
+            }
+            if (a != anchor_off[i + 1]) { set_error("mpn_hit_select_batch: read %d: the chains' counts do not add up to its anchors", i); return -1; }
+            std::sort(firsts.begin(), firsts.end());
+            if (std::adjacent_find(firsts.begin(), firsts.end()) != firsts.end()) { set_error("mpn_hit_select_batch: read %d: two chains start at the same anchor", i); return -1; }
+        }
+    }
+    HostChains h;
+    h.n_chain.resize((size_t)n); h.u_pos.resize((size_t)n); h.b_pos.resize((size_t)n); h.rep_len.assign((size_t)n, 0);
+    h.chain_off.assign(chain_off, chain_off + n + 1);
+    std::vector<uint32_t> name_hash((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        h.n_chain[(size_t)i] = (int32_t)(chain_off[i + 1] - chain_off[i]); h.u_pos[(size_t)i] = chain_off[i]; h.b_pos[(size_t)i] = anchor_off[i];
+        name_hash[(size_t)i] = names && names[i] ? x31_hash(names[i]) : 0;
+    }
+    const uint64_t u_none = 0;
+    h.u_all = n_chains ? u : &u_none; h.rec_all = recs.data(); h.n_pool_chains = n_chains;
+    StreamLease st((hipStream_t)0);
+    DevBuf<int32_t> d_n_chain, d_len;
+    DevBuf<int64_t> d_u_pos, d_b_pos;
+    DevBuf<uint64_t> d_u;
+    DevBuf<ChainRec> d_recs;
+    DevBuf<u128> d_chained;
+    DevBuf<uint32_t> d_name_hash;
+    if (d_n_chain.upload(h.n_chain.data(), (size_t)n, st) || d_len.upload(q_len, (size_t)n, st) || d_u_pos.upload(h.u_pos.data(), (size_t)n, st) ||
+        d_b_pos.upload(h.b_pos.data(), (size_t)n, st) || d_u.upload(h.u_all, (size_t)std::max<int64_t>(1, n_chains), st) ||
+        d_recs.upload(recs.data(), recs.size(), st) || d_chained.upload(reinterpret_cast<const u128 *>(n_anch ? anchors : &u_none), (size_t)n_anch, st) ||
+        d_name_hash.upload(name_hash.data(), (size_t)n, st))
+        return -1;
+    std::vector<ReadState> rs((size_t)n);
+    HitStageBufs hb;
+    int64_t *sq_off = nullptr;
+    WallTimer wt;
+    const HitChainsDev dc{d_n_chain.p, d_u_pos.p, d_b_pos.p, d_u.p, d_recs.p, d_chained.p};
+    if (hits_from_chains(opt, k, n, dc, h, nullptr, q_len, d_len.p, d_name_hash.p, names, path, max_chains ? max_chains : HIT_MAX_CHAINS, grid_cap, 1, st,
+                         rs.data(), hb, sq_off, wt))
+        return -1;
+    if (sq_off[n] > n_anch) { set_error("mpn_hit_select_batch: the squeezed lists hold more anchors than the reads have"); return -1; }
+    if (opt->with_cigar && sq_off[n] > 0) MPN_HIP_CHECK(hipMemcpyAsync(sq_anchors, hb.a.p, (size_t)sq_off[n] * sizeof(u128), hipMemcpyDeviceToHost, st));
+    MPN_HIP_CHECK(stream_sync(st));
+    int64_t w = 0;
+    for (int i = 0; i < n; ++i) {
+        const ReadState &S = rs[(size_t)i];
+        if ((int64_t)S.regs.size() > chain_off[i + 1] - chain_off[i]) { set_error("mpn_hit_select_batch: read %d: more hits than chains", i); return -1; }
+        n_regs[i] = (int32_t)S.regs.size(); n_a[i] = S.n_a;
+        for (const Reg &r : S.regs) {
+            int64_t *o = hits + 15 * w++;
+            o[0] = (int64_t)r.fx; o[1] = (int64_t)r.fy; o[2] = (int64_t)r.lx; o[3] = (int64_t)r.ly; o[4] = r.score; o[5] = r.score0; o[6] = r.cnt; o[7] = r.as;
+            o[8] = r.parent; o[9] = r.subsc; o[10] = r.n_sub; o[11] = r.mlen; o[12] = r.blen; o[13] = (int64_t)r.hash; o[14] = (int64_t)r.sam_pri;
+        }
     }
     return 0;
 }

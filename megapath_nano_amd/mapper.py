@@ -128,6 +128,9 @@ def _bind():
         lib.mpn_aln_tags_batch.restype = ct.c_int
         lib.mpn_aln_finish_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, P, P, P, P, P, P, P, P, P, P, P, P, P, ct.c_int32, P, P]
         lib.mpn_aln_finish_batch.restype = ct.c_int
+        lib.mpn_hit_select_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, ct.c_int32, P, ct.POINTER(ct.c_char_p), P, P, P, P, P, P, P, P, P, P,
+                                             ct.c_int32, ct.c_int32, ct.c_int32, P, P, P, P]
+        lib.mpn_hit_select_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
         lib.mpn_map_last_stats_ex.argtypes = [P, ct.c_int32]
@@ -694,6 +697,37 @@ def aln_finish_batch(opt, queries, q_ivals, revs, targets, t_starts, cigars, for
         d['cigar'] = fixed[coff[i]:coff[i] + d['n_cigar']].tolist()
         res.append(d)
     return res
+
+
+HIT_KEYS = ('fx', 'fy', 'lx', 'ly', 'score', 'score0', 'cnt', 'as', 'parent', 'subsc', 'n_sub', 'mlen', 'blen', 'hash', 'sam_pri')
+
+
+def hit_select_batch(opt, k, q_len, names, chain_off, u, recs, anchor_off, anchors, path=0, max_chains=0, grid_cap=0):
+    """The hit stage on arbitrary chains (mpn_hit_select_batch).  CSR over reads: chain_off[n + 1], anchor_off[n + 1]; per chain in
+    pool order u (score << 32 | cnt) and recs = (fx, fy, lx, ly, mlen, blen) arrays; anchors: uint64 [total, 2] (x, y).  path: 0 the
+    mapper's dispatch, 1 the large kernel instantiation for all, 2 the host functions; max_chains 0 = 384; grid_cap 0 = the mapper's
+    grids.  -> (n_regs int32[n], n_a int32[n], hits int64 [sum n_regs, 15] in HIT_KEYS order (fx..ly and hash as unsigned bit
+    patterns), squeezed anchors uint64 [sum n_a, 2] or None without opt.with_cigar)."""
+    lib = _bind()
+    n = len(q_len)
+    c = lambda v, t: np.ascontiguousarray(v, dtype=t)  # noqa: E731
+    q_len, chain_off, anchor_off, u = c(q_len, np.int32), c(chain_off, np.int64), c(anchor_off, np.int64), c(u, np.uint64)
+    fx, fy, lx, ly = (c(r, np.uint64) for r in recs[:4])
+    mlen, blen = c(recs[4], np.int32), c(recs[5], np.int32)
+    anchors = c(anchors, np.uint64).reshape(-1, 2)
+    assert len(chain_off) == n + 1 and len(anchor_off) == n + 1 and len(names) == n
+    n_chains, n_anch = int(chain_off[-1]) if n else 0, int(anchor_off[-1]) if n else 0
+    assert all(len(x) == n_chains for x in (u, fx, fy, lx, ly, mlen, blen)) and len(anchors) == n_anch
+    cnames = (ct.c_char_p * max(1, n))(*[(nm.encode() if isinstance(nm, str) else nm) for nm in names])
+    n_regs, n_a = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    hits = np.zeros((n_chains + 1, 15), dtype=np.int64)
+    sq = np.zeros((n_anch + 1, 2), dtype=np.uint64)
+    rc = lib.mpn_hit_select_batch(ct.byref(opt), int(k), n, q_len.ctypes.data, cnames, chain_off.ctypes.data, u.ctypes.data, fx.ctypes.data,
+                                  fy.ctypes.data, lx.ctypes.data, ly.ctypes.data, mlen.ctypes.data, blen.ctypes.data, anchor_off.ctypes.data,
+                                  anchors.ctypes.data, int(path), int(max_chains), int(grid_cap), n_regs.ctypes.data, n_a.ctypes.data,
+                                  hits.ctypes.data, sq.ctypes.data)
+    _ffi.check(rc, 'mpn_hit_select_batch')
+    return n_regs, n_a, hits[:int(n_regs.sum())], (sq[:int(n_a.sum())] if opt.with_cigar else None)
 
 
 STAT_NAMES = {0: 'bases', 1: 'minimizers', 2: 'anchors', 3: 'chains', 4: 'dp_jobs', 5: 'dp_cells', 6: 'alignments',

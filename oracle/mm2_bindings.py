@@ -79,6 +79,9 @@ def lib():
                                 ct.c_int8, ct.c_int8, ct.c_int8, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.POINTER(Ez)]
         L.mmo_fix_update.argtypes = [ct.c_void_p, ct.c_int32, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p]
         L.mmo_fix_update.restype = None
+        L.mmo_hits_from_chains.argtypes = [ct.POINTER(Opt), ct.c_int, ct.c_char_p, ct.c_int32, ct.c_int32, ct.c_void_p, ct.c_void_p,
+                                           ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32)]
+        L.mmo_hits_from_chains.restype = ct.POINTER(Reg)
         _lib = L
     return _lib
 
@@ -248,3 +251,18 @@ def fix_update(cigar, q, t, a=2, b=4, sc_ambi=1, q_=4, e=2):
     d = {k: int(out[j]) for j, k in enumerate(('n_cigar', 'qshift', 'tshift', 'blen', 'mlen', 'n_ambi', 'dp_max'))}
     d['cigar'] = cig[:d['n_cigar']].tolist()
     return d
+
+
+def hits_from_chains(opt, k, name, qlen, u, a):
+    """gen_regs -> set_parent -> select_sub -> join_long of the oracle on one read's chains: u uint64[n_u] (score << 32 | cnt), a uint64
+    [n, 2] their anchors back to back, chains in the order of their first anchors -> (list of reg dicts, squeezed anchors uint64 [n_a, 2])"""
+    u = np.ascontiguousarray(u, dtype=np.uint64)
+    a = np.array(a, dtype=np.uint64).reshape(-1, 2)
+    a = np.ascontiguousarray(np.concatenate([a, np.zeros((1, 2), np.uint64)]))
+    n, n_a = ct.c_int32(), ct.c_int32()
+    regs = lib().mmo_hits_from_chains(ct.byref(opt), k, name.encode() if name is not None else None, qlen, len(u), u.ctypes.data, a.ctypes.data,
+                                      ct.byref(n), ct.byref(n_a))
+    out = [{f: getattr(regs[i], f) for f, _ in Reg._fields_ if f != 'cigar'} for i in range(n.value)]
+    if regs:
+        lib().mmo_free(regs)
+    return out, a[:n_a.value].copy()

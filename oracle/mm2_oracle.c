@@ -1544,6 +1544,28 @@ mmo_reg *mmo_map_read(const mmo_idx *mi, const mmo_opt *o, const char *name, con
     return regs;
 }
 
+/* The statics above on a caller's chains: what mmo_map_read does between mmo_chain and the base-level alignment. */
+mmo_reg *mmo_hits_from_chains(const mmo_opt *o, int k, const char *name, int32_t qlen, int32_t n_u, const uint64_t *u, mm128 *a,
+                              int32_t *n_regs_, int32_t *n_a_)
+{
+    int32_t n_regs = n_u, i, n_a = 0;
+    uint32_t hash;
+    mmo_reg *regs;
+    *n_regs_ = 0, *n_a_ = 0;
+    if (n_u <= 0 || qlen <= 0) return 0;
+    hash = name ? x31_hash(name) : 0;
+    hash ^= wang32((uint32_t)qlen) + wang32(o->seed);
+    hash = wang32(hash);
+    regs = gen_regs(hash, qlen, n_u, u, a);
+    set_parent(o->mask_level, n_regs, regs, o->a * 2 + o->b);
+    select_sub(o->pri_ratio, k * 2, o->best_n, &n_regs, regs);
+    for (i = 0; i < n_regs; ++i) n_a += regs[i].cnt;
+    if (n_regs < 2) squeeze_a(n_regs, regs, a); /* (join_long returns before its own squeeze; align_skeleton's does it then) */
+    join_long(o, qlen, &n_regs, regs, a);
+    *n_regs_ = n_regs, *n_a_ = n_a;
+    return regs;
+}
+
 /* ---- split index: minimap2 -I parts + --split-prefix (map.c: mm_split_merge / merge_hits), restated ------------------
  * Every part is mapped on its own (its own mid-occ cut-off); the hits of a read from all parts are then pooled with the
  * target ids shifted to the concatenated target list, the sub-optimal bookkeeping (subsc, n_sub, dp_max2) is cleared,

@@ -112,6 +112,14 @@ void mmo_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *target, 
 void mmo_fix_update(uint32_t *cigar, int32_t n_cigar, const uint8_t *qseq, const uint8_t *tseq, int a, int b, int sc_ambi, int q, int e,
                     int32_t *out8);
 
+/* the static gen_regs -> set_parent -> select_sub -> join_long of the mapper on a caller's chains, with the hash built as
+ * mmo_map_read builds it (min_diff = 2k): u[n_u] = score<<32|cnt and the chains' anchors a[] back to back, chains in the order of
+ * their first anchors.  Returns the hits (malloc'd, no CIGARs: release with mmo_free) and *n_regs; a[] is squeezed in place to
+ * its first *n_a anchors as join_long leaves it (LONG_JOIN marks included).  A read that leaves select_sub with fewer than two
+ * hits, where join_long returns before its squeeze_a, gets the squeeze_a that align_skeleton starts with instead. */
+mmo_reg *mmo_hits_from_chains(const mmo_opt *o, int k, const char *name, int32_t qlen, int32_t n_u, const uint64_t *u, mm128 *a,
+                              int32_t *n_regs, int32_t *n_a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,8 +108,8 @@ def test_saturated_seed_space_matches_oracle(libmpn, oracle_built):
 def test_strain_rich_target_set_matches_oracle(libmpn, oracle_built):
     """The regime of the bench headline in small: 40 assemblies of each of 3 community genomes at 97-99.9 % identity beside 30
     unrelated genomes (150 x 600 kb), `-N 50 -p 1`: every read has dozens of loci, i.e. dozens of chain ends (the backtrack runs a
-    lane per end), dozens of chains per read in hit_select_kernel (rank sorts, secondaries within the score window, long joins),
-    many alignments per read.  PAF identical to the oracle for 120 reads incl. long ones; then the same target set as THREE index
+    lane per end), dozens of chains per read in hit_select_kernel (rank sorts, secondaries within the score window; nothing here counts a long
+    join: mm_join_long and the edges of the selection have a stage test of their own, test_hit_select_gpu.py), many alignments per read.  PAF identical to the oracle for 120 reads incl. long ones; then the same target set as THREE index
     parts through mpn_map_batch_parts against the oracle's split-index merge."""
     import torch
     from megapath_nano_amd import mapper, synth
