@@ -24,9 +24,15 @@
  *   mpn_second_best_by_read  bin/megapath_nano.py:244-310: align_list_to_best_align_list); the largest score of a read off its best
  *                            row's assembly (:2553-2593: step_unique_alignment).  The random numbers are an input.
  *
+ *   mpn_good_rows       the best row per (read, unit) and, of those, the rows that reach a fraction of their read's best score: the
+ *                       reference's good_align_list (bin/megapath_nano.py:642-663), the first half of
+ *                       align_list_to_align_stat_by_sequence_id (:591) and the best row per read of step_assembly_selection (:1459)
+ *   mpn_sum_by_key      the grouped integer sums of summary_stat_1 (:485-493) per assembly or per (assembly, sequence)
+ *
  * All run on the GPU (csrc/interval_kernels.hip: a stable LSD radix sort of 128-bit keys, three-phase sweeps and segmented scans over
  * the sorted list); all pointers are HOST pointers, results are exact integers -- and, in mpn_pick_weighted, float64 values that one
- * IEEE division and one multiplication define.  Return 0, or a negative error (mpn_last_error()).
+ * IEEE division and one multiplication define; mpn_good_rows compares through one IEEE float64 product.  Return 0, or a negative
+ * error (mpn_last_error()).
  */
 #ifndef MPN_ABUNDANCE_H
 #define MPN_ABUNDANCE_H
@@ -126,6 +132,29 @@ int mpn_pick_weighted(int64_t m, const int32_t *read, const int64_t *weight, con
  * int64 but the smallest one.  A record outside the domain returns -2 before anything is written. */
 int mpn_second_best_by_read(int64_t n, const int32_t *read, const int32_t *assembly, const int64_t *score,
                             int32_t n_reads, const int32_t *excluded, int64_t *second);
+
+/* The good alignments of every read (the reference's good_align_list, bin/megapath_nano.py:642-663; with one unit and no threshold
+ * the `sort_values(read, score, tiebreaker).drop_duplicates(read, keep='last')` of :1287 and :1459).  Row i is an alignment of
+ * read[i] in [0, n_reads) on unit[i] in [0, n_units) -- an assembly, a sequence, or the single unit 0 -- with |score[i]| < 2^53 and
+ * a finite tiebreak[i] (-0.0 counts as 0.0).
+ *   - per (read, unit) the row with the largest (score, tiebreak) is kept, the LAST in input order among equal ones;
+ *   - read_best[r], r < n_reads = the largest kept score of read r, 0 for a read without rows;
+ *   - a kept row is good iff use_threshold == 0 or (double)score >= (double)read_best * threshold: ONE IEEE float64 product (both
+ *     conversions are exact in this domain), as pandas evaluates `alignment_score >= best_alignment_score * pct`.
+ * good_row[0..*n_good), room for n entries: the good rows' indices, ordered by (read, unit).  n < 2^31; threshold is finite (it is
+ * checked whether or not it is used).  Bad arguments or a record outside the domain return -2 before anything is written or
+ * launched. */
+int mpn_good_rows(int64_t n, const int32_t *read, const int32_t *unit, const int64_t *score, const double *tiebreak,
+                  int32_t n_reads, int32_t n_units, int32_t use_threshold, double threshold,
+                  int64_t *good_row, int64_t *n_good, int64_t *read_best);
+
+/* The grouped sums of the reference's summary_stat_1 (bin/megapath_nano.py:485-493).  cols: n_cols (1..6) arrays of n values, one
+ * after another, each |value| < 2^32; row i belongs to key[i] in [0, n_keys).  count[k] = the number of rows of key k;
+ * sums[c * n_keys + k] = the sum of column c over them; keys without rows get 0.  n < 2^31, so no sum leaves int64.  A segmented
+ * scan over the rows sorted by key: no atomic touches the output, and the cost does not depend on how the rows spread over the keys.
+ * Bad arguments or a record outside the domain return -2 before anything is written or launched. */
+int mpn_sum_by_key(int64_t n, const int32_t *key, int32_t n_keys, int32_t n_cols, const int64_t *cols,
+                   int64_t *count, int64_t *sums);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,14 @@ device half of `unique_alignment` (step_unique_alignment, :2553-2593).  `short_a
 (:2330-2422 with its two draws) and `combine_with_human_and_decoy` (:2425-2446) complete the steps that stand on it.  The random
 numbers come from the host, one `rng()` per candidate of a read with several, in the order of (read_id, assembly_id): the number
 and order of the calls are the reference's.
+
+From species to assemblies: `step_assembly_selection` (the reference's :1400-1476, on by default) is `assembly_selection`.  Under it
+`good_align_list` (:642-663: the best row per (read, assembly), of those the rows that reach good_align_threshold percent of their
+read's best score -- one float64 product, as pandas forms it), `best_align_per_read` (the sort_values / drop_duplicates idiom of
+:1287 and :1459) and `align_stat_by_sequence_id` (:585-639) all stand on mpn_good_rows -- the same sort and scans as
+mpn_best_candidates with another compaction -- and the grouped sums of summary_stat_1 (:485-493) on mpn_sum_by_key, a segmented scan
+that carries a count and six sums and puts no atomic on its output; `host_good_rows` and `host_sum_by_key` are the numpy
+statements.  The summed tiebreaker, the one float sum, is np.bincount on the host either way.
 """
 import ctypes as ct
 import math
@@ -73,6 +81,10 @@ def _lib():
         lib.mpn_pick_weighted.restype = ct.c_int
         lib.mpn_second_best_by_read.argtypes = [ct.c_int64, P, P, P, ct.c_int32, P, P]
         lib.mpn_second_best_by_read.restype = ct.c_int
+        lib.mpn_good_rows.argtypes = [ct.c_int64, P, P, P, P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_double, P, P, P]
+        lib.mpn_good_rows.restype = ct.c_int
+        lib.mpn_sum_by_key.argtypes = [ct.c_int64, P, ct.c_int32, ct.c_int32, P, P, P]
+        lib.mpn_sum_by_key.restype = ct.c_int
         _bound = True
     return lib
 
@@ -163,42 +175,34 @@ def covered_bp_by_assembly(rows, noise_bed=None, device=None):
     return dict(zip(asm, both - noise))
 
 
-def align_stat_by_assembly_id(align_list, assembly_length, assembly_tax=None, noise_bed=None, device=None):
-    """align_list: the Align() table.  assembly_length: DataFrame(assembly_id, assembly_length); assembly_tax (optional):
-    DataFrame(assembly_id, tax_id, species_tax_id, genus_tax_id, genus_height); noise_bed (optional): DataFrame(sequence_id,
-    start, end, assembly_id) as the reference's noise BEDs carry them (name column = assembly_id).  -> DataFrame, one row per
-    assembly."""
-    best = best_per_read_and_assembly(align_list)
-    asm, ac = _codes(best['assembly_id'])
-    n = len(asm)
+def _float_sums(code, n, cols):
+    """count and integer sums per code through np.bincount (float64 additions: exact while the sums stay below 2^53)"""
+    return (np.bincount(code, minlength=n).astype(np.int64),
+            [np.bincount(code, weights=np.asarray(v, dtype=np.float64), minlength=n).astype(np.int64) for v in cols])
 
-    def total(values):
-        return np.bincount(ac, weights=np.asarray(values, dtype=np.float64), minlength=n)
 
+def _summary_stat_1(best, code, n, sums):
+    """The grouped sums of the reference's summary_stat_1 (megapath_nano.py:485-493) as columns, in its order.  sums(code, n,
+    cols) -> count, [sum per column]: _float_sums, or mpn_sum_by_key / its host statement.  The summed tiebreaker, the one float
+    sum, is always np.bincount over the rows in their order."""
     aligned = (best['sequence_to'] - best['sequence_from']).to_numpy()
-    out = pandas.DataFrame({
-        'assembly_id': asm,
-        'total_number_of_read': np.bincount(ac, minlength=n).astype(np.int64),
-        'total_read_bp': total(best['read_length']).astype(np.int64),
-        'total_aligned_bp': total(aligned).astype(np.int64),
-        'match': total(best['match']).astype(np.int64),
-        'edit_dist': total(best['edit_dist']).astype(np.int64),
-        'alignment_score': total(best['alignment_score']).astype(np.int64),
-        'alignment_score_tiebreaker': total(best['alignment_score_tiebreaker']),
-    })
-    length = dict(zip(assembly_length['assembly_id'], assembly_length['assembly_length']))
-    out['assembly_length'] = np.array([int(length.get(a, 0)) for a in asm], dtype=np.int64)
-    for col in ('tax_id', 'species_tax_id', 'genus_tax_id', 'genus_height'):
-        lut = dict(zip(assembly_tax['assembly_id'], assembly_tax[col])) if assembly_tax is not None and col in assembly_tax else {}
-        out[col] = np.array([int(lut.get(a, 0)) for a in asm], dtype=np.int64)
-    cov = covered_bp_by_assembly(best, noise_bed=noise_bed, device=device)
-    out['covered_bp'] = np.array([int(cov.get(a, 0)) for a in asm], dtype=np.int64)
-    out['noise_span_bp'] = 0
-    if noise_bed is not None and noise_bed.shape[0]:
-        # bed_to_covered_bp_by_assembly_id(noise_bed): the plain sum of the noise intervals' lengths per assembly (:523-533)
-        span = (noise_bed['end'] - noise_bed['start']).groupby(noise_bed['assembly_id'].astype(str)).sum()
-        out['noise_span_bp'] = np.array([int(span.get(a, 0)) for a in asm], dtype=np.int64)
-    L = out['assembly_length'].to_numpy(dtype=np.float64)
+    count, (read_bp, aligned_bp, match, edit_dist, score) = sums(code, n, [best['read_length'], aligned, best['match'], best['edit_dist'],
+                                                                           best['alignment_score']])
+    return {
+        'total_number_of_read': count,
+        'total_read_bp': read_bp,
+        'total_aligned_bp': aligned_bp,
+        'match': match,
+        'edit_dist': edit_dist,
+        'alignment_score': score,
+        'alignment_score_tiebreaker': np.bincount(code, weights=np.asarray(best['alignment_score_tiebreaker'], dtype=np.float64), minlength=n),
+    }
+
+
+def _summary_stat_2(out, length_col):
+    """The derived columns of the reference's summary_stat_2 (megapath_nano.py:495-518) added to `out`, which has the sums,
+    `length_col`, covered_bp and noise_span_bp."""
+    L = out[length_col].to_numpy(dtype=np.float64)
     noise = out['noise_span_bp'].to_numpy(dtype=np.float64)
     tab = out['total_aligned_bp'].to_numpy(dtype=np.float64)
 
@@ -222,6 +226,34 @@ def align_stat_by_assembly_id(align_list, assembly_length, assembly_tax=None, no
         out['adjusted_total_aligned_bp'] = np.round(clean(aad * L), 0).astype(np.int64)
         out['adjusted_average_depth'] = clean(aad)
     return out
+
+
+def _stat_of_best_rows(best, assembly_length, assembly_tax, noise_bed, device, sums):
+    """align_stat_by_assembly_id from the best rows per (read, assembly), listed in (read_id, assembly_id) order"""
+    asm, ac = _codes(best['assembly_id'])
+    n = len(asm)
+    out = pandas.DataFrame({'assembly_id': asm, **_summary_stat_1(best, ac, n, sums)})
+    length = dict(zip(assembly_length['assembly_id'], assembly_length['assembly_length']))
+    out['assembly_length'] = np.array([int(length.get(a, 0)) for a in asm], dtype=np.int64)
+    for col in ('tax_id', 'species_tax_id', 'genus_tax_id', 'genus_height'):
+        lut = dict(zip(assembly_tax['assembly_id'], assembly_tax[col])) if assembly_tax is not None and col in assembly_tax else {}
+        out[col] = np.array([int(lut.get(a, 0)) for a in asm], dtype=np.int64)
+    cov = covered_bp_by_assembly(best, noise_bed=noise_bed, device=device)
+    out['covered_bp'] = np.array([int(cov.get(a, 0)) for a in asm], dtype=np.int64)
+    out['noise_span_bp'] = 0
+    if noise_bed is not None and noise_bed.shape[0]:
+        # bed_to_covered_bp_by_assembly_id(noise_bed): the plain sum of the noise intervals' lengths per assembly (:523-533)
+        span = (noise_bed['end'] - noise_bed['start']).groupby(noise_bed['assembly_id'].astype(str)).sum()
+        out['noise_span_bp'] = np.array([int(span.get(a, 0)) for a in asm], dtype=np.int64)
+    return _summary_stat_2(out, 'assembly_length')
+
+
+def align_stat_by_assembly_id(align_list, assembly_length, assembly_tax=None, noise_bed=None, device=None):
+    """align_list: the Align() table.  assembly_length: DataFrame(assembly_id, assembly_length); assembly_tax (optional):
+    DataFrame(assembly_id, tax_id, species_tax_id, genus_tax_id, genus_height); noise_bed (optional): DataFrame(sequence_id,
+    start, end, assembly_id) as the reference's noise BEDs carry them (name column = assembly_id).  -> DataFrame, one row per
+    assembly."""
+    return _stat_of_best_rows(best_per_read_and_assembly(align_list), assembly_length, assembly_tax, noise_bed, device, _float_sums)
 
 
 # ---- depth profile, depth BED, depth span -----------------------------------------------------------------------------------
@@ -842,3 +874,252 @@ def combine_with_human_and_decoy(*, align_list, human_and_decoy_best_align_list)
     best = pandas.Series(other['alignment_score'].to_numpy(), index=other['read_id'].to_numpy())
     bar = align_list['read_id'].map(best).fillna(0).to_numpy()
     return pandas.concat([align_list[align_list['alignment_score'].to_numpy() > bar], other], axis=0, sort=True)
+
+
+# ---- good alignments, grouped sums, the per-sequence statistic, assembly selection ---------------------------------------------
+_SCORE_LIMIT = 2 ** 53   # |score| below it: the conversion to float64 is exact
+_VALUE_LIMIT = 2 ** 32   # |value| below it: 2^31 of them sum inside int64
+SUM_COLS = 6             # the columns one mpn_sum_by_key call takes
+
+
+def _threshold_arg(threshold):
+    """-> use_threshold, threshold as a Python float (None: no threshold)"""
+    return (0, 0.0) if threshold is None else (1, float(threshold))
+
+
+def device_good_rows(read, unit, score, tiebreak, n_reads, n_units, threshold=None):
+    """mpn_good_rows.  Row i: read[i] in [0, n_reads), unit[i] in [0, n_units), |score[i]| < 2^53, tiebreak[i] finite.
+    -> good_row int64[m], read_best int64[n_reads]: per (read, unit) the row with the largest (score, tiebreak) is kept, the last in
+    input order among equal ones; read_best[r] = the largest kept score of read r (0 without rows); good_row = the kept rows with
+    float64(score) >= float64(read_best) * threshold (threshold None: every kept row), ordered by (read, unit)."""
+    read, unit, score, tiebreak, n_reads, n_units = _best_args(read, unit, score, tiebreak, n_reads, n_units)
+    use, threshold = _threshold_arg(threshold)
+    n = len(read)
+    good, n_good, best = np.empty(max(n, 1), np.int64), ct.c_int64(0), np.zeros(max(n_reads, 1), np.int64)
+    _ffi.check(_lib().mpn_good_rows(n, read.ctypes.data, unit.ctypes.data, score.ctypes.data, tiebreak.ctypes.data, n_reads, n_units, use, threshold,
+                                    good.ctypes.data, ct.byref(n_good), best.ctypes.data), 'mpn_good_rows')
+    return good[:n_good.value].copy(), best[:n_reads]
+
+
+def host_good_rows(read, unit, score, tiebreak, n_reads, n_units, threshold=None):
+    """numpy statement of mpn_good_rows (same arguments, same result)."""
+    read, unit, score, tiebreak, n_reads, n_units = _best_args(read, unit, score, tiebreak, n_reads, n_units)
+    use, threshold = _threshold_arg(threshold)
+    if not math.isfinite(threshold):
+        raise ValueError('the threshold is not finite')
+    n = len(read)
+    bad = (read < 0) | (read >= n_reads) | (unit < 0) | (unit >= n_units) | (score <= -_SCORE_LIMIT) | (score >= _SCORE_LIMIT) | ~np.isfinite(tiebreak)
+    if bad.any():
+        raise ValueError(f'record {int(np.flatnonzero(bad)[0])} outside the domain')
+    read_best = np.zeros(n_reads, dtype=np.int64)
+    if n == 0:
+        return np.zeros(0, np.int64), read_best
+    order = np.lexsort((np.arange(n), tiebreak, score, unit, read))        # the input order decides among equal rows; -0.0 == 0.0
+    r, u = read[order], unit[order]
+    last = np.ones(n, dtype=bool)
+    last[:-1] = (r[1:] != r[:-1]) | (u[1:] != u[:-1])
+    kept = order[last]                                                     # ordered by (read, unit)
+    k_read, k_score = read[kept], score[kept]
+    head = np.ones(len(kept), dtype=bool)
+    head[1:] = k_read[1:] != k_read[:-1]
+    read_best[k_read[head]] = np.maximum.reduceat(k_score, np.flatnonzero(head))
+    if use:
+        kept = kept[k_score.astype(np.float64) >= read_best[k_read].astype(np.float64) * np.float64(threshold)]   # one float64 product
+    return kept.astype(np.int64), read_best
+
+
+def _sum_args(key, n_keys, cols):
+    key = np.ascontiguousarray(key, dtype=np.int32)
+    cols = [np.asarray(c, dtype=np.int64) for c in cols]
+    if any(c.shape != key.shape for c in cols):
+        raise ValueError('every column has one value per row')
+    flat = np.ascontiguousarray(np.concatenate(cols)) if cols else np.zeros(0, np.int64)
+    return key, int(n_keys), len(cols), flat
+
+
+def device_sum_by_key(key, n_keys, cols):
+    """mpn_sum_by_key.  key[i] in [0, n_keys); cols: 1 to 6 arrays of one value per row, |value| < 2^32.
+    -> count int64[n_keys], sums int64[len(cols), n_keys]: the rows and the column sums per key, 0 for a key without rows."""
+    key, n_keys, n_cols, flat = _sum_args(key, n_keys, cols)
+    count, sums = np.zeros(max(n_keys, 1), np.int64), np.zeros(max(n_cols * n_keys, 1), np.int64)
+    _ffi.check(_lib().mpn_sum_by_key(len(key), key.ctypes.data, n_keys, n_cols, flat.ctypes.data, count.ctypes.data, sums.ctypes.data), 'mpn_sum_by_key')
+    return count[:n_keys], sums[:n_cols * n_keys].reshape(n_cols, n_keys)
+
+
+def host_sum_by_key(key, n_keys, cols):
+    """numpy statement of mpn_sum_by_key (same arguments, same result).  np.bincount adds in float64, so every value goes in as
+    v >> 16 and v & 0xffff: over fewer than 2^31 rows both sums stay below 2^53 and are exact."""
+    key, n_keys, n_cols, flat = _sum_args(key, n_keys, cols)
+    if not 1 <= n_cols <= SUM_COLS:
+        raise ValueError(f'1 to {SUM_COLS} columns')
+    bad = (key < 0) | (key >= n_keys)
+    if bad.any():
+        raise ValueError(f'record {int(np.flatnonzero(bad)[0])} outside the domain')
+    vals = flat.reshape(n_cols, len(key))
+    if ((vals <= -_VALUE_LIMIT) | (vals >= _VALUE_LIMIT)).any():
+        raise ValueError('a value outside the domain')
+    sums = np.zeros((n_cols, n_keys), dtype=np.int64)
+    for c in range(n_cols):
+        high = np.bincount(key, weights=(vals[c] >> 16).astype(np.float64), minlength=n_keys).astype(np.int64)
+        low = np.bincount(key, weights=(vals[c] & 0xffff).astype(np.float64), minlength=n_keys).astype(np.int64)
+        sums[c] = (high << 16) + low
+    return np.bincount(key, minlength=n_keys).astype(np.int64)[:n_keys], sums
+
+
+def _best_rows(align_list, unit_col, threshold, device):
+    """positions of the good rows of align_list (mpn_good_rows; unit_col None: the single unit 0), ordered by (read_id, unit)"""
+    reads, rc = _codes(align_list['read_id'])
+    if unit_col is None:
+        n_units, uc = 1, np.zeros(len(rc), dtype=np.int32)
+    else:
+        units, uc = _codes(align_list[unit_col])
+        n_units = len(units)
+    run = device_good_rows if device else host_good_rows
+    return run(rc, uc, align_list['alignment_score'].to_numpy(dtype=np.int64), align_list['alignment_score_tiebreaker'].to_numpy(dtype=np.float64),
+               len(reads), n_units, threshold)[0]
+
+
+def good_align_list(*, align_list, good_align_threshold, device=None):
+    """The reference's good_align_list (megapath_nano.py:642-663): per (read_id, assembly_id) the row with the largest
+    (alignment_score, tiebreaker), the last in table order among equal ones; of those the rows with
+    alignment_score >= (their read's largest kept score) * (good_align_threshold / 100), the product in float64.
+    -> those rows with their index labels and columns, ordered by (read_id, assembly_id).  An empty table comes back empty.
+    device: as in covered_bp_by_assembly."""
+    if align_list.shape[0] == 0:
+        return align_list.copy()
+    if device is None:
+        device = True
+    return align_list.iloc[_best_rows(align_list, 'assembly_id', good_align_threshold / 100, device)]
+
+
+def best_align_per_read(align_list, device=None):
+    """`sort_values(['read_id', 'alignment_score', 'alignment_score_tiebreaker']).drop_duplicates('read_id', keep='last')` of the
+    reference (megapath_nano.py:1287, :1459): one row per read, the one with the largest (alignment_score, tiebreaker), the last in
+    table order among equal ones, ordered by read_id, index labels and columns kept.  device: as in covered_bp_by_assembly."""
+    if align_list.shape[0] == 0:
+        return align_list.copy()
+    if device is None:
+        device = True
+    return align_list.iloc[_best_rows(align_list, None, None, device)]
+
+
+def _key_sums(device):
+    run = device_sum_by_key if device else host_sum_by_key
+
+    def sums(code, n, cols):
+        count, s = run(code, n, cols)
+        return count, list(s)
+    return sums
+
+
+def _align_stat_by_assembly_id_exact(align_list, assembly_length, assembly_tax, device):
+    """align_stat_by_assembly_id with the best rows from mpn_good_rows and the integer sums from mpn_sum_by_key (device) or from
+    their host statements: the same table wherever align_stat_by_assembly_id's float64 sums are exact (below 2^53)."""
+    best = align_list.iloc[_best_rows(align_list, 'assembly_id', None, device)]
+    return _stat_of_best_rows(best, assembly_length, assembly_tax, None, device, _key_sums(device))
+
+
+_SEQUENCE_STAT_COLUMNS = ['assembly_id', 'sequence_id', 'total_number_of_read', 'total_read_bp', 'total_aligned_bp', 'match', 'edit_dist', 'alignment_score',
+                          'alignment_score_tiebreaker', 'sequence_length', 'covered_bp', 'noise_span_bp', 'average_read_length', 'average_depth',
+                          'covered_percent', 'noise_span_percent', 'adjusted_covered_percent', 'average_identity', 'average_edit_dist',
+                          'average_alignment_score', 'adjusted_average_depth', 'adjusted_total_aligned_bp']
+
+
+def align_stat_by_sequence_id(align_list, sequence_length, noise_bed=None, device=None):
+    """The reference's align_list_to_align_stat_by_sequence_id (megapath_nano.py:585-639).  align_list: the Align() table;
+    sequence_length: DataFrame(sequence_id, sequence_length), a sequence it lacks has length 0; noise_bed (optional):
+    DataFrame(sequence_id, start, end[, assembly_id]), matched on sequence_id alone (`bedtools subtract` sees that column only).
+    Per (read_id, sequence_id) the row with the largest (alignment_score, tiebreaker) is kept; the sums of summary_stat_1 per
+    (assembly_id, sequence_id); covered_bp = the union length of the kept rows' target intervals on the sequence minus what the
+    noise BED covers there; noise_span_bp = the summed length of the noise intervals of the sequence; the columns of summary_stat_2
+    over sequence_length.  -> DataFrame, one row per sequence, ordered by the bytes of assembly_id + ',' + sequence_id.
+    A sequence_id under two assemblies raises ValueError (the reference's validate='1:1' merge raises there).
+    device: as in covered_bp_by_assembly."""
+    if align_list.shape[0] == 0:
+        return pandas.DataFrame({c: np.zeros(0, dtype=object if c.endswith('_id') else np.float64 if 'average' in c or 'percent' in c or 'tiebreaker' in c
+                                             else np.int64) for c in _SEQUENCE_STAT_COLUMNS})
+    if device is None:
+        device = True
+    best = align_list.iloc[_best_rows(align_list, 'sequence_id', None, device)]
+    asm = best['assembly_id'].to_numpy(dtype=object).astype(str)
+    seqs, sc = _codes(best['sequence_id'])
+    n = len(seqs)
+    asm_of = np.empty(n, dtype=asm.dtype)
+    asm_of[sc] = asm
+    if not np.array_equal(asm_of[sc], asm):
+        raise ValueError(f'sequence_id {seqs[sc[np.flatnonzero(asm_of[sc] != asm)[0]]]} lies under two assemblies')
+    order = np.argsort(np.char.add(np.char.add(asm_of, ','), seqs), kind='stable')    # the order of groupby(assembly_id + ',' + sequence_id)
+    rank = np.empty(n, dtype=np.int32)
+    rank[order] = np.arange(n, dtype=np.int32)
+    key = rank[sc]
+    out = pandas.DataFrame({'assembly_id': asm_of[order], 'sequence_id': seqs[order], **_summary_stat_1(best, key, n, _key_sums(device))})
+    length = dict(zip(sequence_length['sequence_id'].astype(str), sequence_length['sequence_length']))
+    out['sequence_length'] = np.array([int(length.get(s, 0)) for s in out['sequence_id']], dtype=np.int64)
+    cover = device_cover_by_group if device else host_cover_by_group
+    start, end = best['sequence_from'].to_numpy(dtype=np.int64), best['sequence_to'].to_numpy(dtype=np.int64)
+    out['noise_span_bp'] = 0
+    if noise_bed is None or noise_bed.shape[0] == 0:
+        covered = cover(key, key, start, end, n)
+    else:
+        # |A \ N| = |A u N| - |N| per sequence, over the noise intervals of the sequences that carry alignments
+        where = pandas.Index(out['sequence_id']).get_indexer(noise_bed['sequence_id'].astype(str))
+        hit = where >= 0
+        n_key = where[hit].astype(np.int32)
+        n_start, n_end = noise_bed['start'].to_numpy(dtype=np.int64)[hit], noise_bed['end'].to_numpy(dtype=np.int64)[hit]
+        both_key = np.concatenate([key, n_key])
+        covered = cover(both_key, both_key, np.concatenate([start, n_start]), np.concatenate([end, n_end]), n) - cover(n_key, n_key, n_start, n_end, n)
+        # bed_to_covered_bp_by_sequence_id(noise_bed): the plain sum of the noise intervals' lengths per sequence
+        out['noise_span_bp'] = np.bincount(n_key, weights=(n_end - n_start).astype(np.float64), minlength=n).astype(np.int64)
+    out.insert(out.columns.get_loc('noise_span_bp'), 'covered_bp', np.asarray(covered, dtype=np.int64))
+    return _summary_stat_2(out, 'sequence_length')
+
+
+class AssemblySelection:
+    """What assembly_selection returns: the attributes of the reference's assembly_selection.O and the two counts it logs."""
+    __slots__ = ('align_list', 'best_align_list', 'good_align_list', 'align_stat', 'assembly_list', 'species_align_stat',
+                 'num_species_reached_min_average_depth', 'num_species_not_reached')
+
+
+def _species_pick(stat):
+    return stat.sort_values(['species_tax_id', 'adjusted_average_depth', 'alignment_score_tiebreaker']).drop_duplicates(subset=['species_tax_id'], keep='last')
+
+
+def assembly_selection(*, species_align_list, assembly_align_list, species_list, read_id_species_id, assembly_ID_min_average_depth, good_align_threshold,
+                       assembly_length, assembly_tax, device=None):
+    """step_assembly_selection (megapath_nano.py:1400-1476).  species_align_list / assembly_align_list: the Align() tables against
+    the species-ID and the assembly-ID genome sets, each with a species_tax_id column; species_list: DataFrame with species_tax_id,
+    one row per species; read_id_species_id: DataFrame(read_id, species_tax_id), one row per read; assembly_length / assembly_tax:
+    as in align_stat_by_assembly_id (they stand for the reference's assembly_metadata).
+    The statistic per assembly of species_align_list picks one assembly per species -- the largest (adjusted_average_depth, summed
+    tiebreaker), the last among equal ones -- and the species of species_list whose pick reaches assembly_ID_min_average_depth keep
+    their rows of assembly_align_list; species_align_list keeps the rows on the species its read was placed in.  Of the two together
+    (`concat(sort=True)`): the best row per read, the good rows (good_align_list), the statistic per assembly of the good rows and,
+    from it, one assembly per species.  The per-species pick runs over one row per assembly and stays in pandas.
+    -> AssemblySelection.  device: as in covered_bp_by_assembly; the best rows come from mpn_good_rows and the integer sums from
+    mpn_sum_by_key (or their host statements), and the summed tiebreaker is np.bincount over the listed rows either way."""
+    if device is None:
+        device = True
+
+    def stat(table):
+        return _align_stat_by_assembly_id_exact(table, assembly_length, assembly_tax, device)
+    out = AssemblySelection()
+    species_stat = _species_pick(stat(species_align_list))
+    species_stat = species_stat.merge(right=species_list[['species_tax_id']].set_index('species_tax_id'), how='inner', left_on='species_tax_id',
+                                      right_index=True, suffixes=['', '_y'], validate='1:1')
+    reached = species_stat[species_stat['adjusted_average_depth'].to_numpy() >= assembly_ID_min_average_depth][['species_tax_id']]
+    not_reached = species_list.merge(right=reached.assign(reached_min_average_depth=1).set_index('species_tax_id'), how='left', left_on='species_tax_id',
+                                     right_index=True, suffixes=['', '_y'], validate='1:1').fillna(0).query('reached_min_average_depth == 0')
+    from_assembly = assembly_align_list.merge(right=reached.set_index('species_tax_id'), how='inner', left_on='species_tax_id', right_index=True,
+                                              suffixes=['', '_y'], validate='m:1')
+    from_species = species_align_list.merge(right=read_id_species_id.rename(columns={'species_tax_id': 'read_species_tax_id'}).set_index('read_id'),
+                                            how='inner', left_on='read_id', right_index=True, suffixes=['', '_y'], validate='m:1')
+    from_species = from_species[(from_species['species_tax_id'] == from_species['read_species_tax_id']).to_numpy()].drop(['read_species_tax_id'], axis=1)
+    out.species_align_stat = species_stat
+    out.align_list = pandas.concat([from_assembly, from_species], axis=0, sort=True)
+    out.best_align_list = best_align_per_read(out.align_list, device=device)
+    out.good_align_list = good_align_list(align_list=out.align_list, good_align_threshold=good_align_threshold, device=device)
+    out.align_stat = stat(out.good_align_list)
+    out.assembly_list = _species_pick(out.align_stat).copy()
+    out.num_species_reached_min_average_depth = int(reached.shape[0])
+    out.num_species_not_reached = int(not_reached.shape[0])
+    return out

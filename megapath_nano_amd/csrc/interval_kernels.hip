@@ -794,6 +794,65 @@ struct BaCompactPass {
     }
 };
 
+// No segments, like BaCompactPass: the running count of GOOD rows -- kept rows whose score reaches `threshold` times their read's
+// largest (the reference's good_align_list, bin/megapath_nano.py:642-663) -- puts each into its place in the list.  The bar is one
+// IEEE float64 product, formed by __dmul_rn and compared: with no addition beside it there is nothing to contract into an FMA, and
+// the intrinsic says so whatever the flags.  Both conversions are exact (|score| < 2^53).
+struct BaGoodPass {
+    struct V { int64_t c; int32_t head, pad; };
+    const Rec3 *rec; const int64_t *w_idx, *w_score, *r_max; int64_t n; int32_t use_threshold; double threshold; int64_t *good_row, *n_good;
+    __device__ static V identity() { return V{0, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return V{a.c + b.c, 0, 0}; }
+    __device__ bool good(int64_t i) const {
+        if (w_idx[i] < 0) return false;
+        if (!use_threshold) return true;
+        const double bar = __dmul_rn((double)r_max[rec[i].lo >> 32], threshold);
+        return (double)w_score[i] >= bar;
+    }
+    __device__ V load(int64_t i) const { return V{good(i) ? 1 : 0, 0, 0}; }
+    __device__ void store(int64_t i, const V &inc) const {
+        if (good(i)) good_row[inc.c - 1] = w_idx[i];
+        if (i + 1 == n) n_good[0] = inc.c;
+    }
+};
+
+// Rows sorted by lo = key, input order kept among equal keys.  A segment is one key: the number of its rows and the running sums of
+// up to BA_SUM_COLS columns (a column the caller did not give is loaded as 0), stored by the key's last row.  64 bytes a value;
+// integer addition is exact in any order, so the shape of the scan plays no part in the result.  No atomics: one key may hold most
+// of the rows (the assembly that most reads hit), and the scan costs the same whatever the distribution.
+constexpr int BA_SUM_COLS = 6;
+struct BaSumPass {
+    struct V { int64_t cnt; int64_t s[BA_SUM_COLS]; int32_t head, pad; };
+    const Rec3 *rec; const int64_t *cols; int64_t n; int32_t n_cols, n_keys; int64_t *count, *sums;
+    __device__ static V identity() { V v; v.cnt = 0; for (int c = 0; c < BA_SUM_COLS; ++c) v.s[c] = 0; v.head = 0; v.pad = 0; return v; }
+    __device__ static V merge(const V &a, const V &b) {
+        V v;
+        v.cnt = a.cnt + b.cnt;
+#pragma unroll
+        for (int c = 0; c < BA_SUM_COLS; ++c) v.s[c] = a.s[c] + b.s[c];
+        v.head = 0; v.pad = 0;
+        return v;
+    }
+    __device__ V load(int64_t i) const {
+        const Rec3 r = rec[i];
+        V v;
+        v.cnt = 1;
+#pragma unroll
+        for (int c = 0; c < BA_SUM_COLS; ++c) v.s[c] = c < n_cols ? cols[(size_t)c * (size_t)n + (size_t)r.idx] : 0;
+        v.head = i == 0 || rec[i - 1].lo != r.lo;
+        v.pad = 0;
+        return v;
+    }
+    __device__ void store(int64_t i, const V &inc) const {
+        const uint64_t k = rec[i].lo;
+        if (i + 1 != n && rec[i + 1].lo == k) return;
+        count[k] = inc.cnt;
+#pragma unroll
+        for (int c = 0; c < BA_SUM_COLS; ++c) if (c < n_cols) sums[(size_t)c * (size_t)n_keys + k] = inc.s[c];
+    }
+};
+static_assert(sizeof(BaSumPass::V) == 64, "the count, six sums and head");
+
 // A segment is one read of the candidate list: its summed weight and its number of candidates, stored by its last candidate.
 struct BaWeightPass {
     struct V { int64_t sum, cnt; int32_t head, pad; };
@@ -1204,5 +1263,98 @@ extern "C" int mpn_second_best_by_read(int64_t n, const int32_t *read, const int
     if (d_second.download(second, (size_t)n_reads, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
     for (int32_t r = 0; r < n_reads; ++r) if (second[r] == BA_MIN) second[r] = 0;   // no row off the excluded assembly
+    return 0;
+}
+
+extern "C" int mpn_good_rows(int64_t n, const int32_t *read, const int32_t *unit, const int64_t *score, const double *tiebreak, int32_t n_reads,
+                             int32_t n_units, int32_t use_threshold, double threshold, int64_t *good_row, int64_t *n_good, int64_t *read_best) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || n_reads < 0 || n_units < 0 || !n_good || (n_reads > 0 && !read_best) || !std::isfinite(threshold) ||
+        (n > 0 && (!read || !unit || !score || !tiebreak || !good_row))) {
+        set_error("mpn_good_rows: bad arguments (n in [0, 2^31), n_reads and n_units >= 0, a finite threshold, no NULL array)");
+        return -2;
+    }
+    constexpr int64_t LIMIT = (int64_t)1 << 53;
+    std::vector<uint64_t> hi((size_t)n, 0), lo((size_t)n), tb((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (read[i] < 0 || read[i] >= n_reads || unit[i] < 0 || unit[i] >= n_units || score[i] <= -LIMIT || score[i] >= LIMIT || !std::isfinite(tiebreak[i])) {
+            set_error("mpn_good_rows: record %lld outside the domain (read in [0, n_reads), unit in [0, n_units), |score| < 2^53, finite tiebreak)", (long long)i);
+            return -2;
+        }
+        lo[(size_t)i] = (uint64_t)read[i] << 32 | (uint64_t)unit[i];
+        tb[(size_t)i] = ba_ordered_bits(tiebreak[i] == 0.0 ? 0.0 : tiebreak[i]);
+    }
+    *n_good = 0;
+    for (int32_t r = 0; r < n_reads; ++r) read_best[r] = 0;
+    if (n == 0) return 0;
+
+    hipStream_t st = 0;
+    DevBuf<uint64_t> d_hi, d_lo, d_tb;
+    DevBuf<int64_t> d_score, w_idx, w_score, r_max, r_cnt, d_row, d_n;
+    DevBuf<Rec3> a, b;
+    if (d_hi.upload(hi.data(), (size_t)n, st) || d_lo.upload(lo.data(), (size_t)n, st) || d_tb.upload(tb.data(), (size_t)n, st) ||
+        d_score.upload(score, (size_t)n, st) || a.alloc((size_t)n) || b.alloc((size_t)n) || w_idx.alloc((size_t)n) || w_score.alloc((size_t)n) ||
+        r_max.alloc((size_t)n_reads) || r_cnt.alloc((size_t)n_reads) || r_cnt.zero(st) || d_row.alloc((size_t)n) || d_n.alloc(1)) return -1;
+    hipLaunchKernelGGL(rs_fill_kernel, dim3(ba_grid(n)), dim3(256), 0, st, (const uint64_t *)d_hi.p, (const uint64_t *)d_lo.p, n, a.p);
+    hipLaunchKernelGGL(ba_fill_kernel, dim3(ba_grid(n_reads)), dim3(256), 0, st, r_max.p, (int64_t)n_reads, BA_MIN);
+    MPN_HIP_CHECK(hipGetLastError());
+    // digits that no record has: all of hi, the bytes of the unit above n_units - 1 and those of the read above n_reads - 1
+    uint32_t skip = 0xff00;
+    for (int p = 0; p < 4; ++p) {
+        if (((uint64_t)(n_units - 1) >> (8 * p)) == 0) skip |= 1u << p;
+        if (((uint64_t)(n_reads - 1) >> (8 * p)) == 0) skip |= 1u << (4 + p);
+    }
+    Rec3 *rec = nullptr;
+    if (radix_sort_rec3(a.p, b.p, n, &rec, st, skip)) return -1;
+    if (ba_scan(BaGroupPass{rec, d_score.p, d_tb.p, n, w_idx.p, w_score.p}, n, st) ||
+        ba_scan(BaReadPass{rec, w_idx.p, w_score.p, n, r_max.p, r_cnt.p}, n, st) ||
+        ba_scan(BaGoodPass{rec, w_idx.p, w_score.p, r_max.p, n, use_threshold, threshold, d_row.p, d_n.p}, n, st)) return -1;
+    int64_t m = 0;
+    if (d_n.download(&m, 1, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    if (m < 0 || m > n) { set_error("mpn_good_rows: %lld good rows out of %lld rows", (long long)m, (long long)n); return -1; }
+    if (d_row.download(good_row, (size_t)m, st) || r_max.download(read_best, (size_t)n_reads, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    for (int32_t r = 0; r < n_reads; ++r) if (read_best[r] == BA_MIN) read_best[r] = 0;   // a read without rows
+    *n_good = m;
+    return 0;
+}
+
+extern "C" int mpn_sum_by_key(int64_t n, const int32_t *key, int32_t n_keys, int32_t n_cols, const int64_t *cols, int64_t *count, int64_t *sums) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || n_keys < 0 || n_cols < 1 || n_cols > BA_SUM_COLS || (n_keys > 0 && (!count || !sums)) || (n > 0 && (!key || !cols))) {
+        set_error("mpn_sum_by_key: bad arguments (n in [0, 2^31), n_keys >= 0, n_cols in [1, %d], no NULL array)", BA_SUM_COLS);
+        return -2;
+    }
+    constexpr int64_t LIMIT = (int64_t)1 << 32;
+    std::vector<uint64_t> hi((size_t)n, 0), lo((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (key[i] < 0 || key[i] >= n_keys) { set_error("mpn_sum_by_key: record %lld outside the domain (key in [0, n_keys))", (long long)i); return -2; }
+        lo[(size_t)i] = (uint64_t)key[i];
+    }
+    for (int32_t c = 0; c < n_cols; ++c)
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t v = cols[(size_t)c * (size_t)n + (size_t)i];
+            if (v <= -LIMIT || v >= LIMIT) { set_error("mpn_sum_by_key: record %lld outside the domain (|value| < 2^32 in column %d)", (long long)i, (int)c); return -2; }
+        }
+    for (int32_t k = 0; k < n_keys; ++k) count[k] = 0;
+    for (size_t j = 0; j < (size_t)n_cols * (size_t)n_keys; ++j) sums[j] = 0;
+    if (n == 0) return 0;
+
+    hipStream_t st = 0;
+    DevBuf<uint64_t> d_hi, d_lo;
+    DevBuf<int64_t> d_cols, d_count, d_sums;
+    DevBuf<Rec3> a, b;
+    if (d_hi.upload(hi.data(), (size_t)n, st) || d_lo.upload(lo.data(), (size_t)n, st) || d_cols.upload(cols, (size_t)n_cols * (size_t)n, st) || a.alloc((size_t)n) ||
+        b.alloc((size_t)n) || d_count.alloc((size_t)n_keys) || d_count.zero(st) || d_sums.alloc((size_t)n_cols * (size_t)n_keys) || d_sums.zero(st)) return -1;
+    hipLaunchKernelGGL(rs_fill_kernel, dim3(ba_grid(n)), dim3(256), 0, st, (const uint64_t *)d_hi.p, (const uint64_t *)d_lo.p, n, a.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    // digits that no record has: all of hi, the upper half of lo and the bytes of the key above n_keys - 1
+    uint32_t skip = 0xfff0;
+    for (int p = 0; p < 4; ++p)
+        if (((uint64_t)(n_keys - 1) >> (8 * p)) == 0) skip |= 1u << p;
+    Rec3 *rec = nullptr;
+    if (radix_sort_rec3(a.p, b.p, n, &rec, st, skip)) return -1;
+    if (ba_scan(BaSumPass{rec, d_cols.p, n, n_cols, n_keys, d_count.p, d_sums.p}, n, st)) return -1;
+    if (d_count.download(count, (size_t)n_keys, st) || d_sums.download(sums, (size_t)n_cols * (size_t)n_keys, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
     return 0;
 }
