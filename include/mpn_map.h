@@ -187,6 +187,28 @@ int mpn_hit_select_batch(const mpn_map_opt *opt, int32_t k, int32_t n, const int
                          int32_t path, int32_t max_chains, int32_t grid_cap, int32_t *n_regs, int32_t *n_a, int64_t *hits,
                          uint64_t *sq_anchors);
 
+/* ---- stage: the planning of the base-level extension on arbitrary hits (tests) ----------------------------------------------------
+ * The first half of minimap2's mm_align1 for every hit of an alignment round (mm_fix_bad_ends, mm_filter_bad_seeds, the limits of
+ * the two end extensions, the cut of the hit into left extension, gap fills and right extension), run by the same function with
+ * the same launch as a round of mpn_map_batch.  t_len: n_targets target lengths.  Arrays are CSR over reads: read i has the
+ * squeezed anchors anchors[anchor_off[i] .. anchor_off[i + 1]) as (x, y) word pairs (x = strand << 63 | rid << 32 | target
+ * position, y = flags | span << 32 | read position on the hit's strand; the flag bits 40..42 may be set, as a first round leaves
+ * them) and the hits hit_off[i] .. hit_off[i + 1): h_as, h_cnt (its anchors [as, as + cnt) of the read's list), h_mlen,
+ * h_split_inv.  grid_cap: 0 = the mapper's grid, else at most that many blocks.
+ * Validated on the host before any launch (-1): q_len > 0; every anchor with rid < n_targets, 0 <= (int32)x < t_len[rid],
+ * 0 <= (int32)y < q_len, span in 1..255 and no bit above 42; every hit with cnt >= 1 and as + cnt within the read's anchors, one
+ * x >> 32 for all its anchors, x and y strictly increasing; the hits of a read disjoint; win_cap at least the sum of cnt + 1.
+ * Out: hits_out: 11 words per hit in input order: n_jobs, as1, cnt1 (the anchors mm_fix_bad_ends keeps) and qs, rs, qe, re, qs0,
+ * qe0, rid, rev of the stitching record; win_out: 13 words per window: read, rid, rev, qs, qlen, ts, tlen, reversed, w, zdrop,
+ * end_bonus, flag, job_anchor (the anchor a gap fill ends at, counted from as1; -1 for an extension), the windows of a hit in
+ * order (left extension, fills, right extension), hit after hit in input order; *n_win their number; anchors_out: every anchor
+ * word as the kernel left it in device memory (SEED_IGNORE marks, bit 41 of y).  A window refused by max_sw_mat is a placeholder
+ * with qlen = tlen = w = zdrop = end_bonus = 0 and flag | 0x100.  Returns 0, or -1. */
+int mpn_ext_plan_batch(const mpn_map_opt *opt, int32_t k, int32_t n_targets, const int32_t *t_len, int32_t n, const int32_t *q_len,
+                       const int64_t *anchor_off, const uint64_t *anchors, const int64_t *hit_off, const int32_t *h_as,
+                       const int32_t *h_cnt, const int32_t *h_mlen, const int32_t *h_split_inv, int32_t grid_cap,
+                       int32_t *hits_out, int64_t win_cap, int64_t *n_win, int32_t *win_out, uint64_t *anchors_out);
+
 /* ---- product call: map a batch of reads, PAF text out ----------------------------------------------------
  * names: n NUL-terminated read names.  paf receives the lines of all reads in input order (NUL terminated).
  * Returns the number of bytes written, or negative error (-3: paf_cap too small). */

@@ -1268,6 +1268,25 @@ static int run_jobs(const RefView &rv, const mpn_map_opt *opt, int nj_cap, const
 
 using namespace mpn;
 
+// The planning launch of an alignment round (plan_kernels.h), for the mapper's round loop and for the stage entry
+// mpn_ext_plan_batch alike: the n_sr hits d_pr of the round are cut into DP windows.  d_used: the round's counters (64 bytes,
+// reset here; the window count is d_used[3]); d_jobs / d_janchor: room for cnt + 2 windows per hit.  grid_cap: 0 = the
+// mapper's grid, else at most that many blocks (the tests: one block takes every hit in turn).
+static int plan_enqueue(const mpn_map_opt *opt, int32_t k, const PlanReg *d_pr, int n_sr, u128 *d_a, const int32_t *d_tlens,
+                        unsigned long long *d_used, ExtJob *d_jobs, int32_t *d_janchor, StitchReg *d_sr, PlanSum *d_ps, int grid_cap,
+                        hipStream_t st) {
+    PlanOpt po;
+    po.bw = opt->bw; po.bw15 = (int)(opt->bw * 1.5 + 1.); po.min_chain_score = opt->min_chain_score; po.max_gap = opt->max_gap;
+    po.min_cnt = opt->min_cnt; po.a = opt->a; po.q = opt->q; po.e = opt->e; po.zdrop = opt->zdrop; po.zdrop_inv = opt->zdrop_inv;
+    po.end_bonus = opt->end_bonus; po.min_ksw_len = opt->min_ksw_len; po.k = k; po.pad = 0; po.max_sw_mat = opt->max_sw_mat;
+    MPN_HIP_CHECK(hipMemsetAsync(d_used, 0, 64, st));   // every counter of the round in one fill
+    int grid = std::min(n_sr, 256 * 4);
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
+    hipLaunchKernelGGL(plan_kernel, dim3((unsigned)grid), dim3(64), 0, st, po, d_pr, n_sr, d_a, d_tlens, d_used + 3, d_jobs, d_janchor, d_sr, d_ps);
+    MPN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // Stitching + CIGAR fix-up + statistics of every hit aligned in this round, on the device (stitch_kernels.h, fin_kernels.h):
 // the windows' CIGARs are concatenated per hit in HBM, fixed and measured there; the host gets 56 + 32 bytes per hit, and the
 // fixed CIGARs only when the caller wants text (need_cigar).
@@ -1739,10 +1758,6 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
     const int64_t n_sq = sq_off[n];
     if (opt->with_cigar && n_sq > 0) {
         DevBuf<u128> &d_a = hb.a;
-        PlanOpt po;
-        po.bw = opt->bw; po.bw15 = (int)(opt->bw * 1.5 + 1.); po.min_chain_score = opt->min_chain_score; po.max_gap = opt->max_gap;
-        po.min_cnt = opt->min_cnt; po.a = opt->a; po.q = opt->q; po.e = opt->e; po.zdrop = opt->zdrop; po.zdrop_inv = opt->zdrop_inv;
-        po.end_bonus = opt->end_bonus; po.min_ksw_len = opt->min_ksw_len; po.k = idx->k; po.pad = 0; po.max_sw_mat = opt->max_sw_mat;
         const RefView rv{idx->d_seq2.p, idx->d_seq_off.p, idx->d_nrun_s.p, idx->d_nrun_e.p, idx->n_nruns};
         const HostSeqs hseqs{seqs, seq_off, seq_len, idx->seq_off.data()};
         std::vector<int32_t> sr_base((size_t)n + 1, 0);
@@ -1793,12 +1808,9 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
             ExtJob *d_jobs = SL.pool_jobs.as<ExtJob>();
             int32_t *d_janchor = SL.pool_job_anchor.as<int32_t>();
             unsigned long long *d_used = SL.pool_used.as<unsigned long long>();
-            MPN_HIP_CHECK(hipMemsetAsync(d_used, 0, 64, st));   // every counter of the round in one fill
             MPN_HIP_CHECK(hipMemcpyAsync(d_pr, h_pr, (size_t)n_sr * sizeof(PlanReg), hipMemcpyHostToDevice, st));
             EvTimer evp(st);
-            hipLaunchKernelGGL(plan_kernel, dim3((unsigned)std::min(n_sr, 256 * 4)), dim3(64), 0, st, po, (const PlanReg *)d_pr, n_sr, d_a.p,
-                               (const int32_t *)idx->d_lens.p, d_used + 3, d_jobs, d_janchor, d_sr, d_ps);
-            MPN_HIP_CHECK(hipGetLastError());
+            if (plan_enqueue(opt, idx->k, d_pr, n_sr, d_a.p, idx->d_lens.p, d_used, d_jobs, d_janchor, d_sr, d_ps, 0, st)) return -1;
             evp.mark(55);
             wt.stop_into(g_stats[20]);
             ++g_stats[7];
@@ -2960,5 +2972,129 @@ extern "C" int mpn_hit_select_batch(const mpn_map_opt *opt, int32_t k, int32_t n
             o[8] = r.parent; o[9] = r.subsc; o[10] = r.n_sub; o[11] = r.mlen; o[12] = r.blen; o[13] = (int64_t)r.hash; o[14] = (int64_t)r.sam_pri;
         }
     }
+    return 0;
+}
+
+// stage entry point for the tests of the extension planning stage: plan_kernel, launched by plan_enqueue as the mapper's round loop
+// launches it, on arbitrary hits of arbitrary squeezed anchor lists.  Arrays are CSR over reads (anchors, hits).  hits_out: 11
+// words per hit in input order: n_jobs, as1, cnt1, qs, rs, qe, re, qs0, qe0, rid, rev.  win_out: 13 words per window: read, rid, rev,
+// qs, qlen, ts, tlen, reversed, w, zdrop, end_bonus, flag, job_anchor; the windows of hit 0, then those of hit 1, ... (the kernel
+// places the hits' window groups in no particular order: they are put in hit order here, by first_job).
+extern "C" int mpn_ext_plan_batch(const mpn_map_opt *opt, int32_t k, int32_t n_targets, const int32_t *t_len, int32_t n, const int32_t *q_len,
+                                  const int64_t *anchor_off, const uint64_t *anchors, const int64_t *hit_off, const int32_t *h_as,
+                                  const int32_t *h_cnt, const int32_t *h_mlen, const int32_t *h_split_inv, int32_t grid_cap,
+                                  int32_t *hits_out, int64_t win_cap, int64_t *n_win, int32_t *win_out, uint64_t *anchors_out) {
+    std::lock_guard<std::mutex> call_guard(g_call_mu);
+    hipStream_t st = 0;
+    if (n < 0) { set_error("mpn_ext_plan_batch: negative count"); return -1; }
+    if (n_win) *n_win = 0;
+    if (n == 0) return 0;
+    if (!opt || !t_len || !q_len || !anchor_off || !hit_off || !hits_out || !n_win || !win_out || !anchors_out) {
+        set_error("mpn_ext_plan_batch: options or an array missing"); return -1;
+    }
+    if (k < 1 || k > 255 || n_targets < 1 || grid_cap < 0 || win_cap < 0) { set_error("mpn_ext_plan_batch: k, n_targets, grid_cap or win_cap out of range"); return -1; }
+    // everything is checked here, before any launch
+    if (anchor_off[0] != 0 || hit_off[0] != 0) { set_error("mpn_ext_plan_batch: offsets do not start at 0"); return -1; }
+    for (int t = 0; t < n_targets; ++t)
+        if (t_len[t] <= 0) { set_error("mpn_ext_plan_batch: target %d: no length", t); return -1; }
+    for (int i = 0; i < n; ++i) {
+        if (anchor_off[i + 1] < anchor_off[i] || hit_off[i + 1] < hit_off[i] || anchor_off[i + 1] - anchor_off[i] > 0x3fffffff ||
+            hit_off[i + 1] - hit_off[i] > 0x3fffffff) {
+            set_error("mpn_ext_plan_batch: read %d: offsets out of order", i); return -1;
+        }
+        if (q_len[i] <= 0) { set_error("mpn_ext_plan_batch: read %d: no length", i); return -1; }
+    }
+    const int64_t n_anch = anchor_off[n], n_hits64 = hit_off[n];
+    if (n_hits64 > 0x3fffffff) { set_error("mpn_ext_plan_batch: too many hits"); return -1; }
+    const int n_hits = (int)n_hits64;
+    if (n_hits == 0) return 0;
+    if (!anchors || !h_as || !h_cnt || !h_mlen || !h_split_inv) { set_error("mpn_ext_plan_batch: a hit array missing"); return -1; }
+    std::vector<PlanReg> pregs((size_t)n_hits);
+    int64_t cap_need = 0, cap_dev = 0;
+    {
+        std::vector<std::pair<int32_t, int32_t>> iv;
+        for (int i = 0; i < n; ++i) {
+            const int64_t n_a = anchor_off[i + 1] - anchor_off[i];
+            const uint64_t *a = anchors + 2 * anchor_off[i];
+            for (int64_t j = 0; j < n_a; ++j) {   // the walks over a hit's neighbours read every anchor of the read
+                const uint64_t x = a[2 * j], y = a[2 * j + 1];
+                const int64_t rid = (int64_t)(x << 1 >> 33);
+                const int32_t span = (int32_t)(y >> 32 & 0xff);
+                if (rid >= n_targets || (int32_t)x < 0 || (int32_t)x >= t_len[rid] || (int32_t)y < 0 || (int32_t)y >= q_len[i] || span < 1 || y >> 43) {
+                    set_error("mpn_ext_plan_batch: read %d: anchor %lld outside its target or the read, without span, or with unknown flags", i, (long long)j); return -1;
+                }
+            }
+            iv.clear();
+            for (int64_t h = hit_off[i]; h < hit_off[i + 1]; ++h) {
+                const int32_t as = h_as[h], cnt = h_cnt[h];
+                if (cnt < 1 || as < 0 || (int64_t)as + cnt > n_a) { set_error("mpn_ext_plan_batch: read %d: a hit without anchors, or beyond the read's", i); return -1; }
+                for (int32_t j = as + 1; j < as + cnt; ++j) {
+                    const uint64_t *p = a + 2 * (j - 1), *c = a + 2 * j;
+                    if (p[0] >> 32 != c[0] >> 32) { set_error("mpn_ext_plan_batch: read %d: a hit on two targets or strands", i); return -1; }
+                    if ((int32_t)c[0] <= (int32_t)p[0] || (int32_t)c[1] <= (int32_t)p[1]) {
+                        set_error("mpn_ext_plan_batch: read %d: anchor %d of a hit does not lie behind the one before it", i, j); return -1;
+                    }
+                }
+                iv.push_back({as, as + cnt});
+                pregs[(size_t)h] = PlanReg{anchor_off[i], (int32_t)n_a, as, cnt, h_mlen[h], i, q_len[i], h_split_inv[h] ? 1 : 0, 0};
+                cap_need += (int64_t)cnt + 1;   // a hit of cnt anchors has at most cnt + 1 windows
+                cap_dev += (int64_t)cnt + 2;    // (the room the mapper gives it)
+            }
+            std::sort(iv.begin(), iv.end());
+            for (size_t q = 1; q < iv.size(); ++q)
+                if (iv[q].first < iv[q - 1].second) { set_error("mpn_ext_plan_batch: read %d: two hits share an anchor", i); return -1; }
+        }
+    }
+    if (cap_need > win_cap || cap_dev > 0x7fffffff) { set_error("mpn_ext_plan_batch: room for %lld windows needed", (long long)cap_need); return -1; }
+    DevBuf<u128> d_a;
+    DevBuf<int32_t> d_tl, d_janchor;
+    DevBuf<PlanReg> d_pr;
+    DevBuf<PlanSum> d_ps;
+    DevBuf<StitchReg> d_sr;
+    DevBuf<ExtJob> d_jobs;
+    DevBuf<unsigned long long> d_used;
+    if (d_a.upload(reinterpret_cast<const u128 *>(anchors), (size_t)n_anch, st) || d_tl.upload(t_len, (size_t)n_targets, st) ||
+        d_pr.upload(pregs.data(), pregs.size(), st) || d_ps.alloc((size_t)n_hits) || d_sr.alloc((size_t)n_hits) ||
+        d_jobs.alloc((size_t)cap_dev) || d_janchor.alloc((size_t)cap_dev) || d_used.alloc(16))
+        return -1;
+    if (plan_enqueue(opt, k, d_pr.p, n_hits, d_a.p, d_tl.p, d_used.p, d_jobs.p, d_janchor.p, d_sr.p, d_ps.p, grid_cap, st)) return -1;
+    std::vector<StitchReg> sregs((size_t)n_hits);
+    std::vector<PlanSum> psum((size_t)n_hits);
+    unsigned long long used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (d_sr.download(sregs.data(), sregs.size(), st) || d_ps.download(psum.data(), psum.size(), st) || d_used.download(used, 8, st) ||
+        d_a.download(reinterpret_cast<u128 *>(anchors_out), (size_t)n_anch, st))
+        return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    const int64_t total = (int64_t)used[3];
+    if (total < 0 || total > cap_need) { set_error("mpn_ext_plan_batch: the kernel counted %lld windows, %lld at most expected", (long long)total, (long long)cap_need); return -1; }
+    int64_t sum = 0;
+    for (int h = 0; h < n_hits; ++h) {
+        const StitchReg &s = sregs[(size_t)h];
+        if (s.n_jobs < 0 || s.n_jobs > pregs[(size_t)h].cnt + 1 || s.first_job < 0 || (int64_t)s.first_job + s.n_jobs > total) {
+            set_error("mpn_ext_plan_batch: hit %d: windows [%d, +%d) of %lld", h, s.first_job, s.n_jobs, (long long)total); return -1;
+        }
+        sum += s.n_jobs;
+    }
+    if (sum != total) { set_error("mpn_ext_plan_batch: the hits hold %lld windows, the counter %lld", (long long)sum, (long long)total); return -1; }
+    std::vector<ExtJob> jobs((size_t)total + 1);
+    std::vector<int32_t> janchor((size_t)total + 1);
+    if (total > 0) {
+        if (d_jobs.download(jobs.data(), (size_t)total, st) || d_janchor.download(janchor.data(), (size_t)total, st)) return -1;
+        MPN_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    int64_t w = 0;
+    for (int h = 0; h < n_hits; ++h) {
+        const StitchReg &s = sregs[(size_t)h];
+        int32_t *o = hits_out + (size_t)h * 11;
+        o[0] = s.n_jobs; o[1] = psum[(size_t)h].as1; o[2] = psum[(size_t)h].cnt1; o[3] = s.qs; o[4] = s.rs; o[5] = s.qe; o[6] = s.re; o[7] = s.qs0;
+        o[8] = s.qe0; o[9] = s.rid; o[10] = s.rev;
+        for (int j = 0; j < s.n_jobs; ++j, ++w) {
+            const ExtJob &jb = jobs[(size_t)s.first_job + j];
+            int32_t *q = win_out + (size_t)w * 13;
+            q[0] = jb.read; q[1] = jb.rid; q[2] = jb.rev; q[3] = jb.qs; q[4] = jb.qlen; q[5] = jb.ts; q[6] = jb.tlen; q[7] = jb.reversed; q[8] = jb.w;
+            q[9] = jb.zdrop; q[10] = jb.end_bonus; q[11] = jb.flag; q[12] = janchor[(size_t)s.first_job + j];
+        }
+    }
+    *n_win = w;
     return 0;
 }

@@ -131,6 +131,9 @@ def _bind():
         lib.mpn_hit_select_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, ct.c_int32, P, ct.POINTER(ct.c_char_p), P, P, P, P, P, P, P, P, P, P,
                                              ct.c_int32, ct.c_int32, ct.c_int32, P, P, P, P]
         lib.mpn_hit_select_batch.restype = ct.c_int
+        lib.mpn_ext_plan_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, ct.c_int32, P, ct.c_int32, P, P, P, P, P, P, P, P, ct.c_int32, P, ct.c_int64,
+                                           P, P, P]
+        lib.mpn_ext_plan_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
         lib.mpn_map_last_stats_ex.argtypes = [P, ct.c_int32]
@@ -728,6 +731,37 @@ def hit_select_batch(opt, k, q_len, names, chain_off, u, recs, anchor_off, ancho
                                   hits.ctypes.data, sq.ctypes.data)
     _ffi.check(rc, 'mpn_hit_select_batch')
     return n_regs, n_a, hits[:int(n_regs.sum())], (sq[:int(n_a.sum())] if opt.with_cigar else None)
+
+
+PLAN_HIT_KEYS = ('n_jobs', 'as1', 'cnt1', 'qs', 'rs', 'qe', 're', 'qs0', 'qe0', 'rid', 'rev')
+PLAN_WIN_KEYS = ('read', 'rid', 'rev', 'qs', 'qlen', 'ts', 'tlen', 'reversed', 'w', 'zdrop', 'end_bonus', 'flag', 'anchor')
+
+
+def ext_plan_batch(opt, k, t_len, q_len, anchor_off, anchors, hit_off, h_as, h_cnt, h_mlen, h_split_inv, grid_cap=0):
+    """The extension planning stage on arbitrary hits (mpn_ext_plan_batch).  t_len: target lengths.  CSR over reads: anchor_off[n + 1]
+    into anchors uint64 [total, 2] (x, y; flag bits 40..42 of y allowed), hit_off[n + 1] into the per-hit arrays h_as, h_cnt, h_mlen,
+    h_split_inv.  grid_cap 0 = the mapper's grid, else at most that many blocks.  -> (hits int32 [n_hits, 11] in PLAN_HIT_KEYS order, windows
+    int32 [sum n_jobs, 13] in PLAN_WIN_KEYS order, hit after hit in input order, anchors uint64 [total, 2] as the kernel left them)."""
+    lib = _bind()
+    n = len(q_len)
+    c = lambda v, t: np.ascontiguousarray(v, dtype=t)  # noqa: E731
+    t_len, q_len, anchor_off, hit_off = c(t_len, np.int32), c(q_len, np.int32), c(anchor_off, np.int64), c(hit_off, np.int64)
+    h_as, h_cnt, h_mlen, h_split_inv = (c(v, np.int32) for v in (h_as, h_cnt, h_mlen, h_split_inv))
+    anchors = c(anchors, np.uint64).reshape(-1, 2)
+    assert len(anchor_off) == n + 1 and len(hit_off) == n + 1
+    n_anch, n_hits = (int(anchor_off[-1]), int(hit_off[-1])) if n else (0, 0)
+    assert len(anchors) == n_anch and all(len(v) == n_hits for v in (h_as, h_cnt, h_mlen, h_split_inv))
+    win_cap = int(np.maximum(h_cnt.astype(np.int64), 0).sum()) + n_hits
+    hits = np.zeros((n_hits + 1, 11), dtype=np.int32)
+    wins = np.zeros((win_cap + 1, 13), dtype=np.int32)
+    left = np.zeros((n_anch + 1, 2), dtype=np.uint64)
+    n_win = ct.c_int64(0)
+    rc = lib.mpn_ext_plan_batch(ct.byref(opt), int(k), len(t_len), t_len.ctypes.data, n, q_len.ctypes.data, anchor_off.ctypes.data,
+                                anchors.ctypes.data, hit_off.ctypes.data, h_as.ctypes.data, h_cnt.ctypes.data, h_mlen.ctypes.data,
+                                h_split_inv.ctypes.data, int(grid_cap), hits.ctypes.data, win_cap, ct.addressof(n_win), wins.ctypes.data,
+                                left.ctypes.data)
+    _ffi.check(rc, 'mpn_ext_plan_batch')
+    return hits[:n_hits], wins[:n_win.value], left[:n_anch]
 
 
 STAT_NAMES = {0: 'bases', 1: 'minimizers', 2: 'anchors', 3: 'chains', 4: 'dp_jobs', 5: 'dp_cells', 6: 'alignments',

@@ -82,6 +82,9 @@ def lib():
         L.mmo_hits_from_chains.argtypes = [ct.POINTER(Opt), ct.c_int, ct.c_char_p, ct.c_int32, ct.c_int32, ct.c_void_p, ct.c_void_p,
                                            ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32)]
         L.mmo_hits_from_chains.restype = ct.POINTER(Reg)
+        L.mmo_plan_hit.argtypes = [ct.POINTER(Opt), ct.c_int, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32,
+                                   ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int32]
+        L.mmo_plan_hit.restype = ct.c_int32
         _lib = L
     return _lib
 
@@ -266,3 +269,20 @@ def hits_from_chains(opt, k, name, qlen, u, a):
     if regs:
         lib().mmo_free(regs)
     return out, a[:n_a.value].copy()
+
+
+PLAN_HIT_KEYS = ('as1', 'cnt1', 'qs', 'rs', 'qe', 're', 'qs0', 'qe0', 'rid', 'rev')
+PLAN_WIN_KEYS = ('qs', 'qlen', 'ts', 'tlen', 'reversed', 'w', 'zdrop', 'end_bonus', 'flag', 'anchor', 'refused')
+
+
+def plan_hit(opt, k, tlen, qlen, as_, cnt, mlen, split_inv, a):
+    """the planning half of the oracle's align1 on the hit a[as_ : as_ + cnt] of one read's squeezed anchors a (uint64 [n_a, 2], changed
+    in place: SEED_IGNORE marks) -> (dict of PLAN_HIT_KEYS, list of window dicts of PLAN_WIN_KEYS)"""
+    assert a.dtype == np.uint64 and a.flags['C_CONTIGUOUS'] and a.ndim == 2 and a.shape[1] == 2
+    out = np.zeros(10, dtype=np.int32)
+    win = np.zeros((cnt + 2, 12), dtype=np.int32)
+    n = lib().mmo_plan_hit(ct.byref(opt), k, tlen, qlen, as_, cnt, mlen, split_inv, len(a), a.ctypes.data, out.ctypes.data, win.ctypes.data,
+                           len(win))
+    assert n >= 0
+    return ({key: int(v) for key, v in zip(PLAN_HIT_KEYS, out)},
+            [{key: int(v) for key, v in zip(PLAN_WIN_KEYS, row)} for row in win[:n]])

@@ -1166,10 +1166,16 @@ static void seq_rev(int len, uint8_t *s)
     for (i = 0; i < len >> 1; ++i) { uint8_t t = s[i]; s[i] = s[len - 1 - i], s[len - 1 - i] = t; }
 }
 
+/* a window whose DP matrix would exceed max_sw_mat gets no DP: it counts as z-dropped at its start */
+static int pair_refused(const mmo_opt *opt, int qlen, int tlen)
+{
+    return opt->max_sw_mat > 0 && (int64_t)tlen * qlen > opt->max_sw_mat;
+}
+
 static void align_pair(const mmo_opt *opt, int qlen, const uint8_t *qseq, int tlen, const uint8_t *tseq, int w,
                        int end_bonus, int zdrop, int flag, mmo_ez *ez)
 {
-    if (opt->max_sw_mat > 0 && (int64_t)tlen * qlen > opt->max_sw_mat) { ez_reset(ez); ez->zdropped = 1; return; }
+    if (pair_refused(opt, qlen, tlen)) { ez_reset(ez); ez->zdropped = 1; return; }
     mmo_extd2(qlen, qseq, tlen, tseq, (int8_t)opt->a, (int8_t)-opt->b, (int8_t)-opt->sc_ambi, (int8_t)opt->q,
               (int8_t)opt->e, (int8_t)opt->q2, (int8_t)opt->e2, w, zdrop, end_bonus, flag, ez);
 }
@@ -1246,21 +1252,15 @@ static int test_zdrop(const mmo_opt *opt, const uint8_t *qseq, const uint8_t *ts
     return max_zdrop > opt->zdrop ? 1 : 0;
 }
 
-static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qseq0[2], mmo_reg *r, mmo_reg *r2,
-                   int n_a, mm128 *a, mmo_ez *ez)
-{
-    int32_t rid = a[r->as].x << 1 >> 33, rev = a[r->as].x >> 63, as1, cnt1;
-    uint8_t *tseq, *qseq;
-    int32_t i, l, bw, dropped = 0, rs0, re0, qs0, qe0;
-    int32_t rs, re, qs, qe, rs1, qs1, re1, qe1;
-    const int32_t tlen_all = mi->len[rid], kh = mi->k >> 1;
-    int8_t mat[25];
+/* Everything mm_align1 does before its first ksw call: the anchors that survive mm_fix_bad_ends, the SEED_IGNORE marks of
+ * mm_filter_bad_seeds (set in a[]), the k-mer centres of the first and last anchor kept, and the region the two end extensions
+ * may reach (from the hit's neighbours in the squeezed list and the gap limits). */
+typedef struct { int32_t as1, cnt1, rs, qs, re, qe, rs0, qs0, re0, qe0; } plan_lim;
 
-    r2->cnt = 0;
-    if (r->cnt == 0) return;
-    for (i = 0; i < 4; ++i) { int j; for (j = 0; j < 4; ++j) mat[i * 5 + j] = i == j ? opt->a : -opt->b; mat[i * 5 + 4] = -opt->sc_ambi; }
-    for (i = 0; i < 5; ++i) mat[20 + i] = -opt->sc_ambi;
-    bw = (int)(opt->bw * 1.5 + 1.);
+static void plan_limits(const mmo_opt *opt, int k, int32_t tlen_all, int qlen, const mmo_reg *r, int n_a, mm128 *a, plan_lim *p)
+{
+    int32_t as1, cnt1, i, l, rs0, re0, qs0, qe0, rs, re, qs, qe, rs1, qs1, re1, qe1;
+    const int32_t kh = k >> 1;
 
     fix_bad_ends(r, a, opt->bw, opt->min_chain_score * 2, &as1, &cnt1);
     filter_bad_seeds(as1, cnt1, a, 10, 40, opt->max_gap >> 1, 10);
@@ -1318,6 +1318,30 @@ static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qse
         re1 = re1 < re + l ? re1 : re + l;
         re0 = re0 > re1 ? re0 : re1;
     } else re0 = re, qe0 = qe;
+    p->as1 = as1, p->cnt1 = cnt1, p->rs = rs, p->qs = qs, p->re = re, p->qe = qe;
+    p->rs0 = rs0, p->qs0 = qs0, p->re0 = re0, p->qe0 = qe0;
+}
+
+static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qseq0[2], mmo_reg *r, mmo_reg *r2,
+                   int n_a, mm128 *a, mmo_ez *ez)
+{
+    int32_t rid = a[r->as].x << 1 >> 33, rev = a[r->as].x >> 63, as1, cnt1;
+    uint8_t *tseq, *qseq;
+    int32_t i, bw, dropped = 0, rs0, re0, qs0, qe0;
+    int32_t rs, re, qs, qe, rs1, qs1, re1, qe1;
+    const int32_t tlen_all = mi->len[rid], kh = mi->k >> 1;
+    int8_t mat[25];
+    plan_lim pl;
+
+    r2->cnt = 0;
+    if (r->cnt == 0) return;
+    for (i = 0; i < 4; ++i) { int j; for (j = 0; j < 4; ++j) mat[i * 5 + j] = i == j ? opt->a : -opt->b; mat[i * 5 + 4] = -opt->sc_ambi; }
+    for (i = 0; i < 5; ++i) mat[20 + i] = -opt->sc_ambi;
+    bw = (int)(opt->bw * 1.5 + 1.);
+
+    plan_limits(opt, mi->k, tlen_all, qlen, r, n_a, a, &pl);
+    as1 = pl.as1, cnt1 = pl.cnt1, rs = pl.rs, qs = pl.qs, re = pl.re, qe = pl.qe;
+    rs0 = pl.rs0, qs0 = pl.qs0, re0 = pl.re0, qe0 = pl.qe0;
 
     tseq = (uint8_t *)malloc((size_t)(re0 - rs0 > 0 ? re0 - rs0 : 1));
 
@@ -1386,6 +1410,51 @@ static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qse
         update_extra(r, &qseq0[r->rev][qs1], tseq, mat, (int8_t)opt->q, (int8_t)opt->e);
     }
     free(tseq);
+}
+
+/* The windows align1 hands to align_pair for one hit when no window z-drops, without any DP: plan_limits, then the left
+ * extension, the gap fills (the fill loop's continue, test and bw1 rules) and the right extension.  a[n_a]: the read's squeezed
+ * anchors (SEED_IGNORE marks are set in place); the hit is a[as .. as + cnt) with approximate match length mlen.
+ * out10 = as1, cnt1, qs, rs, qe, re, qs0, qe0, rid, rev.  Window j at win[12 * j ..] = qs, qlen, ts, tlen, reversed, w, zdrop,
+ * end_bonus, flag, anchor (index in the trimmed hit of the anchor a fill ends at, -1 for an extension), refused (what align_pair
+ * decides by max_sw_mat), 0.  Returns the number of windows (at most cnt + 1), or -1 if cap is too small. */
+int32_t mmo_plan_hit(const mmo_opt *opt, int k, int32_t tlen_all, int32_t qlen, int32_t as, int32_t cnt, int32_t mlen, int32_t split_inv,
+                     int32_t n_a, mm128 *a, int32_t *out10, int32_t *win, int32_t cap)
+{
+    mmo_reg r;
+    plan_lim pl;
+    int32_t i, n = 0, rs, qs, re, qe;
+    const int32_t kh = k >> 1, bw = (int)(opt->bw * 1.5 + 1.);
+#define MMO_WIN(QS, QL, TS, TL, REV, W, ZD, EB, FL, AN) do { \
+        int32_t *w_ = win + 12 * n; \
+        if (n >= cap) return -1; \
+        w_[0] = (QS), w_[1] = (QL), w_[2] = (TS), w_[3] = (TL), w_[4] = (REV), w_[5] = (W), w_[6] = (ZD), w_[7] = (EB), w_[8] = (FL), w_[9] = (AN); \
+        w_[10] = pair_refused(opt, (QL), (TL)), w_[11] = 0; \
+        ++n; \
+    } while (0)
+    memset(&r, 0, sizeof(r));
+    r.as = as, r.cnt = cnt, r.mlen = mlen, r.split_inv = (uint32_t)split_inv;
+    plan_limits(opt, k, tlen_all, qlen, &r, n_a, a, &pl);
+    rs = pl.rs, qs = pl.qs, re = pl.re, qe = pl.qe;
+    out10[0] = pl.as1, out10[1] = pl.cnt1, out10[2] = qs, out10[3] = rs, out10[4] = qe, out10[5] = re, out10[6] = pl.qs0, out10[7] = pl.qe0;
+    out10[8] = (int32_t)(a[as].x << 1 >> 33), out10[9] = (int32_t)(a[as].x >> 63);
+    if (qs > 0 && rs > 0)
+        MMO_WIN(pl.qs0, qs - pl.qs0, pl.rs0, rs - pl.rs0, 1, bw, r.split_inv ? opt->zdrop_inv : opt->zdrop, opt->end_bonus,
+                MMO_EZ_EXTZ_ONLY | MMO_EZ_RIGHT | MMO_EZ_REV_CIGAR, -1);
+    for (i = 1; i < pl.cnt1; ++i) {
+        if ((a[pl.as1 + i].y & (MMO_SEED_IGNORE | MMO_SEED_TANDEM)) && i != pl.cnt1 - 1) continue;
+        re = (int32_t)a[pl.as1 + i].x - kh, qe = (int32_t)a[pl.as1 + i].y - kh;
+        if (i == pl.cnt1 - 1 || (a[pl.as1 + i].y & MMO_SEED_LONG_JOIN) || (qe - qs >= opt->min_ksw_len && re - rs >= opt->min_ksw_len)) {
+            int bw1 = bw;
+            if (a[pl.as1 + i].y & MMO_SEED_LONG_JOIN) bw1 = qe - qs > re - rs ? qe - qs : re - rs;
+            MMO_WIN(qs, qe - qs, rs, re - rs, 0, bw1, opt->zdrop, -1, MMO_EZ_APPROX_MAX, i);
+            rs = re, qs = qe;
+        }
+    }
+    if (qe < pl.qe0 && re < pl.re0)
+        MMO_WIN(qe, pl.qe0 - qe, re, pl.re0 - re, 0, bw, opt->zdrop, opt->end_bonus, MMO_EZ_EXTZ_ONLY, -1);
+#undef MMO_WIN
+    return n;
 }
 
 /* the inverted segment between the two halves of a hit that was split at an inversion (mm_align1_inv): a local alignment of

@@ -120,6 +120,15 @@ void mmo_fix_update(uint32_t *cigar, int32_t n_cigar, const uint8_t *qseq, const
 mmo_reg *mmo_hits_from_chains(const mmo_opt *o, int k, const char *name, int32_t qlen, int32_t n_u, const uint64_t *u, mm128 *a,
                               int32_t *n_regs, int32_t *n_a);
 
+/* the static planning half of align1 (fix_bad_ends, filter_bad_seeds, the extension limits; the function align1 itself calls) on
+ * a caller's hit a[as .. as + cnt) of the squeezed list a[n_a] of a read of qlen bases on a target of tlen_all, then the windows
+ * align1 would hand to align_pair if none z-dropped, without DP.  SEED_IGNORE marks are left in a[].  out10 = as1, cnt1, qs, rs,
+ * qe, re, qs0, qe0, rid, rev; window j at win[12 * j ..] = qs, qlen, ts, tlen, reversed, w, zdrop, end_bonus, flag, anchor (a fill's
+ * last anchor, counted from as1; -1 for an extension), refused (align_pair's max_sw_mat rule), 0.  Returns the window count
+ * (<= cnt + 1) or -1 if cap windows are too few. */
+int32_t mmo_plan_hit(const mmo_opt *opt, int k, int32_t tlen_all, int32_t qlen, int32_t as, int32_t cnt, int32_t mlen, int32_t split_inv,
+                     int32_t n_a, mm128 *a, int32_t *out10, int32_t *win, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif
