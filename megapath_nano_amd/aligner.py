@@ -498,6 +498,23 @@ def _join_taxonomy(align_list, sequence_tax):
     return joined
 
 
+def align_table(batches, *, assembly_metadata, global_options, target_assembly_list):
+    """What Align() makes of its mapped batches (aligner.py:291-335): the rows of all batches, filtered by sequence length and
+    min_alignment_score, joined with the taxonomy of target_assembly_list when there is one, and one tiebreaker per surviving row
+    drawn from Python's `random` as the caller seeded it.  Shared by Align() and placement.placement_to_assembly."""
+    frames = [_frame_of(b) for b in batches if len(b.cols['read_idx'])]
+    if frames:
+        table = pandas.concat(frames, ignore_index=True)[list(list_col)]
+    else:
+        table = pandas.DataFrame({c: pandas.Series(dtype=(str if c in _TEXT_COLS else np.int64)) for c in list_col})
+    keep = (table['sequence_length'].to_numpy() > 0) & (table['alignment_score'].to_numpy() >= global_options['min_alignment_score'])
+    align_list = table[keep]                                                                          # aligner.py:311-312
+    if target_assembly_list is not None and len(target_assembly_list['assembly_id']) > 0:
+        align_list = _join_taxonomy(align_list, assembly_metadata.get_sequence_tax_id(assembly_list=target_assembly_list))
+    # one random.random() per surviving row, in row order (aligner.py:334-335)
+    return align_list.assign(alignment_score_tiebreaker=random_block(random, align_list.shape[0]))
+
+
 def Align(*, assembly_metadata, global_options, temp_dir_name, log_file, query_filename_list=None,
           query_assembly_list=None, target_filename_list=None, target_assembly_list=None, aligner_options=None,
           paf_path_and_prefix=None, mapping_only=False, module_option='', AMR_output_folder='', align_concat_fa=False,
@@ -536,14 +553,4 @@ def Align(*, assembly_metadata, global_options, temp_dir_name, log_file, query_f
         batches, header = map_files(target_paths, query_paths, options, want_paf=False, want_sam=False, want_cols=True,
                                     read_batch_bases=batch_bases, cache_key=cache_key)
 
-    frames = [_frame_of(b) for b in batches if len(b.cols['read_idx'])]
-    if frames:
-        table = pandas.concat(frames, ignore_index=True)[list(list_col)]
-    else:
-        table = pandas.DataFrame({c: pandas.Series(dtype=(str if c in _TEXT_COLS else np.int64)) for c in list_col})
-    keep = (table['sequence_length'].to_numpy() > 0) & (table['alignment_score'].to_numpy() >= global_options['min_alignment_score'])
-    align_list = table[keep]                                                                          # aligner.py:311-312
-    if target_assembly_list is not None and len(target_assembly_list['assembly_id']) > 0:
-        align_list = _join_taxonomy(align_list, assembly_metadata.get_sequence_tax_id(assembly_list=target_assembly_list))
-    # one random.random() per surviving row, in row order (aligner.py:334-335)
-    return align_list.assign(alignment_score_tiebreaker=random_block(random, align_list.shape[0]))
+    return align_table(batches, assembly_metadata=assembly_metadata, global_options=global_options, target_assembly_list=target_assembly_list)

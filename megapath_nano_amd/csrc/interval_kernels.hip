@@ -4,6 +4,7 @@
 // a record is 24 bytes and a radix pass reads and writes it once (48 B per record and pass; constant digits are skipped).
 #include "mpn_common.h"
 #include "../../include/mpn_abundance.h"
+#include "../../include/mpn_reads.h"
 
 #include <cmath>
 #include <cstring>
@@ -909,6 +910,73 @@ __global__ __launch_bounds__(256) void ba_second_kernel(const int32_t *__restric
 
 static int ba_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
 
+// ---- the plan of a read split (include/mpn_reads.h; the gather is in read_split_kernels.hip) -------------------------------------
+// Membership pairs sorted by lo = group << 32 | read.  No segments: the running count of DISTINCT pairs puts each into its place
+// among the output reads (a pair given twice counts once, as nanosplit's set of files per read has it).
+__global__ __launch_bounds__(256) void sp_fill_kernel(const int32_t *__restrict__ read, const int32_t *__restrict__ group, int64_t m, Rec3 *__restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = Rec3{0, (uint64_t)(uint32_t)group[i] << 32 | (uint32_t)read[i], i};
+}
+
+struct SpUniquePass {
+    struct V { int64_t c; int32_t head, pad; };
+    const Rec3 *rec; const int32_t *len; int64_t m; int32_t *out_read, *u_group, *u_len; int64_t *n_out;
+    __device__ static V identity() { return V{0, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return V{a.c + b.c, 0, 0}; }
+    __device__ bool first(int64_t i) const { return i == 0 || rec[i - 1].lo != rec[i].lo; }
+    __device__ V load(int64_t i) const { return V{first(i) ? 1 : 0, 0, 0}; }
+    __device__ void store(int64_t i, const V &inc) const {
+        if (first(i)) {
+            const uint64_t k = rec[i].lo;
+            const int32_t r = (int32_t)(uint32_t)k;
+            out_read[inc.c - 1] = r; u_group[inc.c - 1] = (int32_t)(k >> 32); u_len[inc.c - 1] = len[r];
+        }
+        if (i + 1 == m) n_out[0] = inc.c;
+    }
+};
+
+// Output reads in order; a segment is one group.  The running sum of the lengths gives every read its offset inside its group's
+// block; the last read of a group stores the group's bytes; the first one (and the very last read) close the CSR over the groups
+// they pass, empty ones included.
+struct SpOffsetPass {
+    struct V { int64_t sum; int32_t head, pad; };
+    const int32_t *u_group, *u_len; int64_t n_out; int32_t n_groups; int64_t *rel, *g_bytes, *group_first;
+    __device__ static V identity() { return V{0, 0, 0}; }
+    __device__ static V merge(const V &a, const V &b) { return V{a.sum + b.sum, 0, 0}; }
+    __device__ V load(int64_t j) const { return V{u_len[j], j == 0 || u_group[j - 1] != u_group[j], 0}; }
+    __device__ void store(int64_t j, const V &inc) const {
+        const int32_t g = u_group[j];
+        rel[j] = inc.sum - u_len[j];
+        if (j == 0 || u_group[j - 1] != g)
+            for (int32_t k = j == 0 ? 0 : u_group[j - 1] + 1; k <= g; ++k) group_first[k] = j;
+        if (j + 1 == n_out || u_group[j + 1] != g) g_bytes[g] = inc.sum;
+        if (j + 1 == n_out)
+            for (int32_t k = g + 1; k <= n_groups; ++k) group_first[k] = n_out;
+    }
+};
+
+// one block: group_byte[g] = the sizes of the groups before g, each rounded up to MPN_SPLIT_ALIGN; group_byte[n_groups] = all of them
+__global__ __launch_bounds__(1024) void sp_group_byte_kernel(const int64_t *__restrict__ g_bytes, int32_t n_groups, int64_t *__restrict__ group_byte) {
+    __shared__ int64_t part[1024];
+    const int t = threadIdx.x, per = (n_groups + 1023) / 1024, lo = min(n_groups, t * per), hi = min(n_groups, lo + per);
+    constexpr int64_t A = MPN_SPLIT_ALIGN;
+    int64_t s = 0;
+    for (int k = lo; k < hi; ++k) s += (g_bytes[k] + A - 1) / A * A;
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) { int64_t acc = 0; for (int k = 0; k < 1024; ++k) { const int64_t v = part[k]; part[k] = acc; acc += v; } group_byte[n_groups] = acc; }
+    __syncthreads();
+    int64_t o = part[t];
+    for (int k = lo; k < hi; ++k) { group_byte[k] = o; o += (g_bytes[k] + A - 1) / A * A; }
+}
+
+__global__ __launch_bounds__(256) void sp_out_off_kernel(const int32_t *__restrict__ u_group, const int64_t *__restrict__ rel, const int64_t *__restrict__ group_byte,
+                                                         int64_t n_out, int64_t *__restrict__ out_off) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_out; j += (int64_t)gridDim.x * blockDim.x) out_off[j] = group_byte[u_group[j]] + rel[j];
+}
+
+extern thread_local int64_t tl_split_ns[2];   // read_split_kernels.hip
+
 }  // namespace mpn
 
 using namespace mpn;
@@ -1356,5 +1424,69 @@ extern "C" int mpn_sum_by_key(int64_t n, const int32_t *key, int32_t n_keys, int
     if (ba_scan(BaSumPass{rec, d_cols.p, n, n_cols, n_keys, d_count.p, d_sums.p}, n, st)) return -1;
     if (d_count.download(count, (size_t)n_keys, st) || d_sums.download(sums, (size_t)n_cols * (size_t)n_keys, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int mpn_reads_split_plan(int32_t n, const int32_t *len, int64_t m, const int32_t *mem_read, const int32_t *mem_group, int32_t n_groups,
+                                    int64_t out_cap, int64_t *n_out, int32_t *out_read, int64_t *group_first, int64_t *out_off,
+                                    int64_t *group_byte, int64_t *out_bytes) {
+    tl_split_ns[0] = 0;
+    if (n < 0 || m < 0 || m >= ((int64_t)1 << 31) || n_groups < 0 || out_cap < 0 || !n_out || !group_first || !group_byte || !out_bytes || (n > 0 && !len) ||
+        (m > 0 && (!mem_read || !mem_group || !out_read || !out_off))) {
+        set_error("mpn_reads_split_plan: bad arguments (n, n_groups, out_cap >= 0, m in [0, 2^31), no NULL array that is needed)");
+        return -1;
+    }
+    for (int32_t i = 0; i < n; ++i)
+        if (len[i] < 0) { set_error("mpn_reads_split_plan: read %d has the negative length %d", (int)i, (int)len[i]); return -1; }
+    for (int64_t i = 0; i < m; ++i)
+        if (mem_read[i] < 0 || mem_read[i] >= n || mem_group[i] < 0 || mem_group[i] >= n_groups) {
+            set_error("mpn_reads_split_plan: pair %lld = (read %d, group %d) outside [0, %d) x [0, %d)", (long long)i, (int)mem_read[i], (int)mem_group[i], (int)n, (int)n_groups);
+            return -1;
+        }
+    *n_out = 0;
+    *out_bytes = MPN_SPLIT_ALIGN;
+    for (int32_t g = 0; g <= n_groups; ++g) { group_first[g] = 0; group_byte[g] = 0; }
+    if (m == 0) return 0;
+
+    hipStream_t st = 0;
+    DevBuf<int32_t> d_len, d_read, d_group, d_out_read, u_group, u_len;
+    DevBuf<int64_t> d_n, rel, g_bytes, d_first, d_gbyte, d_off;
+    DevBuf<Rec3> a, b;
+    if (d_len.upload(len, (size_t)n, st) || d_read.upload(mem_read, (size_t)m, st) || d_group.upload(mem_group, (size_t)m, st) || a.alloc((size_t)m) || b.alloc((size_t)m) ||
+        d_out_read.alloc((size_t)m) || u_group.alloc((size_t)m) || u_len.alloc((size_t)m) || d_n.alloc(1) || rel.alloc((size_t)m) || g_bytes.alloc((size_t)n_groups) ||
+        g_bytes.zero(st) || d_first.alloc((size_t)n_groups + 1) || d_gbyte.alloc((size_t)n_groups + 1) || d_off.alloc((size_t)m)) return -1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    MPN_HIP_CHECK(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("mpn_reads_split_plan: hipEventCreate failed"); return -1; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    (void)hipEventRecord(e0, st);
+    hipLaunchKernelGGL(sp_fill_kernel, dim3(ba_grid(m)), dim3(256), 0, st, (const int32_t *)d_read.p, (const int32_t *)d_group.p, m, a.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    // digits that no record has: all of hi, the bytes of the read above n - 1 and those of the group above n_groups - 1
+    uint32_t skip = 0xff00;
+    for (int p = 0; p < 4; ++p) {
+        if (((uint64_t)(n - 1) >> (8 * p)) == 0) skip |= 1u << p;
+        if (((uint64_t)(n_groups - 1) >> (8 * p)) == 0) skip |= 1u << (4 + p);
+    }
+    Rec3 *rec = nullptr;
+    if (radix_sort_rec3(a.p, b.p, m, &rec, st, skip)) return -1;
+    if (ba_scan(SpUniquePass{rec, d_len.p, m, d_out_read.p, u_group.p, u_len.p, d_n.p}, m, st)) return -1;
+    int64_t k = 0;
+    if (d_n.download(&k, 1, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    if (k < 1 || k > m) { set_error("mpn_reads_split_plan: %lld distinct pairs out of %lld", (long long)k, (long long)m); return -1; }
+    if (k > out_cap) { set_error("mpn_reads_split_plan: %lld output reads, room for %lld", (long long)k, (long long)out_cap); return -1; }
+    if (ba_scan(SpOffsetPass{u_group.p, u_len.p, k, n_groups, rel.p, g_bytes.p, d_first.p}, k, st)) return -1;
+    hipLaunchKernelGGL(sp_group_byte_kernel, dim3(1), dim3(1024), 0, st, (const int64_t *)g_bytes.p, n_groups, d_gbyte.p);
+    hipLaunchKernelGGL(sp_out_off_kernel, dim3(ba_grid(k)), dim3(256), 0, st, (const int32_t *)u_group.p, (const int64_t *)rel.p, (const int64_t *)d_gbyte.p, k, d_off.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    (void)hipEventRecord(e1, st);
+    if (d_out_read.download(out_read, (size_t)k, st) || d_off.download(out_off, (size_t)k, st) || d_first.download(group_first, (size_t)n_groups + 1, st) ||
+        d_gbyte.download(group_byte, (size_t)n_groups + 1, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) tl_split_ns[0] = (int64_t)((double)ms * 1e6);
+    *n_out = k;
+    *out_bytes = group_byte[n_groups] + MPN_SPLIT_ALIGN;
     return 0;
 }

@@ -142,3 +142,60 @@ def subseq(in_path, names, out):
     finally:
         stream.close()
     return n
+
+
+def read_split_list(path):
+    """The read list of nanosplit: `read_id <whitespace> output_path` lines -> (dict name -> sorted list of output indices, output
+    paths in the order of their first mention).  A pair given twice counts once.  A line without two fields raises ValueError
+    (the reference tool would silently reuse the previous pair: DESIGN section 6)."""
+    files, index = {}, {}
+    with open(path, 'rb') as f:
+        for no, raw in enumerate(f, 1):
+            words = raw.split()
+            if len(words) < 2:
+                raise ValueError(f'{path}:{no}: a read id and an output path expected, got {raw[:40]!r}')
+            name, out = words[0].decode(), os.fsdecode(words[1])
+            files.setdefault(name, set()).add(index.setdefault(out, len(index)))
+    return {n: sorted(s) for n, s in files.items()}, list(index)
+
+
+def nanosplit(read_list_path, in_paths, device=None):
+    """The reference's bin/tools/nanosplit: every record of in_paths (FASTA / FASTQ, plain or gzip) is written to each output file
+    its name is listed for, in the order of the input files and of the records in them; every listed output file is created.
+    Names are expanded to record indices here; sequences and qualities are regrouped by mapper.split_reads -- on the GPU, or with
+    device=False by the numpy statement of the same plan -- and the files are formatted from the group-contiguous buffers.
+    -> list of (output path, records written)"""
+    from . import mapper
+    wanted, out_paths = read_split_list(read_list_path)
+    heads, seqs, quals, mem_read, mem_group = [], [], [], [], []
+    for path in in_paths:
+        kind, stream = open_once(path)
+        try:
+            if kind == 'index':
+                raise ValueError(f'{path}: a saved index, not sequences')
+            for name, comment, seq, qual in iter_fastx_full(stream):
+                groups = wanted.get(name)
+                if groups is None:
+                    continue
+                mem_read += [len(seqs)] * len(groups)
+                mem_group += groups
+                heads.append(name.encode() + ((b' ' + comment) if comment else b''))
+                seqs.append(seq)
+                quals.append(qual)
+        finally:
+            stream.close()
+    packed = mapper.PackedReads([''] * len(seqs), seqs, quals=quals)
+    split = mapper.split_reads(packed, mem_read, mem_group, len(out_paths), device=True if device is None else device)
+    res, written = split.res, []
+    for g, out_path in enumerate(out_paths):
+        lo, hi = int(res['group_first'][g]), int(res['group_first'][g + 1])
+        with open(out_path, 'wb') as out:
+            for j in range(lo, hi):
+                r, a = int(res['out_read'][j]), int(res['out_off'][j])
+                b = a + int(packed.lens[r])
+                if quals[r] is not None:
+                    out.write(b'@' + heads[r] + b'\n' + res['seqs'][a:b].tobytes() + b'\n+\n' + res['quals'][a:b].tobytes() + b'\n')
+                else:
+                    out.write(b'>' + heads[r] + b'\n' + res['seqs'][a:b].tobytes() + b'\n')
+        written.append((out_path, hi - lo))
+    return written

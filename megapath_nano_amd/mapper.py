@@ -136,6 +136,12 @@ def _bind():
         lib.mpn_ext_plan_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
+        lib.mpn_reads_split_plan.argtypes = [ct.c_int32, P, ct.c_int64, P, P, ct.c_int32, ct.c_int64, P, P, P, P, P, P]
+        lib.mpn_reads_split_plan.restype = ct.c_int
+        lib.mpn_reads_split_gather.argtypes = [ct.c_int32, P, P, ct.c_int64, P, P, ct.c_int32, ct.c_int64, P, P, ct.c_int64, P, P, ct.c_int64, P, P]
+        lib.mpn_reads_split_gather.restype = ct.c_int
+        lib.mpn_reads_split_last_ns.argtypes = [ct.c_int32]
+        lib.mpn_reads_split_last_ns.restype = ct.c_int64
         lib.mpn_map_last_stats_ex.argtypes = [P, ct.c_int32]
         lib.mpn_map_last_stats_ex.restype = ct.c_int32
         _bound = True
@@ -374,16 +380,16 @@ class PackedReads:
         self._finish(device)
 
     @classmethod
-    def from_arrays(cls, names, buf, off, lens, dev=None):
+    def from_arrays(cls, names, buf, off, lens, dev=None, qbuf=None):
         """buf: concatenated ASCII (uint8, padded to a 4-byte multiple past the last base), off int64, lens int32 (host
-        numpy); dev: the same three as torch tensors already resident in HBM, or None."""
+        numpy); dev: the same three as torch tensors already resident in HBM, or None; qbuf: qualities laid out like buf, or None."""
         self = cls.__new__(cls)
         self.n = len(lens)
         self.names = list(names)
         self.buf = np.ascontiguousarray(buf, dtype=np.uint8)
         self.off = np.ascontiguousarray(off, dtype=np.int64)
         self.lens = np.ascontiguousarray(lens, dtype=np.int32)
-        self.qbuf = None
+        self.qbuf = None if qbuf is None else np.ascontiguousarray(qbuf, dtype=np.uint8)
         self._finish(None)
         self.dev = dev
         return self
@@ -421,6 +427,165 @@ class PackedReads:
             out.qbuf[:b - a] = self.qbuf[a:b]
         out._finish(self.dev[0].device if self.dev is not None else None)
         return out
+
+
+# ---- regrouping a batch by (read, group) pairs: include/mpn_reads.h ---------------------------------------------------------------
+SPLIT_ALIGN = 16
+PLAN_KEYS = ('n_out', 'out_read', 'group_first', 'out_off', 'group_byte', 'out_bytes')
+
+
+def _split_args(lens, mem_read, mem_group):
+    c = lambda v, t: np.ascontiguousarray(v, dtype=t)  # noqa: E731
+    lens, mem_read, mem_group = c(lens, np.int32), c(mem_read, np.int32), c(mem_group, np.int32)
+    if mem_read.shape != mem_group.shape or mem_read.ndim != 1:
+        raise ValueError('mem_read and mem_group: two 1-d arrays of one length')
+    return lens, mem_read, mem_group
+
+
+def host_split_plan(lens, mem_read, mem_group, n_groups):
+    """The plan of a split as a numpy statement (what mpn_reads_split_plan computes on the device) -> dict of PLAN_KEYS."""
+    lens, mem_read, mem_group = _split_args(lens, mem_read, mem_group)
+    n, n_groups = len(lens), int(n_groups)
+    if (lens < 0).any() or ((mem_read < 0) | (mem_read >= n)).any() or ((mem_group < 0) | (mem_group >= n_groups)).any():
+        raise ValueError('split: a negative length, or a pair outside [0, n) x [0, n_groups)')
+    key = np.unique(mem_group.astype(np.int64) << 32 | mem_read.astype(np.int64))     # sorted by (group, read), a pair once
+    out_group, out_read = (key >> 32).astype(np.int64), (key & 0xffffffff).astype(np.int32)
+    group_first = np.searchsorted(out_group, np.arange(n_groups + 1)).astype(np.int64)
+    out_len = lens[out_read].astype(np.int64)
+    g_bytes = np.bincount(out_group, weights=None if not len(key) else out_len, minlength=n_groups).astype(np.int64) if n_groups else np.zeros(0, np.int64)
+    group_byte = np.zeros(n_groups + 1, dtype=np.int64)
+    group_byte[1:] = np.cumsum((g_bytes + SPLIT_ALIGN - 1) // SPLIT_ALIGN * SPLIT_ALIGN)
+    before = np.cumsum(out_len) - out_len                                               # bytes of all earlier output reads
+    out_off = group_byte[out_group] + before - (before[group_first[out_group]] if len(key) else 0)
+    return dict(n_out=len(key), out_read=out_read, group_first=group_first, out_off=out_off.astype(np.int64), group_byte=group_byte,
+                out_bytes=int(group_byte[n_groups]) + SPLIT_ALIGN)
+
+
+def host_split_gather(plan, buf, off, lens, qbuf=None):
+    """-> (bases uint8[out_bytes], qualities or None): the reads of the plan copied into place, every other byte 0"""
+    outs = []
+    for src in (buf, qbuf):
+        if src is None:
+            outs.append(None)
+            continue
+        o = np.zeros(plan['out_bytes'], dtype=np.uint8)
+        for r, d in zip(plan['out_read'], plan['out_off']):
+            o[d:d + lens[r]] = src[off[r]:off[r] + lens[r]]
+        outs.append(o)
+    return outs[0], outs[1]
+
+
+def host_split_reads(buf, off, lens, mem_read, mem_group, n_groups, qbuf=None):
+    """Reads regrouped by (read, group) pairs with nanosplit's semantics, on the host -> the plan's dict plus 'seqs' and 'quals'."""
+    plan = host_split_plan(lens, mem_read, mem_group, n_groups)
+    plan['seqs'], plan['quals'] = host_split_gather(plan, buf, off, lens, qbuf)
+    return plan
+
+
+def device_split_plan(lens, mem_read, mem_group, n_groups, out_cap=None):
+    """mpn_reads_split_plan -> dict of PLAN_KEYS"""
+    lib = _bind()
+    lens, mem_read, mem_group = _split_args(lens, mem_read, mem_group)
+    n, m, n_groups = len(lens), len(mem_read), int(n_groups)
+    cap = m if out_cap is None else int(out_cap)
+    out_read, out_off = np.zeros(max(cap, 1), dtype=np.int32), np.zeros(max(cap, 1), dtype=np.int64)
+    group_first, group_byte = np.zeros(max(n_groups, 0) + 1, dtype=np.int64), np.zeros(max(n_groups, 0) + 1, dtype=np.int64)
+    n_out, out_bytes = ct.c_int64(0), ct.c_int64(0)
+    _ffi.check(lib.mpn_reads_split_plan(n, lens.ctypes.data, m, mem_read.ctypes.data, mem_group.ctypes.data, n_groups, cap, ct.addressof(n_out),
+                                        out_read.ctypes.data, group_first.ctypes.data, out_off.ctypes.data, group_byte.ctypes.data,
+                                        ct.addressof(out_bytes)), 'mpn_reads_split_plan')
+    k = int(n_out.value)
+    return dict(n_out=k, out_read=out_read[:k], group_first=group_first, out_off=out_off[:k], group_byte=group_byte, out_bytes=int(out_bytes.value))
+
+
+def device_split_gather(plan, buf, off, lens, d_out, qbuf=None, d_qout=None, dev_src=None, want_host=True):
+    """mpn_reads_split_gather into the caller's device buffers d_out / d_qout (torch uint8 tensors of at least out_bytes).
+    buf / qbuf: host sources; dev_src = (bases, qualities or None) as torch uint8 tensors: the same sources resident in HBM, read
+    instead.  -> (host copy of the bases or None, host copy of the qualities or None)"""
+    lib = _bind()
+    off, lens = np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(lens, dtype=np.int32)
+    src_bytes = int((off + lens).max()) if len(lens) else 0
+    if dev_src is not None:
+        if int(dev_src[0].numel()) < src_bytes or (qbuf is not None and int(dev_src[1].numel()) < src_bytes):
+            raise ValueError(f'split: the reads end at byte {src_bytes}, beyond their device buffer')
+        s_ptr, q_ptr = dev_src[0].data_ptr(), (dev_src[1].data_ptr() if qbuf is not None else None)
+    else:
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        qbuf = None if qbuf is None else np.ascontiguousarray(qbuf, dtype=np.uint8)
+        if len(buf) < src_bytes or (qbuf is not None and len(qbuf) < src_bytes):
+            raise ValueError(f'split: the reads end at byte {src_bytes}, beyond their buffer')
+        s_ptr, q_ptr = buf.ctypes.data, (qbuf.ctypes.data if qbuf is not None else None)
+    with_q = qbuf is not None
+    out_bytes = int(plan['out_bytes'])
+    h_out = np.empty(out_bytes, dtype=np.uint8) if want_host else None
+    h_qout = np.empty(out_bytes, dtype=np.uint8) if want_host and with_q else None
+    out_read, out_off = np.ascontiguousarray(plan['out_read'], dtype=np.int32), np.ascontiguousarray(plan['out_off'], dtype=np.int64)
+    cap = int(d_out.numel()) if not with_q else min(int(d_out.numel()), int(d_qout.numel()))
+    _ffi.check(lib.mpn_reads_split_gather(len(lens), s_ptr, q_ptr, src_bytes, off.ctypes.data, lens.ctypes.data, 1 if dev_src is not None else 0,
+                                          int(plan['n_out']), out_read.ctypes.data, out_off.ctypes.data, out_bytes, d_out.data_ptr(),
+                                          d_qout.data_ptr() if with_q else None, cap, h_out.ctypes.data if want_host else None,
+                                          h_qout.ctypes.data if h_qout is not None else None), 'mpn_reads_split_gather')
+    return h_out, h_qout
+
+
+def split_last_ns():
+    """Device time of this thread's last plan and gather call (HIP events), ns -> (plan, gather)"""
+    lib = _bind()
+    return int(lib.mpn_reads_split_last_ns(0)), int(lib.mpn_reads_split_last_ns(1))
+
+
+def device_split_reads(buf, off, lens, mem_read, mem_group, n_groups, qbuf=None, dev_src=None, device='cuda'):
+    """The device form of host_split_reads: the same dict, plus 'd_seqs' / 'd_quals' (torch uint8 tensors of out_bytes in HBM)."""
+    import torch
+    plan = device_split_plan(lens, mem_read, mem_group, n_groups)
+    plan['d_seqs'] = torch.empty(plan['out_bytes'], dtype=torch.uint8, device=device)
+    plan['d_quals'] = torch.empty(plan['out_bytes'], dtype=torch.uint8, device=device) if qbuf is not None else None
+    plan['seqs'], plan['quals'] = device_split_gather(plan, buf, off, lens, plan['d_seqs'], qbuf, plan['d_quals'], dev_src)
+    return plan
+
+
+class ReadSplit:
+    """The groups of split_reads(): one output buffer (host, and in HBM when the source batch is resident), a view per group."""
+
+    def __init__(self, packed, res, n_groups):
+        self.packed, self.res, self.n_groups = packed, res, int(n_groups)
+        self._d_off = self._d_len = None
+        if res.get('d_seqs') is not None:
+            import torch
+            dev = res['d_seqs'].device
+            # every read's offset inside its own group's block, and its length, resident once for all group views
+            g_of = np.repeat(np.arange(self.n_groups), np.diff(res['group_first']))
+            self._d_off = torch.from_numpy(res['out_off'] - res['group_byte'][g_of]).to(dev)
+            self._d_len = torch.from_numpy(np.ascontiguousarray(packed.lens[res['out_read']])).to(dev)
+
+    def n_reads(self, g):
+        return int(self.res['group_first'][g + 1] - self.res['group_first'][g])
+
+    def group(self, g):
+        """-> PackedReads of group g: views of the one output buffer, no copy"""
+        r = self.res
+        lo, hi, b0 = int(r['group_first'][g]), int(r['group_first'][g + 1]), int(r['group_byte'][g])
+        reads = r['out_read'][lo:hi]
+        dev = None
+        if self._d_off is not None:
+            dev = (r['d_seqs'][b0:], self._d_off[lo:hi], self._d_len[lo:hi])
+        return PackedReads.from_arrays([self.packed.names[i] for i in reads], r['seqs'][b0:], r['out_off'][lo:hi] - b0, self.packed.lens[reads], dev=dev,
+                                       qbuf=None if r['quals'] is None else r['quals'][b0:])
+
+
+def split_reads(packed, read_idx, group, n_groups, device=None):
+    """Regroup a PackedReads by (read, group) pairs (nanosplit's semantics: a pair once, input order inside a group) -> ReadSplit.
+    device: None = on the GPU when the batch is resident there (packed.dev), True / False to choose."""
+    on_dev = packed.dev is not None if device is None else bool(device)
+    if not on_dev:
+        return ReadSplit(packed, host_split_reads(packed.buf, packed.off, packed.lens, read_idx, group, n_groups, packed.qbuf), n_groups)
+    import torch
+    dev_src, where = None, 'cuda'
+    if packed.dev is not None:
+        where = packed.dev[0].device
+        # the bases stay where they are; the qualities of a batch are not resident, they go up once for the gather
+        dev_src = (packed.dev[0], None if packed.qbuf is None else torch.from_numpy(packed.qbuf).to(where))
+    return ReadSplit(packed, device_split_reads(packed.buf, packed.off, packed.lens, read_idx, group, n_groups, packed.qbuf, dev_src, where), n_groups)
 
 
 _rows_per_read = 2.0  # running estimate used to size the column arrays (a short guess costs a copy, not a second mapping)
