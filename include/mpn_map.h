@@ -209,6 +209,35 @@ int mpn_ext_plan_batch(const mpn_map_opt *opt, int32_t k, int32_t n_targets, con
                        const int32_t *h_cnt, const int32_t *h_mlen, const int32_t *h_split_inv, int32_t grid_cap,
                        int32_t *hits_out, int64_t win_cap, int64_t *n_win, int32_t *win_out, uint64_t *anchors_out);
 
+/* ---- stage: the stitching of a hit's DP windows on arbitrary hits, windows and window results (tests) -------------------------------
+ * The second half of minimap2's mm_align1 for every hit of an alignment round (the windows' CIGARs appended in order with
+ * mm_append_cigar's merge, the DP score, the end coordinates, the cut at the first gap fill that z-dropped or got no DP, the anchor
+ * the hit is split at and the measures of its two halves), run by the same function with the same launch as a round of
+ * mpn_map_batch.  Read i has the squeezed anchors anchors[anchor_off[i] .. anchor_off[i + 1]) as (x, y) word pairs.
+ * hits: 15 words per hit: read, rid, rev, as, cnt (its anchors), as1, cnt1 (those mm_fix_bad_ends kept), qs, rs, qe, re, qs0, qe0
+ * (the stitching record), first_win, n_win (its windows wins[first_win .. first_win + n_win): left extension if any, fills in
+ * order, right extension if any).  wins: 13 words per window: flag (0x40 extension, 0x100 placeholder without DP, 0x200 inversion
+ * found by the z-drop test; 0x02, 0x08, 0x80 are carried), reversed, qs, ts, job_anchor (the anchor a fill ends at, counted from
+ * as1; -1 for an extension), and of its result max, zdropped, max_q, max_t, mqe_t, score, reach_end, n_cigar; cig_pos[w]: where its
+ * n_cigar operations lie in compact[n_compact].  grid_cap: 0 = the mapper's grid, else at most that many blocks.
+ * Validated on the host before any launch (-1): every hit with read < n, rev 0 / 1, cnt >= 1, as + cnt within the read's anchors,
+ * as <= as1, cnt1 >= 1, as1 + cnt1 <= as + cnt, coordinates within +-2^28; the hits' window ranges inside wins and disjoint; flags
+ * among the six above; an extension (0x40) with job_anchor -1, without 0x200, first if reversed and last if not; a fill not
+ * reversed, with job_anchor in 1 .. cnt1 - 1 and not 0x100 and 0x200 at once; of a window without 0x100 (the result of a
+ * placeholder is never read): zdropped and reach_end 0 / 1, max and score within +-2^28, max_q, max_t, mqe_t in -1 .. 2^28, its
+ * operations inside compact, of kinds 0..2 (M, I, D) and shared with no other window; the operations of a hit shorter than 2^28
+ * bases in all (merged lengths are added in place); min_cnt >= 0; pool_cap at least the operations of all windows without 0x100.
+ * Out: out: 25 words per hit in input order: the kernel's StitchOut (cig_off, n_ops, dp_score, rs1, re1, qs1, qe1, has_p, dropped,
+ * drop_fill, drop_max_t, drop_max_q, split_n, split_inv, split_rec) and FinJob (cig_off, code_off, n_cigar, read, rid, rev, qs1,
+ * rs1, qspan, tspan); pool_out: the stitched CIGARs (hit h at cig_off, n_ops words; the order of the hits is the kernel's),
+ * *pool_used the final value of its cursor; splits_out: 8 words per cut hit (record split_rec of its hit): x and y of the first
+ * anchor of the remainder, x and y of the last anchor before it, mlen and blen of the left half, of the right half; *n_splits
+ * their number (room for one per hit).  Returns 0, or -1. */
+int mpn_stitch_batch(int32_t n, const int64_t *anchor_off, const uint64_t *anchors, int32_t n_hits, const int32_t *hits, int64_t n_win,
+                     const int32_t *wins, const int64_t *cig_pos, int64_t n_compact, const uint32_t *compact, int32_t min_cnt,
+                     int32_t grid_cap, int64_t *out, int64_t pool_cap, uint32_t *pool_out, int64_t *pool_used, int64_t *splits_out,
+                     int64_t *n_splits);
+
 /* ---- product call: map a batch of reads, PAF text out ----------------------------------------------------
  * names: n NUL-terminated read names.  paf receives the lines of all reads in input order (NUL terminated).
  * Returns the number of bytes written, or negative error (-3: paf_cap too small). */

@@ -1298,6 +1298,21 @@ struct RoundDev {
     const StitchReg *sregs; const PlanReg *pregs; const PlanSum *psum; const int32_t *job_anchor; const u128 *anchors;
 };
 
+// The stitching launch of an alignment round (stitch_kernels.h), for stitch_and_finish and for the stage entry mpn_stitch_batch
+// alike: the windows of the n_sr hits of rd (jobs, their results and the compact CIGAR pool) are stitched into d_cig from the
+// cursor *d_out_used on; a StitchOut and a FinJob per hit, a SplitRec per cut hit from the cursor *d_n_splits on.  grid_cap: 0 =
+// the mapper's grid, else at most that many blocks (the tests: one block takes every hit in turn).
+static int stitch_enqueue(const RoundDev &rd, int n_sr, const ExtJob *d_jobs, const ExtRes *d_res, const uint32_t *d_compact, uint32_t *d_cig,
+                          unsigned long long *d_out_used, StitchOut *d_so, FinJob *d_fj, int min_cnt, SplitRec *d_splits,
+                          unsigned long long *d_n_splits, int grid_cap, hipStream_t st) {
+    int grid = std::min(n_sr, 256 * 32);
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
+    hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)grid), dim3(64), 0, st, rd.sregs, n_sr, d_jobs, d_res, d_compact, d_cig, d_out_used, d_so, d_fj,
+                       rd.pregs, rd.psum, rd.job_anchor, rd.anchors, min_cnt, d_splits, d_n_splits);
+    MPN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // ---- cs / MD / =X strings of finished alignments (tag_kernels.h): host side ------------------------------------------------
 // tags_enqueue launches aln_tags_wave_kernel for the listed alignments (FinJob / FinOut / fixed CIGARs resident) and queues the
 // download of the per-alignment TagOut records and the pools' cursors; after the caller's wait on the stream, tags_fetch checks
@@ -1476,10 +1491,9 @@ static int stitch_and_finish(const mpn_index *idx, const mpn_map_opt *opt, ReadS
     unsigned long long *d_n_splits = dv.used + 6;
     EvTimer ev(st);
     ev.skip();
-    hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)std::min(n_sr, 256 * 32)), dim3(64), 0, st, rd.sregs, n_sr, (const ExtJob *)dv.jobs,
-                       (const ExtRes *)dv.res, (const uint32_t *)dv.compact, d_cig, d_out_used, d_so, d_fj, rd.pregs, rd.psum, rd.job_anchor, rd.anchors,
-                       opt->min_cnt, d_splits, d_n_splits);
-    MPN_HIP_CHECK(hipGetLastError());
+    if (stitch_enqueue(rd, n_sr, (const ExtJob *)dv.jobs, (const ExtRes *)dv.res, (const uint32_t *)dv.compact, d_cig, d_out_used, d_so, d_fj,
+                       opt->min_cnt, d_splits, d_n_splits, 0, st))
+        return -1;
     ev.mark(54);
     MPN_HIP_CHECK(hipMemcpyAsync(h_so, d_so, (size_t)n_sr * sizeof(StitchOut), hipMemcpyDeviceToHost, st));
     MPN_HIP_CHECK(hipMemcpyAsync(h_out_used, dv.used, 64, hipMemcpyDeviceToHost, st));   // the round's counter block: [2] stitched ops, [6] cut hits
@@ -3096,5 +3110,164 @@ extern "C" int mpn_ext_plan_batch(const mpn_map_opt *opt, int32_t k, int32_t n_t
         }
     }
     *n_win = w;
+    return 0;
+}
+
+// stage entry point for the tests of the stitching stage: stitch_kernel, launched by stitch_enqueue as stitch_and_finish launches
+// it, on arbitrary hits, windows, window results and compact-pool contents.  hits: 15 words per hit; wins: 13 words per window;
+// out: 25 int64 per hit (StitchOut, then FinJob); splits_out: 8 int64 per cut hit (the SplitRec words, x / y bit for bit).
+extern "C" int mpn_stitch_batch(int32_t n, const int64_t *anchor_off, const uint64_t *anchors, int32_t n_hits, const int32_t *hits,
+                                int64_t n_win, const int32_t *wins, const int64_t *cig_pos, int64_t n_compact, const uint32_t *compact,
+                                int32_t min_cnt, int32_t grid_cap, int64_t *out, int64_t pool_cap, uint32_t *pool_out, int64_t *pool_used,
+                                int64_t *splits_out, int64_t *n_splits) {
+    std::lock_guard<std::mutex> call_guard(g_call_mu);
+    hipStream_t st = 0;
+    constexpr int HW = 15, WW = 13;
+    constexpr int32_t LIM = 1 << 28, KNOWN = EZ_APPROX_MAX | EZ_RIGHT | EZ_EXTZ_ONLY | EZ_REV_CIGAR | EZ_REFUSED | EZ_INV;
+    if (n < 0 || n_hits < 0 || n_win < 0 || n_compact < 0) { set_error("mpn_stitch_batch: negative count"); return -1; }
+    if (pool_used) *pool_used = 0;
+    if (n_splits) *n_splits = 0;
+    if (n_hits == 0) return 0;
+    if (!anchor_off || !hits || !out || !pool_used || !n_splits || !splits_out || (n_win > 0 && (!wins || !cig_pos)) || (n_compact > 0 && !compact)) {
+        set_error("mpn_stitch_batch: an array missing"); return -1;
+    }
+    if (min_cnt < 0 || grid_cap < 0 || pool_cap < 0 || n_win > 0x3fffffff || n_compact > 0x3fffffff) {
+        set_error("mpn_stitch_batch: min_cnt, grid_cap, pool_cap or a count out of range"); return -1;
+    }
+    // everything is checked here, before any launch
+    if (n > 0 && anchor_off[0] != 0) { set_error("mpn_stitch_batch: offsets do not start at 0"); return -1; }
+    for (int i = 0; i < n; ++i)
+        if (anchor_off[i + 1] < anchor_off[i] || anchor_off[i + 1] - anchor_off[i] > 0x3fffffff) { set_error("mpn_stitch_batch: read %d: offsets out of order", i); return -1; }
+    const int64_t n_anch = n > 0 ? anchor_off[n] : 0;
+    if (n_anch > 0 && !anchors) { set_error("mpn_stitch_batch: an array missing"); return -1; }
+    std::vector<StitchReg> sregs((size_t)n_hits);
+    std::vector<PlanReg> pregs((size_t)n_hits);
+    std::vector<PlanSum> psum((size_t)n_hits);
+    std::vector<ExtJob> jobs((size_t)n_win + 1);
+    std::vector<ExtRes> res((size_t)n_win + 1);
+    std::vector<int32_t> janchor((size_t)n_win + 1);
+    int64_t ops_max = 0;
+    {
+        std::vector<std::pair<int64_t, int64_t>> wiv, civ;
+        auto coord = [](int32_t v) { return v >= -LIM && v <= LIM; };
+        for (int h = 0; h < n_hits; ++h) {
+            const int32_t *q = hits + (size_t)h * HW;
+            const int32_t read = q[0], rid = q[1], rev = q[2], as = q[3], cnt = q[4], as1 = q[5], cnt1 = q[6], first = q[13], nj = q[14];
+            if (read < 0 || read >= n) { set_error("mpn_stitch_batch: hit %d: no such read", h); return -1; }
+            const int64_t n_a = anchor_off[read + 1] - anchor_off[read];
+            if (rid < 0 || (rev != 0 && rev != 1)) { set_error("mpn_stitch_batch: hit %d: target or strand out of range", h); return -1; }
+            if (as < 0 || cnt < 1 || (int64_t)as + cnt > n_a || as1 < as || cnt1 < 1 || (int64_t)as1 + cnt1 > (int64_t)as + cnt) {
+                set_error("mpn_stitch_batch: hit %d: anchors [%d, +%d) trimmed to [%d, +%d) of %lld", h, as, cnt, as1, cnt1, (long long)n_a); return -1;
+            }
+            for (int c = 7; c < 13; ++c)
+                if (!coord(q[c])) { set_error("mpn_stitch_batch: hit %d: a coordinate out of range", h); return -1; }
+            if (nj < 0 || first < 0 || (int64_t)first + nj > n_win) { set_error("mpn_stitch_batch: hit %d: windows [%d, +%d) of %lld", h, first, nj, (long long)n_win); return -1; }
+            if (nj > 0) wiv.push_back({first, (int64_t)first + nj});
+            int64_t op_len = 0;
+            for (int k = 0; k < nj; ++k) {
+                const int64_t wi = (int64_t)first + k;
+                const int32_t *w = wins + (size_t)wi * WW;
+                const int32_t flag = w[0], reversed = w[1], anchor = w[4], zdropped = w[6], reach_end = w[11], nc = w[12];
+                if ((flag & ~KNOWN) || (reversed != 0 && reversed != 1) || !coord(w[2]) || !coord(w[3])) {
+                    set_error("mpn_stitch_batch: hit %d: window %d: unknown flags, or a coordinate out of range", h, k); return -1;
+                }
+                if (flag & EZ_EXTZ_ONLY) {   // an end extension: the left one first, the right one last
+                    if (anchor != -1 || (flag & EZ_INV) || (reversed ? k != 0 : k != nj - 1)) {
+                        set_error("mpn_stitch_batch: hit %d: window %d: an extension out of place, with an anchor or with the inversion mark", h, k); return -1;
+                    }
+                } else if (reversed || anchor < 1 || anchor > cnt1 - 1 || (flag & (EZ_INV | EZ_REFUSED)) == (EZ_INV | EZ_REFUSED)) {
+                    set_error("mpn_stitch_batch: hit %d: window %d: a fill read backwards, without an anchor of the hit to end at, or refused and tested", h, k); return -1;
+                }
+                ExtJob jb;
+                memset(&jb, 0, sizeof(jb));
+                jb.read = read; jb.rid = rid; jb.rev = rev; jb.qs = w[2]; jb.ts = w[3]; jb.reversed = reversed; jb.flag = flag; jb.cls = -1;
+                jobs[(size_t)wi] = jb;
+                janchor[(size_t)wi] = anchor;
+                ExtRes e;
+                memset(&e, 0, sizeof(e));
+                e.max = w[5]; e.zdropped = zdropped; e.max_q = w[7]; e.max_t = w[8]; e.mqe_t = w[9]; e.mqe = 0; e.score = w[10]; e.reach_end = reach_end;
+                e.n_cigar = nc; e.cig_pos = cig_pos[wi];
+                res[(size_t)wi] = e;
+                if (flag & EZ_REFUSED) continue;   // (a placeholder's result record is never read)
+                if ((zdropped != 0 && zdropped != 1) || (reach_end != 0 && reach_end != 1) || !coord(e.max) || !coord(e.score) || e.max_q < -1 || e.max_q > LIM ||
+                    e.max_t < -1 || e.max_t > LIM || e.mqe_t < -1 || e.mqe_t > LIM) {
+                    set_error("mpn_stitch_batch: hit %d: window %d: a result out of range", h, k); return -1;
+                }
+                if (nc < 0 || e.cig_pos < 0 || e.cig_pos + nc > n_compact) { set_error("mpn_stitch_batch: hit %d: window %d: operations outside the pool", h, k); return -1; }
+                if (nc > 0) civ.push_back({e.cig_pos, e.cig_pos + nc});
+                for (int32_t c = 0; c < nc; ++c) {
+                    const uint32_t op = compact[e.cig_pos + c];
+                    if ((op & 0xf) > 2) { set_error("mpn_stitch_batch: hit %d: window %d: operation %d is not M, I or D", h, k, c); return -1; }
+                    op_len += op >> 4;
+                }
+                ops_max += nc;
+            }
+            // (merged operations are added up in place: no run of them may reach the kind bits' neighbour, bit 32)
+            if (op_len >= LIM) { set_error("mpn_stitch_batch: hit %d: operations of 2^28 bases or more", h); return -1; }
+            sregs[(size_t)h] = StitchReg{first, nj, q[7], q[8], q[9], q[10], q[11], q[12], read, rid, rev, 0};
+            pregs[(size_t)h] = PlanReg{anchor_off[read], (int32_t)n_a, as, cnt, 0, read, 0, 0, 0};
+            psum[(size_t)h] = PlanSum{as1, cnt1};
+        }
+        for (auto *iv : {&wiv, &civ}) {
+            std::sort(iv->begin(), iv->end());
+            for (size_t q = 1; q < iv->size(); ++q)
+                if ((*iv)[q].first < (*iv)[q - 1].second) {
+                    set_error(iv == &wiv ? "mpn_stitch_batch: two hits share a window" : "mpn_stitch_batch: two windows share operations of the pool"); return -1;
+                }
+        }
+    }
+    if (ops_max > pool_cap) { set_error("mpn_stitch_batch: room for %lld operations needed", (long long)ops_max); return -1; }
+    if (ops_max > 0 && !pool_out) { set_error("mpn_stitch_batch: an array missing"); return -1; }
+    DevBuf<u128> d_a;
+    DevBuf<int32_t> d_janchor;
+    DevBuf<PlanReg> d_pr;
+    DevBuf<PlanSum> d_ps;
+    DevBuf<StitchReg> d_sr;
+    DevBuf<ExtJob> d_jobs;
+    DevBuf<ExtRes> d_res;
+    DevBuf<uint32_t> d_compact, d_cig;
+    DevBuf<StitchOut> d_so;
+    DevBuf<FinJob> d_fj;
+    DevBuf<SplitRec> d_splits;
+    DevBuf<unsigned long long> d_used;
+    if (d_a.upload(reinterpret_cast<const u128 *>(anchors), (size_t)n_anch, st) || d_pr.upload(pregs.data(), pregs.size(), st) ||
+        d_ps.upload(psum.data(), psum.size(), st) || d_sr.upload(sregs.data(), sregs.size(), st) || d_jobs.upload(jobs.data(), (size_t)n_win, st) ||
+        d_res.upload(res.data(), (size_t)n_win, st) || d_janchor.upload(janchor.data(), (size_t)n_win, st) ||
+        d_compact.upload(compact, (size_t)n_compact, st) || d_cig.alloc((size_t)pool_cap) || d_so.alloc((size_t)n_hits) || d_fj.alloc((size_t)n_hits) ||
+        d_splits.alloc((size_t)n_hits) || d_used.alloc(8))
+        return -1;
+    MPN_HIP_CHECK(hipMemsetAsync(d_used.p, 0, 64, st));   // the counter block of a round: [2] stitched ops, [6] cut hits
+    const RoundDev rd{d_sr.p, d_pr.p, d_ps.p, d_janchor.p, d_a.p};
+    if (stitch_enqueue(rd, n_hits, d_jobs.p, d_res.p, d_compact.p, d_cig.p, d_used.p + 2, d_so.p, d_fj.p, min_cnt, d_splits.p, d_used.p + 6, grid_cap, st))
+        return -1;
+    std::vector<StitchOut> so((size_t)n_hits);
+    std::vector<FinJob> fj((size_t)n_hits);
+    unsigned long long used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (d_so.download(so.data(), so.size(), st) || d_fj.download(fj.data(), fj.size(), st) || d_used.download(used, 8, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    if (used[2] > (unsigned long long)ops_max || used[6] > (unsigned long long)n_hits) {
+        set_error("mpn_stitch_batch: the kernel counted %llu operations and %llu cut hits, %lld and %d at most expected", used[2], used[6], (long long)ops_max, n_hits);
+        return -1;
+    }
+    std::vector<SplitRec> sp((size_t)used[6] + 1);
+    if (d_cig.download(pool_out, (size_t)used[2], st) || d_splits.download(sp.data(), (size_t)used[6], st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    for (int h = 0; h < n_hits; ++h) {
+        const StitchOut &o = so[(size_t)h];
+        const FinJob &f = fj[(size_t)h];
+        int64_t *q = out + (size_t)h * 25;
+        q[0] = o.cig_off; q[1] = o.n_ops; q[2] = o.dp_score; q[3] = o.rs1; q[4] = o.re1; q[5] = o.qs1; q[6] = o.qe1; q[7] = o.has_p; q[8] = o.dropped;
+        q[9] = o.drop_fill; q[10] = o.drop_max_t; q[11] = o.drop_max_q; q[12] = o.split_n; q[13] = o.split_inv; q[14] = o.split_rec;
+        q[15] = f.cig_off; q[16] = f.code_off; q[17] = f.n_cigar; q[18] = f.read; q[19] = f.rid; q[20] = f.rev; q[21] = f.qs1; q[22] = f.rs1;
+        q[23] = f.qspan; q[24] = f.tspan;
+    }
+    for (size_t i = 0; i < (size_t)used[6]; ++i) {
+        const SplitRec &r = sp[i];
+        int64_t *q = splits_out + i * 8;
+        q[0] = (int64_t)r.fx; q[1] = (int64_t)r.fy; q[2] = (int64_t)r.lx_left; q[3] = (int64_t)r.ly_left; q[4] = r.mlen_l; q[5] = r.blen_l; q[6] = r.mlen_r;
+        q[7] = r.blen_r;
+    }
+    *pool_used = (int64_t)used[2];
+    *n_splits = (int64_t)used[6];
     return 0;
 }

@@ -134,6 +134,9 @@ def _bind():
         lib.mpn_ext_plan_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, ct.c_int32, P, ct.c_int32, P, P, P, P, P, P, P, P, ct.c_int32, P, ct.c_int64,
                                            P, P, P]
         lib.mpn_ext_plan_batch.restype = ct.c_int
+        lib.mpn_stitch_batch.argtypes = [ct.c_int32, P, P, ct.c_int32, P, ct.c_int64, P, P, ct.c_int64, P, ct.c_int32, ct.c_int32, P, ct.c_int64, P, P,
+                                         P, P]
+        lib.mpn_stitch_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
         lib.mpn_reads_split_plan.argtypes = [ct.c_int32, P, ct.c_int64, P, P, ct.c_int32, ct.c_int64, P, P, P, P, P, P]
@@ -927,6 +930,39 @@ def ext_plan_batch(opt, k, t_len, q_len, anchor_off, anchors, hit_off, h_as, h_c
                                 left.ctypes.data)
     _ffi.check(rc, 'mpn_ext_plan_batch')
     return hits[:n_hits], wins[:n_win.value], left[:n_anch]
+
+
+STITCH_HIT_KEYS = ('read', 'rid', 'rev', 'as', 'cnt', 'as1', 'cnt1', 'qs', 'rs', 'qe', 're', 'qs0', 'qe0', 'first_win', 'n_win')
+STITCH_WIN_KEYS = ('flag', 'reversed', 'qs', 'ts', 'anchor', 'max', 'zdropped', 'max_q', 'max_t', 'mqe_t', 'score', 'reach_end', 'n_cigar')
+STITCH_OUT_KEYS = ('cig_off', 'n_ops', 'dp_score', 'rs1', 're1', 'qs1', 'qe1', 'has_p', 'dropped', 'drop_fill', 'drop_max_t', 'drop_max_q',
+                   'split_n', 'split_inv', 'split_rec')
+STITCH_FIN_KEYS = ('cig_off', 'code_off', 'n_cigar', 'read', 'rid', 'rev', 'qs1', 'rs1', 'qspan', 'tspan')
+STITCH_SPLIT_KEYS = ('fx', 'fy', 'lx_left', 'ly_left', 'mlen_l', 'blen_l', 'mlen_r', 'blen_r')
+
+
+def stitch_batch(anchor_off, anchors, hits, wins, cig_pos, compact, min_cnt, grid_cap=0):
+    """The stitching stage on arbitrary hits, windows and window results (mpn_stitch_batch).  anchor_off[n + 1] into anchors uint64
+    [total, 2]; hits int32 [n_hits, 15] in STITCH_HIT_KEYS order; wins int32 [n_win, 13] in STITCH_WIN_KEYS order with cig_pos int64
+    [n_win] into compact uint32.  grid_cap 0 = the mapper's grid, else at most that many blocks.  -> (out int64 [n_hits, 25]: STITCH_OUT_KEYS
+    then STITCH_FIN_KEYS, pool uint32 [the cursor's final value], splits int64 [n_splits, 8] in STITCH_SPLIT_KEYS order, x / y words bit for
+    bit)."""
+    lib = _bind()
+    c = lambda v, t: np.ascontiguousarray(v, dtype=t)  # noqa: E731
+    anchor_off, cig_pos, compact = c(anchor_off, np.int64), c(cig_pos, np.int64), c(compact, np.uint32)
+    anchors, hits, wins = c(anchors, np.uint64).reshape(-1, 2), c(hits, np.int32).reshape(-1, 15), c(wins, np.int32).reshape(-1, 13)
+    n = len(anchor_off) - 1
+    assert n >= 0 and len(anchors) == (int(anchor_off[-1]) if n else 0) and len(cig_pos) == len(wins)
+    n_hits = len(hits)
+    pool_cap = int(np.maximum(wins[:, 12].astype(np.int64), 0).sum())
+    out = np.zeros((n_hits + 1, 25), dtype=np.int64)
+    pool = np.zeros(pool_cap + 1, dtype=np.uint32)
+    splits = np.zeros((n_hits + 1, 8), dtype=np.int64)
+    used, n_splits = ct.c_int64(0), ct.c_int64(0)
+    rc = lib.mpn_stitch_batch(n, anchor_off.ctypes.data, anchors.ctypes.data, n_hits, hits.ctypes.data, len(wins), wins.ctypes.data,
+                              cig_pos.ctypes.data, len(compact), compact.ctypes.data, int(min_cnt), int(grid_cap), out.ctypes.data, pool_cap,
+                              pool.ctypes.data, ct.addressof(used), splits.ctypes.data, ct.addressof(n_splits))
+    _ffi.check(rc, 'mpn_stitch_batch')
+    return out[:n_hits], pool[:used.value], splits[:n_splits.value]
 
 
 STAT_NAMES = {0: 'bases', 1: 'minimizers', 2: 'anchors', 3: 'chains', 4: 'dp_jobs', 5: 'dp_cells', 6: 'alignments',

@@ -85,6 +85,9 @@ def lib():
         L.mmo_plan_hit.argtypes = [ct.POINTER(Opt), ct.c_int, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32,
                                    ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int32]
         L.mmo_plan_hit.restype = ct.c_int32
+        L.mmo_stitch_hit.argtypes = [ct.POINTER(Opt), ct.c_int, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32,
+                                     ct.c_void_p, ct.c_int32, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+        L.mmo_stitch_hit.restype = ct.c_int32
         _lib = L
     return _lib
 
@@ -286,3 +289,25 @@ def plan_hit(opt, k, tlen, qlen, as_, cnt, mlen, split_inv, a):
     assert n >= 0
     return ({key: int(v) for key, v in zip(PLAN_HIT_KEYS, out)},
             [{key: int(v) for key, v in zip(PLAN_WIN_KEYS, row)} for row in win[:n]])
+
+
+STITCH_WIN_KEYS = ('kind', 'qs', 'ts', 'max', 'zdropped', 'max_q', 'max_t', 'mqe_t', 'score', 'reach_end', 'n_cigar', 'zcode')
+STITCH_OUT_KEYS = ('n_ops', 'dp_score', 'rs1', 're1', 'qs1', 'qe1', 'has_p', 'dropped', 'drop_fill', 'drop_max_t', 'drop_max_q', 'split_n',
+                   'r2_cnt', 'r2_as', 'r2_split_inv', 'mlen', 'blen', 'r2_mlen', 'r2_blen', 'consumed')
+
+
+def stitch_hit(opt, k, tlen, qlen, as_, cnt, mlen, split_inv, a, wins, ops):
+    """the second half of the oracle's align1 on the hit a[as_ : as_ + cnt] of one read's squeezed anchors a (uint64 [n_a, 2], SEED_IGNORE
+    marks set in place), with recorded window results: wins = rows of STITCH_WIN_KEYS, ops = the windows' CIGAR ops back to back
+    -> (dict of STITCH_OUT_KEYS, the appended CIGAR as a list of ints)"""
+    assert a.dtype == np.uint64 and a.flags['C_CONTIGUOUS'] and a.ndim == 2 and a.shape[1] == 2
+    win = np.ascontiguousarray(wins, dtype=np.int32).reshape(-1, 12)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    assert int(win[:, 10].sum()) == len(ops)
+    out = np.zeros(20, dtype=np.int32)
+    cig = np.zeros(len(ops) + 1, dtype=np.uint32)
+    rc = lib().mmo_stitch_hit(ct.byref(opt), k, tlen, qlen, as_, cnt, mlen, split_inv, len(a), a.ctypes.data, len(win), win.ctypes.data,
+                              ops.ctypes.data, out.ctypes.data, cig.ctypes.data)
+    assert rc == 0, 'the windows are not those align1 reaches'
+    res = {key: int(v) for key, v in zip(STITCH_OUT_KEYS, out)}
+    return res, [int(v) for v in cig[:res['n_ops']]]

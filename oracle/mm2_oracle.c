@@ -1322,40 +1322,33 @@ static void plan_limits(const mmo_opt *opt, int k, int32_t tlen_all, int qlen, c
     p->rs0 = rs0, p->qs0 = qs0, p->re0 = re0, p->qe0 = qe0;
 }
 
-static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qseq0[2], mmo_reg *r, mmo_reg *r2,
-                   int n_a, mm128 *a, mmo_ez *ez)
+/* The second half of mm_align1 asks for the DP result of one window at a time, in order: left extension (kind 0), gap fills
+ * (1), right extension (2).  align1 answers with align_pair / test_zdrop on the sequences; mmo_stitch_hit answers with results a
+ * caller recorded.  window() fills *ez and returns mm_test_zdrop's code for a fill (0 for an extension). */
+typedef struct win_src win_src;
+struct win_src {
+    int (*window)(win_src *s, int kind, int32_t qs, int32_t ql, int32_t ts, int32_t tl, int bw, mmo_ez *ez);
+};
+/* where mm_align1 stands just before mm_update_extra, beside what it left in r and r2 */
+typedef struct { int32_t rs1, re1, qs1, qe1, dropped, drop_fill, drop_max_t, drop_max_q, split_n; } stitch_state;
+
+/* Everything mm_align1 does between plan_limits and mm_update_extra: the windows' CIGARs appended in order, the DP score, the
+ * end coordinates, the cut at the first gap fill that z-dropped and the split of the hit there.  One copy, for align1 and for
+ * the replay of mmo_stitch_hit. */
+static void stitch_hit(const mmo_opt *opt, int k, int qlen, mmo_reg *r, mmo_reg *r2, const mm128 *a, const plan_lim *pl, win_src *src,
+                       mmo_ez *ez, stitch_state *st)
 {
-    int32_t rid = a[r->as].x << 1 >> 33, rev = a[r->as].x >> 63, as1, cnt1;
-    uint8_t *tseq, *qseq;
-    int32_t i, bw, dropped = 0, rs0, re0, qs0, qe0;
-    int32_t rs, re, qs, qe, rs1, qs1, re1, qe1;
-    const int32_t tlen_all = mi->len[rid], kh = mi->k >> 1;
-    int8_t mat[25];
-    plan_lim pl;
+    const int32_t as1 = pl->as1, cnt1 = pl->cnt1, kh = k >> 1, rev = a[r->as].x >> 63;
+    const int32_t rs0 = pl->rs0, qs0 = pl->qs0, re0 = pl->re0, qe0 = pl->qe0;
+    int32_t rs = pl->rs, qs = pl->qs, re = pl->re, qe = pl->qe, rs1, qs1, re1, qe1, i, n_fill = 0, dropped = 0;
+    const int32_t bw = (int)(opt->bw * 1.5 + 1.);
 
-    r2->cnt = 0;
-    if (r->cnt == 0) return;
-    for (i = 0; i < 4; ++i) { int j; for (j = 0; j < 4; ++j) mat[i * 5 + j] = i == j ? opt->a : -opt->b; mat[i * 5 + 4] = -opt->sc_ambi; }
-    for (i = 0; i < 5; ++i) mat[20 + i] = -opt->sc_ambi;
-    bw = (int)(opt->bw * 1.5 + 1.);
-
-    plan_limits(opt, mi->k, tlen_all, qlen, r, n_a, a, &pl);
-    as1 = pl.as1, cnt1 = pl.cnt1, rs = pl.rs, qs = pl.qs, re = pl.re, qe = pl.qe;
-    rs0 = pl.rs0, qs0 = pl.qs0, re0 = pl.re0, qe0 = pl.qe0;
-
-    tseq = (uint8_t *)malloc((size_t)(re0 - rs0 > 0 ? re0 - rs0 : 1));
-
+    st->drop_fill = st->drop_max_t = st->drop_max_q = -1, st->split_n = 0;
     if (qs > 0 && rs > 0) { /* left extension on reversed sequences, gaps right-aligned */
-        qseq = &qseq0[rev][qs0];
-        getseq(mi, rid, rs0, rs, tseq);
-        seq_rev(qs - qs0, qseq);
-        seq_rev(rs - rs0, tseq);
-        align_pair(opt, qs - qs0, qseq, rs - rs0, tseq, bw, opt->end_bonus, r->split_inv ? opt->zdrop_inv : opt->zdrop,
-                   MMO_EZ_EXTZ_ONLY | MMO_EZ_RIGHT | MMO_EZ_REV_CIGAR, ez);
+        src->window(src, 0, qs0, qs - qs0, rs0, rs - rs0, bw, ez);
         if (ez->n_cigar > 0) { append_cigar(r, ez->n_cigar, ez->cigar); r->dp_score += ez->max; }
         rs1 = rs - (ez->reach_end ? ez->mqe_t + 1 : ez->max_t + 1);
         qs1 = qs - (ez->reach_end ? qs - qs0 : ez->max_q + 1);
-        seq_rev(qs - qs0, qseq);
     } else rs1 = rs, qs1 = qs;
     re1 = rs, qe1 = qs;
 
@@ -1364,14 +1357,9 @@ static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qse
         re = (int32_t)a[as1 + i].x - kh, qe = (int32_t)a[as1 + i].y - kh;
         re1 = re, qe1 = qe;
         if (i == cnt1 - 1 || (a[as1 + i].y & MMO_SEED_LONG_JOIN) || (qe - qs >= opt->min_ksw_len && re - rs >= opt->min_ksw_len)) {
-            int j, bw1 = bw;
+            int j, bw1 = bw, zdrop_code;
             if (a[as1 + i].y & MMO_SEED_LONG_JOIN) bw1 = qe - qs > re - rs ? qe - qs : re - rs;
-            qseq = &qseq0[rev][qs];
-            getseq(mi, rid, rs, re, tseq);
-            int zdrop_code;
-            align_pair(opt, qe - qs, qseq, re - rs, tseq, bw1, -1, opt->zdrop, MMO_EZ_APPROX_MAX, ez);
-            if ((zdrop_code = test_zdrop(opt, qseq, tseq, ez->n_cigar, ez->cigar, mat)) != 0)
-                align_pair(opt, qe - qs, qseq, re - rs, tseq, bw1, -1, zdrop_code == 2 ? opt->zdrop_inv : opt->zdrop, 0, ez);
+            zdrop_code = src->window(src, 1, qs, qe - qs, rs, re - rs, bw1, ez);
             if (ez->n_cigar > 0) append_cigar(r, ez->n_cigar, ez->cigar);
             if (ez->zdropped) { /* the alignment broke: keep the left part, hand the rest back as a new hit */
                 r->has_p = 1;
@@ -1381,20 +1369,21 @@ static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qse
                 r->dp_score += ez->max;
                 re1 = rs + (ez->max_t + 1);
                 qe1 = qs + (ez->max_q + 1);
+                st->drop_fill = n_fill, st->drop_max_t = ez->max_t, st->drop_max_q = ez->max_q;
                 if (cnt1 - (j + 1) >= opt->min_cnt) {
+                    st->split_n = as1 + j + 1 - r->as;
                     split_reg(r, r2, as1 + j + 1 - r->as, qlen, a);
                     if (zdrop_code == 2) r2->split_inv = 1;
                 }
                 break;
             } else r->dp_score += ez->score;
             rs = re, qs = qe;
+            ++n_fill;
         }
     }
 
     if (!dropped && qe < qe0 && re < re0) { /* right extension */
-        qseq = &qseq0[rev][qe];
-        getseq(mi, rid, re, re0, tseq);
-        align_pair(opt, qe0 - qe, qseq, re0 - re, tseq, bw, opt->end_bonus, opt->zdrop, MMO_EZ_EXTZ_ONLY, ez);
+        src->window(src, 2, qe, qe0 - qe, re, re0 - re, bw, ez);
         if (ez->n_cigar > 0) { append_cigar(r, ez->n_cigar, ez->cigar); r->dp_score += ez->max; }
         re1 = re + (ez->reach_end ? ez->mqe_t + 1 : ez->max_t + 1);
         qe1 = qe + (ez->reach_end ? qe0 - qe : ez->max_q + 1);
@@ -1403,11 +1392,66 @@ static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qse
     r->rs = rs1, r->re = re1;
     if (rev) r->qs = qlen - qe1, r->qe = qlen - qs1;
     else r->qs = qs1, r->qe = qe1;
+    st->rs1 = rs1, st->re1 = re1, st->qs1 = qs1, st->qe1 = qe1, st->dropped = dropped;
+}
+
+/* align1's windows: the DP itself */
+typedef struct {
+    win_src src;
+    const mmo_opt *opt; const mmo_idx *mi;
+    int32_t rid, rev, split_inv;
+    uint8_t **qseq0, *tseq;
+    const int8_t *mat;
+} dp_src;
+
+static int dp_window(win_src *s, int kind, int32_t qs, int32_t ql, int32_t ts, int32_t tl, int bw, mmo_ez *ez)
+{
+    dp_src *d = (dp_src *)s;
+    const mmo_opt *opt = d->opt;
+    uint8_t *qseq = &d->qseq0[d->rev][qs], *tseq = d->tseq;
+    int zdrop_code = 0;
+    getseq(d->mi, d->rid, ts, ts + tl, tseq);
+    if (kind == 0) {
+        seq_rev(ql, qseq);
+        seq_rev(tl, tseq);
+        align_pair(opt, ql, qseq, tl, tseq, bw, opt->end_bonus, d->split_inv ? opt->zdrop_inv : opt->zdrop,
+                   MMO_EZ_EXTZ_ONLY | MMO_EZ_RIGHT | MMO_EZ_REV_CIGAR, ez);
+        seq_rev(ql, qseq);
+    } else if (kind == 1) {
+        align_pair(opt, ql, qseq, tl, tseq, bw, -1, opt->zdrop, MMO_EZ_APPROX_MAX, ez);
+        if ((zdrop_code = test_zdrop(opt, qseq, tseq, ez->n_cigar, ez->cigar, d->mat)) != 0)
+            align_pair(opt, ql, qseq, tl, tseq, bw, -1, zdrop_code == 2 ? opt->zdrop_inv : opt->zdrop, 0, ez);
+    } else align_pair(opt, ql, qseq, tl, tseq, bw, opt->end_bonus, opt->zdrop, MMO_EZ_EXTZ_ONLY, ez);
+    return zdrop_code;
+}
+
+static void align1(const mmo_opt *opt, const mmo_idx *mi, int qlen, uint8_t *qseq0[2], mmo_reg *r, mmo_reg *r2,
+                   int n_a, mm128 *a, mmo_ez *ez)
+{
+    int32_t rid = a[r->as].x << 1 >> 33, rev = a[r->as].x >> 63;
+    uint8_t *tseq;
+    int32_t i;
+    const int32_t tlen_all = mi->len[rid];
+    int8_t mat[25];
+    plan_lim pl;
+    dp_src src;
+    stitch_state st;
+
+    r2->cnt = 0;
+    if (r->cnt == 0) return;
+    for (i = 0; i < 4; ++i) { int j; for (j = 0; j < 4; ++j) mat[i * 5 + j] = i == j ? opt->a : -opt->b; mat[i * 5 + 4] = -opt->sc_ambi; }
+    for (i = 0; i < 5; ++i) mat[20 + i] = -opt->sc_ambi;
+
+    plan_limits(opt, mi->k, tlen_all, qlen, r, n_a, a, &pl);
+    tseq = (uint8_t *)malloc((size_t)(pl.re0 - pl.rs0 > 0 ? pl.re0 - pl.rs0 : 1));
+    src.src.window = dp_window, src.opt = opt, src.mi = mi, src.rid = rid, src.rev = rev, src.split_inv = r->split_inv;
+    src.qseq0 = qseq0, src.tseq = tseq, src.mat = mat;
+    stitch_hit(opt, mi->k, qlen, r, r2, a, &pl, &src.src, ez, &st);
     if (r->has_p) {
         free(tseq);
-        tseq = (uint8_t *)malloc((size_t)(re1 - rs1 > 0 ? re1 - rs1 : 1));
-        getseq(mi, rid, rs1, re1, tseq);
-        update_extra(r, &qseq0[r->rev][qs1], tseq, mat, (int8_t)opt->q, (int8_t)opt->e);
+        tseq = (uint8_t *)malloc((size_t)(st.re1 - st.rs1 > 0 ? st.re1 - st.rs1 : 1));
+        getseq(mi, rid, st.rs1, st.re1, tseq);
+        update_extra(r, &qseq0[r->rev][st.qs1], tseq, mat, (int8_t)opt->q, (int8_t)opt->e);
     }
     free(tseq);
 }
@@ -1455,6 +1499,68 @@ int32_t mmo_plan_hit(const mmo_opt *opt, int k, int32_t tlen_all, int32_t qlen, 
         MMO_WIN(qe, pl.qe0 - qe, re, pl.re0 - re, 0, bw, opt->zdrop, opt->end_bonus, MMO_EZ_EXTZ_ONLY, -1);
 #undef MMO_WIN
     return n;
+}
+
+/* mmo_stitch_hit's windows: the caller's recorded results, handed out in order */
+typedef struct {
+    win_src src;
+    const mmo_opt *opt;
+    int32_t n_win, next, bad;
+    const int32_t *win;        /* 12 per window */
+    const uint32_t *ops;       /* the windows' CIGARs back to back, in window order */
+    int64_t op_at;
+} replay_src;
+
+static int replay_window(win_src *s, int kind, int32_t qs, int32_t ql, int32_t ts, int32_t tl, int bw, mmo_ez *ez)
+{
+    replay_src *p = (replay_src *)s;
+    const int32_t *w;
+    (void)bw;
+    ez_reset(ez);
+    if (p->next >= p->n_win) { p->bad = 1; return 0; }
+    w = p->win + 12 * p->next++;
+    if (w[0] != kind || w[1] != qs || w[2] != ts) p->bad = 1;   /* not the window align1 asks for at this place */
+    ez->cigar = (uint32_t *)(p->ops + p->op_at);
+    p->op_at += w[10];
+    if (pair_refused(p->opt, ql, tl)) { ez->zdropped = 1; return 0; }   /* what align_pair does, and test_zdrop on no CIGAR */
+    ez->max = w[3], ez->zdropped = w[4], ez->max_q = w[5], ez->max_t = w[6], ez->mqe_t = w[7], ez->score = w[8], ez->reach_end = w[9];
+    ez->n_cigar = w[10];
+    return kind == 1 ? w[11] : 0;
+}
+
+/* The second half of align1 (the function align1 itself runs after plan_limits) on a caller's hit and on DP results the caller
+ * recorded, without any DP.  The hit and its anchors as for mmo_plan_hit.  Window j at win[12 * j ..] = kind (0 left extension, 1
+ * fill, 2 right extension), qs, ts (checked against the window align1 reaches at that place), then what the DP left: max,
+ * zdropped, max_q, max_t, mqe_t, score, reach_end, n_cigar, zcode (mm_test_zdrop's code for a fill); ops: the windows' n_cigar ops
+ * back to back.  A window that max_sw_mat refuses is handled as align_pair handles it, whatever its record says.
+ * out20 = n_cigar, dp_score, rs1, re1, qs1, qe1, has_p, dropped, drop_fill (index among the fills), drop_max_t, drop_max_q,
+ * split_n (what split_reg is called with; 0: not called), r2.cnt (0: no second hit), r2.as, r2.split_inv, mlen, blen of the hit
+ * and of r2 as split_reg leaves them (the hit's own mlen and 0 without a split), windows consumed.  cigar_out: the appended
+ * CIGAR (room for every op).  Returns 0, -1 if the windows do not match those align1 reaches, or are too few or (without a cut)
+ * too many. */
+int32_t mmo_stitch_hit(const mmo_opt *opt, int k, int32_t tlen_all, int32_t qlen, int32_t as, int32_t cnt, int32_t mlen, int32_t split_inv,
+                       int32_t n_a, mm128 *a, int32_t n_win, const int32_t *win, const uint32_t *ops, int32_t *out20, uint32_t *cigar_out)
+{
+    mmo_reg r, r2;
+    plan_lim pl;
+    replay_src src;
+    stitch_state st;
+    mmo_ez ez;
+    memset(&r, 0, sizeof(r));
+    memset(&r2, 0, sizeof(r2));
+    memset(&ez, 0, sizeof(ez));
+    r.as = as, r.cnt = cnt, r.mlen = mlen, r.split_inv = (uint32_t)split_inv;
+    plan_limits(opt, k, tlen_all, qlen, &r, n_a, a, &pl);
+    src.src.window = replay_window, src.opt = opt, src.n_win = n_win, src.next = 0, src.bad = 0, src.win = win, src.ops = ops, src.op_at = 0;
+    stitch_hit(opt, k, qlen, &r, &r2, a, &pl, &src.src, &ez, &st);
+    out20[0] = r.n_cigar, out20[1] = r.dp_score, out20[2] = st.rs1, out20[3] = st.re1, out20[4] = st.qs1, out20[5] = st.qe1;
+    out20[6] = r.has_p, out20[7] = st.dropped, out20[8] = st.drop_fill, out20[9] = st.drop_max_t, out20[10] = st.drop_max_q;
+    out20[11] = st.split_n, out20[12] = r2.cnt, out20[13] = r2.as, out20[14] = (int32_t)r2.split_inv;
+    out20[15] = r.mlen, out20[16] = r.blen, out20[17] = r2.mlen, out20[18] = r2.blen, out20[19] = src.next;
+    if (r.n_cigar > 0) memcpy(cigar_out, r.cigar, (size_t)r.n_cigar * 4);
+    free(r.cigar);
+    if (src.bad || (!st.dropped && src.next != n_win)) return -1;
+    return 0;
 }
 
 /* the inverted segment between the two halves of a hit that was split at an inversion (mm_align1_inv): a local alignment of

@@ -129,6 +129,16 @@ mmo_reg *mmo_hits_from_chains(const mmo_opt *o, int k, const char *name, int32_t
 int32_t mmo_plan_hit(const mmo_opt *opt, int k, int32_t tlen_all, int32_t qlen, int32_t as, int32_t cnt, int32_t mlen, int32_t split_inv,
                      int32_t n_a, mm128 *a, int32_t *out10, int32_t *win, int32_t cap);
 
+/* the static second half of align1 (everything between plan_limits and update_extra: append_cigar's merges, the DP score, the end
+ * coordinates, the cut at the first z-dropped gap fill, split_reg; the function align1 itself calls) on a caller's hit, given as
+ * for mmo_plan_hit, with the DP result of every window supplied by the caller instead of computed.  Window j at win[12 * j ..] =
+ * kind (0 left extension, 1 fill, 2 right extension), qs, ts, max, zdropped, max_q, max_t, mqe_t, score, reach_end, n_cigar, zcode
+ * (mm_test_zdrop's code: 2 = inversion); ops: the windows' CIGARs back to back.  out20 = n_cigar, dp_score, rs1, re1, qs1, qe1,
+ * has_p, dropped, drop_fill, drop_max_t, drop_max_q, split_n, r2.cnt, r2.as, r2.split_inv, mlen, blen, r2.mlen, r2.blen, windows
+ * consumed; cigar_out: the appended CIGAR.  Returns 0, or -1 if the windows are not those align1 reaches. */
+int32_t mmo_stitch_hit(const mmo_opt *opt, int k, int32_t tlen_all, int32_t qlen, int32_t as, int32_t cnt, int32_t mlen, int32_t split_inv,
+                       int32_t n_a, mm128 *a, int32_t n_win, const int32_t *win, const uint32_t *ops, int32_t *out20, uint32_t *cigar_out);
+
 #ifdef __cplusplus
 }
 #endif
