@@ -533,6 +533,10 @@ def Align(*, assembly_metadata, global_options, temp_dir_name, log_file, query_f
     regular = all(os.path.isfile(p) for p in target_paths)
     cache_key = (tuple(target_paths), options.k, options.w, options.batch_bases) if regular else None
     if output_paf:
+        # MPN_BGZF=device: the BGZF blocks of <prefix>.bam are deflated on the GPU (mpn_bgzf_compress); unset or `zlib`: by zlib
+        how = os.environ.get('MPN_BGZF', 'zlib')
+        if how not in ('zlib', 'device'):
+            raise ValueError(f'MPN_BGZF={how}: expected zlib or device')
         # PAF and SAM go to disk batch by batch: nothing but the integer columns of a batch is kept in memory
         with open(f'{paf_path_and_prefix}.paf', 'w') as paf_f, open(f'{paf_path_and_prefix}.sam', 'w') as sam_f:
             batches, header = map_files(target_paths, query_paths, options, want_paf=True, want_sam=True, want_cols=True,
@@ -544,7 +548,8 @@ def Align(*, assembly_metadata, global_options, temp_dir_name, log_file, query_f
         # duplicate; the amplicon filter keeps everything that is mapped
         exclude = 4 if module_option == 'amplicon_filter_module' else 1796
         bam.sam_to_sorted_bam(f'{paf_path_and_prefix}.sam', f'{paf_path_and_prefix}.bam', exclude_flags=exclude,
-                              sort_keys=abundance.device_sort_order)   # the coordinate sort runs on the GPU (mpn_sort_order)
+                              sort_keys=abundance.device_sort_order,   # the coordinate sort runs on the GPU (mpn_sort_order)
+                              compress_blocks=bam.device_bgzf_blocks if how == 'device' else None)
         if module_option in ('taxon_and_AMR_module', 'AMR_module_only'):                                # aligner.py:250-256
             _run_amr(global_options, f'{paf_path_and_prefix}.bam', AMR_output_folder, log_file)
         if module_option in ('AMR_module_only', 'amplicon_filter_module'):                               # aligner.py:257-259

@@ -44,16 +44,50 @@ def _bgzf_block(payload, level):
             struct.pack('<II', zlib.crc32(payload) & 0xffffffff, len(payload)))
 
 
+BGZF_AUTO, BGZF_STORED, BGZF_NO_MATCH = 0, 1, 2      # include/mpn_bam.h: the modes of mpn_bgzf_compress
+_bgzf_bound = False
+
+
+def device_bgzf_blocks(payloads, mode=BGZF_AUTO):
+    """payloads (bytes-like, at most BGZF_BLOCK bytes each) -> list of complete BGZF blocks, deflated on the GPU by libmpn.so
+    (mpn_bgzf_compress, one workgroup per block).  The compress_blocks hook of BgzfWriter / write_bam / sam_to_sorted_bam."""
+    import ctypes as ct
+    import numpy as np
+    from . import _ffi
+    global _bgzf_bound
+    lib = _ffi.lib()
+    if not _bgzf_bound:
+        lib.mpn_bgzf_compress.argtypes = [ct.c_int64, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int64, ct.c_void_p, ct.c_int32]
+        lib.mpn_bgzf_compress.restype = ct.c_int64
+        _bgzf_bound = True
+    n = len(payloads)
+    if n == 0:
+        return []
+    pay_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.fromiter((len(p) for p in payloads), dtype=np.int64, count=n), out=pay_off[1:])
+    data = np.frombuffer(b''.join(payloads) + b'\0', dtype=np.uint8)     # (never empty: its address is always valid)
+    cap = int(pay_off[n]) + 31 * n                                        # no block is larger than its stored form
+    out = np.empty(cap, dtype=np.uint8)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    r = lib.mpn_bgzf_compress(n, data.ctypes.data, pay_off.ctypes.data, out.ctypes.data, cap, out_off.ctypes.data, int(mode))
+    if r < 0:
+        raise _ffi.MpnError(f'mpn_bgzf_compress failed (rc={r}): {_ffi.hint(_ffi.last_error())}')
+    buf, oo = out[:r].tobytes(), out_off.tolist()
+    return [buf[oo[i]:oo[i + 1]] for i in range(n)]
+
+
 class BgzfWriter:
     """BGZF stream.  Blocks are compressed by a thread pool (zlib releases the GIL), PENDING blocks at a time, so the file
     address of a block is not known when it is closed: tell() returns a provisional virtual offset (block NUMBER << 16 |
     offset in the block) and resolve() turns it into the real one (block ADDRESS << 16 | offset) once the blocks before it
-    have been written (after drain())."""
+    have been written (after drain()).  compress_blocks(payloads) -> list of BGZF blocks, one per payload and in their order,
+    may replace the pool for every level but 0 (device_bgzf_blocks deflates them on the GPU)."""
     PENDING = 256
 
-    def __init__(self, fileobj, level=-1, threads=None):
+    def __init__(self, fileobj, level=-1, threads=None, compress_blocks=None):
         import os
         self.f, self.level = fileobj, level
+        self.compress_blocks = compress_blocks
         self.buf = bytearray()
         self.pending = []            # closed blocks that are not compressed yet
         self.addr = [0]              # addr[i] = file address of block i, for every block whose predecessors are written
@@ -76,7 +110,11 @@ class BgzfWriter:
     def drain(self):
         if not self.pending:
             return
-        if self.threads > 1 and len(self.pending) > 4 and self.level != 0:
+        if self.compress_blocks is not None and self.level != 0:
+            blocks = self.compress_blocks(self.pending)
+            if len(blocks) != len(self.pending):
+                raise ValueError('compress_blocks returned %d blocks for %d payloads' % (len(blocks), len(self.pending)))
+        elif self.threads > 1 and len(self.pending) > 4 and self.level != 0:
             if self.pool is None:
                 from concurrent.futures import ThreadPoolExecutor
                 self.pool = ThreadPoolExecutor(self.threads)
@@ -320,11 +358,11 @@ class BaiBuilder:
             f.write(struct.pack('<Q', self.n_no_coor))
 
 
-def write_bam(path, header_text, ref_names, ref_lens, records, level=-1, index_path=None):
+def write_bam(path, header_text, ref_names, ref_lens, records, level=-1, index_path=None, compress_blocks=None):
     """records: iterable of (tid, pos0, end0, flag, record bytes) in file order.  The index (if asked for) requires them
-    to be coordinate sorted with the unplaced ones last."""
+    to be coordinate sorted with the unplaced ones last.  compress_blocks: see BgzfWriter."""
     with open(path, 'wb') as f:
-        w = BgzfWriter(f, level)
+        w = BgzfWriter(f, level, compress_blocks=compress_blocks)
         text = header_text.encode()
         hdr = bytearray(b'BAM\1' + struct.pack('<i', len(text)) + text + struct.pack('<i', len(ref_names)))
         for nm, ln in zip(ref_names, ref_lens):
@@ -347,14 +385,17 @@ def write_bam(path, header_text, ref_names, ref_lens, records, level=-1, index_p
         bai.write(index_path)
 
 
-def sam_to_sorted_bam(sam_path, bam_path, exclude_flags=0, level=-1, index=True, sort_keys=None, native=True, batch_bytes=64 << 20):
+def sam_to_sorted_bam(sam_path, bam_path, exclude_flags=0, level=-1, index=True, sort_keys=None, native=True, batch_bytes=64 << 20,
+                      compress_blocks=None):
     """`samtools view -F <exclude_flags> -b | samtools sort; samtools index`: keep the records without any of the flags, order them
     by (reference, position, strand) with the unplaced ones last -- a stable sort, like samtools' -- and write BAM + .bai.
 
     The SAM text of a run is tens of GB: only a key (reference, position, strand) and the line's place in the file are kept per
     record; the lines are read back in sorted order and encoded as they are written.  sort_keys(tid, pos, rev) -> order may
     replace the host sort (megapath_nano_amd.abundance.device_sort_order runs it on the GPU).  native: the records are encoded by
-    libmpn.so (mpn_bam_encode, all host cores) instead of encode_record; the two are compared byte for byte in tests/test_bam.py."""
+    libmpn.so (mpn_bam_encode, all host cores) instead of encode_record; the two are compared byte for byte in tests/test_bam.py.
+    compress_blocks(payloads) -> BGZF blocks may replace the zlib thread pool (device_bgzf_blocks deflates them on the GPU,
+    mpn_bgzf_compress); without it the file is what zlib at `level` makes of it."""
     import numpy as np
     header = []
     tids, poss, revs, offs, lens_ = [], [], [], [], []
@@ -423,7 +464,7 @@ def sam_to_sorted_bam(sam_path, bam_path, exclude_flags=0, level=-1, index=True,
     hd = '@HD\tVN:1.6\tSO:coordinate\n'
     body = ''.join(l for l in header if not l.startswith('@HD'))
     write_bam(bam_path, hd + body, names, lens, records() if native else records_python(), level=level,
-              index_path=bam_path + '.bai' if index else None)
+              index_path=bam_path + '.bai' if index else None, compress_blocks=compress_blocks)
     return len(order)
 
 
