@@ -1,0 +1,72 @@
+/*
+ * mpn_ingest.h -- C-ABI of the target ingestion on the GPU (MPN_TARGET_INGEST=device): the files of a target set go from
+ * compressed bytes to the concatenated bases mpn_index_build_device (mpn_map.h) reads, without existing as host strings.
+ *
+ *   mpn_gzip_inflate   many gzip files (RFC 1952 members of RFC 1951 deflate streams) -> their bytes, one wave per file
+ *                      (csrc/inflate_kernels.hip; the serial decoder is csrc/inflate_core.h, which also compiles for the host).
+ *   mpn_fasta_scan     FASTA text in HBM -> the bases of all records without gaps + a record table (csrc/fasta_kernels.hip),
+ *                      with the semantics of megapath_nano_amd/fastx.py iter_fastx.
+ *
+ * Grouping of files, slot sizing, the fallbacks to the host path and the cutting into index parts are in
+ * megapath_nano_amd/ingest.py.  Calling rules as for mpn_bgzf_compress: a call returns when its results are on the host, the
+ * default stream is used, -1 = device error (mpn_last_error()), -2 = bad arguments.
+ */
+#ifndef MPN_INGEST_H
+#define MPN_INGEST_H
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* What became of one stream.  Anything but OK and OVERFLOW: the bytes of the slot are not to be used. */
+enum {
+    MPN_INFLATE_OK = 0,
+    MPN_INFLATE_TRUNCATED = 1,    /* the input ends inside a member */
+    MPN_INFLATE_BAD_MAGIC = 2,    /* bytes that are neither a gzip member (1f 8b, CM = 8) nor zero padding after one */
+    MPN_INFLATE_BAD_BLOCK = 3,    /* block type 3, or LEN / NLEN of a stored block disagree */
+    MPN_INFLATE_BAD_CODE = 4,     /* over-subscribed or wrongly incomplete code, a bit pattern or symbol without meaning */
+    MPN_INFLATE_BAD_DISTANCE = 5, /* a distance further back than the member's output */
+    MPN_INFLATE_BAD_CRC = 6,
+    MPN_INFLATE_BAD_SIZE = 7,     /* ISIZE is not the member's length mod 2^32 */
+    MPN_INFLATE_OVERFLOW = 8,     /* well-formed, but longer than its slot: out_len is exact, the slot holds its first bytes */
+    MPN_FASTA_UNSUPPORTED = 9     /* mpn_fasta_scan only: text iter_fastx would not read as plain FASTA records */
+};
+
+/* n streams: stream i is in[in_off[i] .. in_off[i + 1]), a whole file: zero or more gzip members back to back, zero bytes
+ * after the last one allowed.  Its bytes go to out[slot_off[i] .. slot_off[i] + min(out_len[i], slot_cap[i])); nothing else of out
+ * is written.  slot_off[i] must be a multiple of 16 and the slots must not overlap.  out_len[i]: the inflated length (exact for
+ * OK and OVERFLOW), n_members[i]: the members that were complete and verified (CRC-32 and ISIZE of each), status[i]: MPN_INFLATE_*.
+ * Malformed input ends in a status, never in an access outside the stream or the slot.  All pointers are HOST pointers (out is
+ * uploaded and downloaded whole: the call exists for tests).  Returns 0. */
+int32_t mpn_gzip_inflate(int64_t n, const uint8_t *in, const int64_t *in_off /* n + 1 */, uint8_t *out, const int64_t *slot_off,
+                         const int64_t *slot_cap, int64_t *out_len, int32_t *n_members, int32_t *status);
+
+/* The same with the compressed bytes and the slots in HBM: d_in (in_off[0] is its first byte's offset: d_in[in_off[i] - in_off[0]])
+ * and d_out are DEVICE pointers, d_out 16-byte aligned; the other arrays are host arrays. */
+int32_t mpn_gzip_inflate_device(int64_t n, const void *d_in, const int64_t *in_off /* n + 1 */, void *d_out, const int64_t *slot_off,
+                                const int64_t *slot_cap, int64_t *out_len, int32_t *n_members, int32_t *status);
+
+/* FASTA text of n streams in HBM: stream i is d_text[text_off[i] .. text_off[i] + text_len[i]) (DEVICE pointer; host arrays).
+ * A record starts at a line whose first byte is '>' (line starts reset at every stream start); its name is the first word of
+ * that line; CR and LF vanish; everything else of the other lines is sequence, unchanged.
+ *
+ * Counting call (d_seq = NULL, rec_cap = 0): n_records / n_bases [i] and status[i] (MPN_INFLATE_OK or MPN_FASTA_UNSUPPORTED) of
+ * every stream.  UNSUPPORTED: sequence bytes before the first header, a line that starts with '@' or '+', a blank, tab, VT or FF
+ * in a sequence line, or a CR that is not part of a line end.
+ * Full call: additionally the bases of all records of all streams, without gaps in stream and record order, at d_seq (DEVICE
+ * pointer, seq_cap bytes); rec_stream / rec_name_off (into d_text) / rec_name_len / rec_seq_len [r] for r < sum of n_records;
+ * and the names one after another in name_pool (name_pool_cap bytes, host).  Returns 0, or -3 if a capacity is too small
+ * (n_records / n_bases are complete, nothing else is). */
+int32_t mpn_fasta_scan(int64_t n, const void *d_text, const int64_t *text_off, const int64_t *text_len, void *d_seq, int64_t seq_cap,
+                       int64_t *n_records, int64_t *n_bases, int32_t *status, int64_t rec_cap, int32_t *rec_stream,
+                       int64_t *rec_name_off, int32_t *rec_name_len, int64_t *rec_seq_len, char *name_pool, int64_t name_pool_cap);
+
+/* Device time of the calling thread's last mpn_gzip_inflate[_device] and last mpn_fasta_scan by HIP events, in milliseconds.
+ * Either pointer may be NULL. */
+void mpn_ingest_last_device_ms(double *inflate_ms, double *scan_ms);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

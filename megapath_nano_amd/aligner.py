@@ -154,6 +154,34 @@ def iter_target_parts(records, batch_bases):
         yield part
 
 
+def iter_target_parts_by_length(records, batch_bases):
+    """The rule of iter_target_parts over records whose sequences are elsewhere (ingest.iter_target_parts_device: in HBM): records
+    are tuples (name, length, ...) and a part is the list of them.  Cuts every sequence of lengths exactly as iter_target_parts
+    cuts the records that have those lengths."""
+    part, part_bases, mini = [], 0, 0
+    mini_batch = min(IDX_MINI_BATCH, max(1, batch_bases))
+    for rec in records:
+        part.append(rec)
+        mini += rec[1]
+        if mini >= mini_batch:
+            part_bases += mini
+            mini = 0
+            if part_bases > batch_bases:
+                yield part
+                part, part_bases = [], 0
+    if part:
+        yield part
+
+
+def target_ingest_on_device(paths):
+    """MPN_TARGET_INGEST=device and a target set the device path takes: regular files only (a FIFO can be read once, and the
+    boundaries of the members `cat` feeds it are unknown before decoding; it stays on the host path), no saved index."""
+    from . import ingest
+    if ingest.ingest_mode() != 'device':
+        return False
+    return bool(paths) and all(ingest.is_device_candidate(p) for p in paths)
+
+
 def load_target(path, k, w):
     """One target path -> mapper.Index: a saved index is loaded (megapath_nano.py:1641-1645), sequences are indexed.
     The path is opened exactly once (it is a FIFO in the reference's human/decoy call, aligner.py:143-144)."""
@@ -352,12 +380,17 @@ def map_files(target_paths, query_paths, options, want_paf=True, want_sam=False,
             all_parts(rest())
         return results, header
 
-    raw_parts = iter_target_parts(iter_target_records(target_paths), options.batch_bases)
+    if target_ingest_on_device(target_paths):
+        # the parts arrive built: inflated, scanned and indexed on the GPU (ingest.py); build() below only counts and saves them
+        from . import ingest
+        raw_parts = ingest.iter_target_parts_device(target_paths, options.batch_bases, k=options.k, w=options.w)
+    else:
+        raw_parts = iter_target_parts(iter_target_records(target_paths), options.batch_bases)
     n_built = 0
 
     def build(part):
         nonlocal n_built
-        idx = mapper.Index(part, k=options.k, w=options.w)
+        idx = part if isinstance(part, mapper.Index) else mapper.Index(part, k=options.k, w=options.w)
         n_built += 1
         if save_index:
             # minimap2 -d FILE dumps every part into the one file (bin/megapath_nano.py:1641-1645): so does this

@@ -1,0 +1,423 @@
+"""Target ingestion on the GPU (MPN_TARGET_INGEST=device): the files of a target set go from compressed bytes on disk to resident
+index parts without existing as host strings.  include/mpn_ingest.h has the two native calls; this module groups the files, sizes the
+slots, takes the fallbacks and cuts the parts.
+
+    files --read--> pinned buffer --H2D--> mpn_gzip_inflate_device --> text in HBM --mpn_fasta_scan--> bases in the part's buffer
+                                                                                                       + names and lengths on the host
+    a part closes (aligner.iter_target_parts_by_length, minimap2's -I rule) --> mapper.Index.from_device
+
+What stays on the host path (fastx.open_once / iter_fastx, which defines the records): a target set with a FIFO or a saved index in
+it (aligner.target_ingest_on_device: a FIFO can be read once and its member boundaries are unknown before decoding), a file whose
+inflate or scan status is not OK (read again through the host path, which yields the same records or raises its own error), and the
+inflate of a stream larger than MPN_INGEST_MAX_STREAM compressed bytes (zlib on the host; its text still goes through the scan).
+"""
+import ctypes as ct
+import gzip
+import io
+import os
+import stat
+
+import numpy as np
+
+from . import _ffi, fastx
+
+OK, OVERFLOW, UNSUPPORTED = 0, 8, 9
+STATUS_NAMES = ('OK', 'TRUNCATED', 'BAD_MAGIC', 'BAD_BLOCK', 'BAD_CODE', 'BAD_DISTANCE', 'BAD_CRC', 'BAD_SIZE', 'OVERFLOW', 'UNSUPPORTED')
+
+# One launch must not run long on a shared device.  A wave inflates a single stream at 1.85 MB/s of compressed input (6.0 MB/s of
+# text; profiles/r15_ingest/README.md), so the longest stream one launch may hold takes about a second; larger ones are inflated by
+# zlib on the host.
+MAX_STREAM_DEFAULT = 2 << 20
+# Inflated text per group of files.  A group holds its compressed bytes (~0.3x), its text and, at worst, a retry's copy of it in HBM
+# next to the part's bases and the resident index: 1 GiB of text keeps that below 3 GiB of the device's 288 GB, and is
+# ~250 assemblies of 4 Mbp, enough streams to fill the 256 CUs.
+BATCH_BYTES_DEFAULT = 1 << 30
+
+_bound = False
+
+
+def ingest_mode():
+    """MPN_TARGET_INGEST: unset or `host` = fastx on the host, `device` = this module."""
+    how = os.environ.get('MPN_TARGET_INGEST', 'host')
+    if how not in ('host', 'device'):
+        raise ValueError(f'MPN_TARGET_INGEST={how}: expected host or device')
+    return how
+
+
+def max_stream():
+    return int(os.environ.get('MPN_INGEST_MAX_STREAM', MAX_STREAM_DEFAULT))
+
+
+def batch_bytes():
+    return int(os.environ.get('MPN_INGEST_BATCH_BYTES', BATCH_BYTES_DEFAULT))
+
+
+def _lib():
+    global _bound
+    import torch
+    torch.cuda.init()          # before libmpn.so is loaded (_ffi.hint)
+    lib = _ffi.lib()
+    if not _bound:
+        P, I64 = ct.c_void_p, ct.c_int64
+        lib.mpn_gzip_inflate.argtypes = [I64] + [P] * 8
+        lib.mpn_gzip_inflate.restype = ct.c_int32
+        lib.mpn_gzip_inflate_device.argtypes = [I64] + [P] * 8
+        lib.mpn_gzip_inflate_device.restype = ct.c_int32
+        lib.mpn_fasta_scan.argtypes = [I64, P, P, P, P, I64, P, P, P, I64, P, P, P, P, P, I64]
+        lib.mpn_fasta_scan.restype = ct.c_int32
+        lib.mpn_ingest_last_device_ms.argtypes = [ct.POINTER(ct.c_double), ct.POINTER(ct.c_double)]
+        lib.mpn_ingest_last_device_ms.restype = None
+        _bound = True
+    return lib
+
+
+def last_device_ms():
+    """-> (inflate ms, scan ms) of the calling thread's last native calls"""
+    a, b = ct.c_double(0), ct.c_double(0)
+    _lib().mpn_ingest_last_device_ms(ct.byref(a), ct.byref(b))
+    return a.value, b.value
+
+
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def _align16(x):
+    return (int(x) + 15) & ~15
+
+
+def inflate_host(n_streams, data, in_off, slot_off, slot_cap, out):
+    """mpn_gzip_inflate on host arrays (uint8 data / out, int64 offsets): what the tests call.  -> (length, members, status) arrays;
+    out is written in place."""
+    lib = _lib()
+    data, out = np.ascontiguousarray(data, dtype=np.uint8), np.require(out, dtype=np.uint8, requirements=['C', 'W'])
+    in_off, slot_off, slot_cap = (np.ascontiguousarray(a, dtype=np.int64) for a in (in_off, slot_off, slot_cap))
+    length, members, status = np.zeros(n_streams, np.int64), np.zeros(n_streams, np.int32), np.zeros(n_streams, np.int32)
+    rc = lib.mpn_gzip_inflate(n_streams, _ptr(data), in_off.ctypes.data, _ptr(out), _ptr(slot_off), _ptr(slot_cap), _ptr(length), _ptr(members),
+                              _ptr(status))
+    if rc:
+        raise _ffi.MpnError(f'mpn_gzip_inflate rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    return length, members, status
+
+
+class Inflated:
+    """The text of n streams in HBM: stream i is text[off[i] : off[i] + length[i]] where status[i] is OK."""
+
+    def __init__(self, text, off, length, members, status, on_host, retried):
+        self.text, self.off, self.length, self.members, self.status = text, off, length, members, status
+        self.on_host, self.retried = on_host, retried      # streams zlib inflated (over the size limit); streams that took the retry
+        self.n = len(off)
+
+    def bytes(self, i):
+        a = int(self.off[i])
+        return self.text[a:a + int(self.length[i])].cpu().numpy().tobytes()
+
+
+def _read_blob(item):
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return bytes(item)
+    with open(item, 'rb') as f:
+        return f.read()
+
+
+def _size_of(item):
+    return len(item) if isinstance(item, (bytes, bytearray, memoryview)) else os.path.getsize(item)
+
+
+def _read_into(item, view):
+    """the whole of a file (or bytes object) into a uint8 numpy view of its size: no copy on the way for a file"""
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        view[:] = np.frombuffer(item, dtype=np.uint8)
+        return
+    with open(item, 'rb', buffering=0) as f:
+        got = 0
+        while got < len(view):
+            k = f.readinto(memoryview(view)[got:])
+            if not k:
+                raise OSError(f'{item}: shorter than its size says')
+            got += k
+
+
+def _slot_guess(tail4, size):
+    """ISIZE of the last member: exact for a single-member file.  Never more than deflate can expand (1032:1): a damaged ISIZE
+    must not size an allocation."""
+    if size < 18:
+        return 0
+    return min(int.from_bytes(bytes(tail4), 'little'), 1032 * size + 64)
+
+
+def inflate_files(items, device='cuda', limit=None, timings=None, tail_bytes=0):
+    """items: paths or bytes objects, each a whole gzip file -> Inflated.  The files are read straight into one pinned buffer and
+    uploaded.  A stream that overflows the slot its last ISIZE sized is run ONCE more with the length the decoder reported -- all
+    such streams of the call in one launch; a stream of more than `limit` (MPN_INGEST_MAX_STREAM) compressed bytes is inflated
+    by zlib here and uploaded (zlib's exception propagates).  Any status other than OK is left for the caller.  tail_bytes: room
+    the caller wants behind the slots in Inflated.text (the plain files of a group go there), from Inflated.tail on."""
+    import time
+    import torch
+    lib = _lib()
+    limit = max_stream() if limit is None else int(limit)
+    t0 = time.perf_counter()
+    n = len(items)
+    full = [_size_of(x) for x in items]
+    on_host = [i for i in range(n) if full[i] > limit]
+    host_text = {i: gzip.GzipFile(fileobj=io.BytesIO(_read_blob(items[i])), mode='rb').read() for i in on_host}
+    in_off = np.zeros(n + 1, dtype=np.int64)
+    in_off[1:] = np.cumsum([0 if i in host_text else full[i] for i in range(n)])
+    staging = torch.empty(max(int(in_off[-1]), 1), dtype=torch.uint8).pin_memory()
+    view = staging.numpy()
+    cap = np.zeros(n, dtype=np.int64)
+    for i, x in enumerate(items):
+        if i in host_text:
+            cap[i] = len(host_text[i])
+        else:
+            _read_into(x, view[in_off[i]:in_off[i + 1]])
+            cap[i] = _slot_guess(view[max(in_off[i + 1] - 4, in_off[i]):in_off[i + 1]], full[i])
+    t1 = time.perf_counter()
+    d_in = staging.to(device)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+
+    def run(d_src, offs, caps, room=0):
+        """the streams d_src[offs[j] : offs[j + 1]] into a fresh buffer of slots of `caps` (+ room bytes behind them)
+        -> (buffer, slot offsets with their end, length, members, status, device ms)"""
+        m = len(caps)
+        caps, offs = np.ascontiguousarray(caps, dtype=np.int64), np.ascontiguousarray(offs, dtype=np.int64)
+        so = np.zeros(m + 1, dtype=np.int64)
+        so[1:] = np.cumsum([_align16(c) for c in caps])
+        buf = torch.empty(max(int(so[-1]) + room, 16), dtype=torch.uint8, device=device)
+        length, members, status = np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        if m:
+            rc = lib.mpn_gzip_inflate_device(m, d_src.data_ptr(), offs.ctypes.data, buf.data_ptr(), so.ctypes.data, caps.ctypes.data,
+                                             length.ctypes.data, members.ctypes.data, status.ctypes.data)
+            if rc:
+                raise _ffi.MpnError(f'mpn_gzip_inflate_device rc={rc}: {_ffi.hint(_ffi.last_error())}')
+        return buf, so, length, members, status, last_device_ms()[0] if m else 0.0
+
+    text, so, length, members, status, ms = run(d_in, in_off, cap, room=int(tail_bytes))
+    off, tail = so[:n].copy(), int(so[-1])
+    for i, t in host_text.items():      # (their compressed size here is 0: the kernel saw an empty stream)
+        if t:
+            text[int(off[i]):int(off[i]) + len(t)] = torch.frombuffer(bytearray(t), dtype=torch.uint8).to(device)
+        length[i], members[i], status[i] = len(t), 0, OK
+    again = np.flatnonzero(status == OVERFLOW)
+    if len(again):
+        # one launch for all of them: their compressed bytes are gathered, device to device, one behind the other
+        d_again = torch.cat([d_in[int(in_off[i]):int(in_off[i + 1])] for i in again])
+        offs2 = np.zeros(len(again) + 1, dtype=np.int64)
+        offs2[1:] = np.cumsum(in_off[again + 1] - in_off[again])
+        text2, so2, length2, members2, status2, ms2 = run(d_again, offs2, length[again].copy())
+        # the scan wants one text buffer: the retried streams' text is appended (a copy of the group's text; a retry is for
+        # multi-member files only)
+        base = _align16(text.numel())
+        text = torch.cat([text, torch.empty(base - text.numel(), dtype=torch.uint8, device=device), text2])
+        off[again], length[again], members[again], status[again] = so2[:-1] + base, length2, members2, status2
+        ms += ms2
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings['read'] = timings.get('read', 0) + (t1 - t0)
+        timings['h2d'] = timings.get('h2d', 0) + (t2 - t1)
+        timings['inflate'] = timings.get('inflate', 0) + (time.perf_counter() - t2)
+        timings['inflate_device_ms'] = timings.get('inflate_device_ms', 0) + ms
+    res = Inflated(text, off, length, members, status, on_host, [int(i) for i in again])
+    res.tail, res.launches = tail, 1 + (1 if len(again) else 0)
+    return res
+
+
+class FastaScan:
+    """Records of the scanned streams: names / lens / stream per record, n_records / n_bases / status per stream, and `seq`, the
+    device tensor that holds the bases of the records one after another from `seq_pos` on (None for a counting call)."""
+
+    def __init__(self, names, lens, stream, n_records, n_bases, status, seq, seq_pos):
+        self.names, self.lens, self.stream = names, lens, stream
+        self.n_records, self.n_bases, self.status, self.seq, self.seq_pos = n_records, n_bases, status, seq, seq_pos
+
+
+def scan_fasta(text, off, length, out=None, out_pos=0, count_only=False):
+    """text: torch uint8 tensor in HBM; stream i is text[off[i] : off[i] + length[i]].  The bases go to out[out_pos:] (a torch uint8
+    tensor in HBM with room for them; a fresh one without `out`).  count_only: records, bases and status per stream only."""
+    import torch
+    lib = _lib()
+    off, length = np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(length, dtype=np.int64)
+    n = len(off)
+    if n and (off.min() < 0 or length.min() < 0 or int((off + length).max()) > text.numel()):
+        raise ValueError('scan_fasta: a stream lies outside the text')
+    n_rec, n_bases, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
+
+    def call(d_seq, seq_cap, rec_cap, rs, rno, rnl, rsl, pool, pool_cap, may_be_short=False):
+        rc = lib.mpn_fasta_scan(n, text.data_ptr(), _ptr(off), _ptr(length), d_seq, seq_cap, _ptr(n_rec), _ptr(n_bases), _ptr(status), rec_cap,
+                                rs, rno, rnl, rsl, pool, pool_cap)
+        if rc and not (rc == -3 and may_be_short):
+            raise _ffi.MpnError(f'mpn_fasta_scan rc={rc}: {_ffi.hint(_ffi.last_error())}')
+        return rc
+    call(None, 0, 0, None, None, None, None, None, 0)
+    ms = last_device_ms()[1]
+    if count_only:
+        return FastaScan([], np.zeros(0, np.int64), np.zeros(0, np.int32), n_rec, n_bases, status, None, 0)
+    R, B = int(n_rec.sum()), int(n_bases.sum())
+    if out is None:
+        out, out_pos = torch.empty(max(B, 1), dtype=torch.uint8, device=text.device), 0
+    if out.numel() - out_pos < B:
+        raise ValueError(f'scan_fasta: {B} bases do not fit behind {out_pos} of {out.numel()}')
+    rs, rno, rnl, rsl = np.zeros(R, np.int32), np.zeros(R, np.int64), np.zeros(R, np.int32), np.zeros(R, np.int64)
+    pool = np.zeros(64 * R + 4096, dtype=np.uint8)
+    if R:
+        args = (out.data_ptr() + out_pos, B, R, _ptr(rs), _ptr(rno), _ptr(rnl), _ptr(rsl))
+        if call(*args, pool.ctypes.data, pool.size, may_be_short=True) == -3:
+            # the names are longer than guessed (the lengths are complete): once more with room for them
+            ms += last_device_ms()[1]
+            pool = np.zeros(int(rnl.astype(np.int64).sum()), dtype=np.uint8)
+            call(*args, pool.ctypes.data, pool.size)
+        ms += last_device_ms()[1]
+    ends = np.cumsum(rnl.astype(np.int64))
+    raw = pool.tobytes()
+    names = [raw[e - l:e].decode() for e, l in zip(ends.tolist(), rnl.tolist())]
+    res = FastaScan(names, rsl, rs, n_rec, n_bases, status, out, out_pos)
+    res.device_ms = ms
+    return res
+
+
+def is_device_candidate(path):
+    """A regular file that is not a saved index: what the device path takes."""
+    try:
+        if not stat.S_ISREG(os.stat(path).st_mode):
+            return False
+        with open(path, 'rb') as f:
+            return f.read(8) != fastx.INDEX_MAGIC
+    except OSError:
+        return False
+
+
+def _host_records(path):
+    kind, stream = fastx.open_once(path)
+    try:
+        if kind == 'index':
+            raise ValueError(f'{path}: a saved index cannot be mixed with sequence targets')
+        return [(name, seq) for name, seq, _ in fastx.iter_fastx(stream)]
+    finally:
+        stream.close()
+
+
+class _PartBuffer:
+    """The bases of the records that have not been built into an index yet, in one device buffer: [start, used)."""
+
+    def __init__(self, device):
+        import torch
+        self.torch, self.device = torch, device
+        self.buf = torch.empty(1 << 20, dtype=torch.uint8, device=device)
+        self.start = self.used = 0
+
+    def reserve(self, more):
+        """room for `more` bytes behind `used`; what is before `start` is dropped when the buffer has to move anyway"""
+        if self.used + more <= self.buf.numel():
+            return
+        live = self.used - self.start
+        new = self.torch.empty(max(2 * (live + more), 1 << 20), dtype=self.torch.uint8, device=self.device)
+        new[:live] = self.buf[self.start:self.used]
+        self.buf, self.start, self.used = new, 0, live
+
+    def append_host(self, data):
+        self.reserve(len(data))
+        if data:
+            self.buf[self.used:self.used + len(data)] = self.torch.frombuffer(bytearray(data), dtype=self.torch.uint8).to(self.device)
+            self.used += len(data)
+
+
+def _file_groups(paths, limit_bytes):
+    """Consecutive files whose inflated text (the ISIZE guess; the size of a plain file) stays below limit_bytes; one file at least."""
+    group, total = [], 0
+    for p in paths:
+        size = os.path.getsize(p)
+        with open(p, 'rb') as f:
+            gz = f.read(2) == b'\x1f\x8b'
+            if gz and size >= 18:
+                f.seek(-4, os.SEEK_END)
+                size = max(size, min(int.from_bytes(f.read(4), 'little'), 1032 * size))
+        if group and total + size > limit_bytes:
+            yield group
+            group, total = [], 0
+        group.append((p, gz))
+        total += size
+    if group:
+        yield group
+
+
+def iter_device_records(paths, part, device='cuda', timings=None):
+    """Yields (name, length) of every record of `paths` in order; before a record is yielded its bases are in `part` (_PartBuffer),
+    behind those of the records before it.  Every path is a device candidate (the callers ask aligner.target_ingest_on_device)."""
+    import time
+    import torch
+    for p in paths:
+        if not is_device_candidate(p):
+            raise ValueError(f'{p}: the device path takes regular sequence files only')
+    for group in _file_groups(paths, batch_bytes()):
+        t0 = time.perf_counter()
+        plain = [(p, os.path.getsize(p)) for p, gz in group if not gz]
+        plain_off = np.zeros(len(plain) + 1, dtype=np.int64)
+        plain_off[1:] = np.cumsum([_align16(size) for _, size in plain])
+        # one text buffer for the scan: the inflated slots, and behind them the plain files, read into a pinned buffer and uploaded
+        inf = inflate_files([p for p, gz in group if gz], device=device, timings=timings, tail_bytes=int(plain_off[-1]))
+        text = inf.text
+        if plain:
+            t0 = time.perf_counter()
+            staging = torch.empty(int(plain_off[-1]), dtype=torch.uint8).pin_memory()
+            for k, (p, size) in enumerate(plain):
+                _read_into(p, staging.numpy()[plain_off[k]:plain_off[k] + size])
+            text[inf.tail:inf.tail + int(plain_off[-1])] = staging.to(device)
+            if timings is not None:
+                timings['read'] = timings.get('read', 0) + (time.perf_counter() - t0)
+        off, length, ok = np.zeros(len(group), np.int64), np.zeros(len(group), np.int64), np.ones(len(group), bool)
+        gi = pi = 0
+        for k, (p, gz) in enumerate(group):
+            if gz:
+                off[k], length[k], ok[k] = inf.off[gi], inf.length[gi], inf.status[gi] == OK
+                gi += 1
+            else:
+                off[k], length[k] = inf.tail + plain_off[pi], plain[pi][1]
+                pi += 1
+        length[~ok] = 0
+        t0 = time.perf_counter()
+        counted = scan_fasta(text, off, length, count_only=True)
+        scan_s = time.perf_counter() - t0
+        ok &= counted.status == OK
+        # the files the device cannot take split the group into runs; every run is scanned straight into the part's buffer
+        k = 0
+        while k < len(group):
+            if not ok[k]:
+                for name, seq in _host_records(group[k][0]):
+                    part.append_host(seq)
+                    yield name, len(seq)
+                k += 1
+                continue
+            e = k
+            while e < len(group) and ok[e]:
+                e += 1
+            t0 = time.perf_counter()
+            part.reserve(int(counted.n_bases[k:e].sum()))
+            got = scan_fasta(text, off[k:e], length[k:e], out=part.buf, out_pos=part.used)
+            part.used += int(got.n_bases.sum())
+            if timings is not None:
+                timings['scan'] = timings.get('scan', 0) + scan_s + (time.perf_counter() - t0)
+                timings['scan_device_ms'] = timings.get('scan_device_ms', 0) + got.device_ms
+                scan_s = 0
+            yield from zip(got.names, got.lens.tolist())
+            k = e
+        del text, inf
+
+
+def iter_target_parts_device(paths, batch_bases, k=15, w=10, device='cuda', timings=None):
+    """The index parts of a target set, cut like aligner.iter_target_parts cuts them, each built by mapper.Index.from_device from
+    bases that were inflated and scanned on the GPU.  The caller closes every part before asking for the next one."""
+    import time
+    from . import aligner, mapper
+    part = _PartBuffer(device)
+    for recs in aligner.iter_target_parts_by_length(iter_device_records(paths, part, device, timings), batch_bases):
+        names, lens = [r[0] for r in recs], np.array([r[1] for r in recs], dtype=np.int64)
+        if len(lens) and int(lens.max()) > 0x7fffffff:
+            raise ValueError('a target sequence of more than 2^31 - 1 bases')
+        total = int(lens.sum())
+        t0 = time.perf_counter()
+        idx = mapper.Index.from_device(names, part.buf.data_ptr() + part.start, lens.astype(np.int32), k=k, w=w)
+        if timings is not None:
+            timings['index'] = timings.get('index', 0) + (time.perf_counter() - t0)
+        part.start += total
+        yield idx

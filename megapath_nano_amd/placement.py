@@ -89,8 +89,13 @@ def placement_to_assembly(*, assembly_metadata, global_options, target_assembly_
         random.seed(hashlib.md5(str(species_tax_id).encode()).hexdigest())
         paths = aligner._resolve_targets(assembly_metadata, global_options, None, targets, False, '')
         batches = []
-        for part in aligner.iter_target_parts(aligner.iter_target_records(paths), options.batch_bases):
-            idx = mapper.Index(part, k=options.k, w=options.w)
+        if aligner.target_ingest_on_device(paths):   # MPN_TARGET_INGEST=device: the parts arrive built (ingest.py)
+            from . import ingest
+            parts = ingest.iter_target_parts_device(paths, options.batch_bases, k=options.k, w=options.w)
+        else:
+            parts = aligner.iter_target_parts(aligner.iter_target_records(paths), options.batch_bases)
+        for part in parts:
+            idx = part if isinstance(part, mapper.Index) else mapper.Index(part, k=options.k, w=options.w)
             try:   # an exception must not leave the species' index in HBM
                 names, lens = np.array(idx.names, dtype=object), idx.lens
                 for p in groups:
