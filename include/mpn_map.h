@@ -15,8 +15,9 @@
  * Semantics: minimap2 2.17 `-x map-ont` as restated in oracle/mm2_oracle.c (PARITY UNPINNED: minimap2 is not
  * vendored by the reference; DESIGN.md section 6 lists the deliberate differences).
  *
- * Stage entry points (mpn_sketch_batch, mpn_seed_chain_batch) exist so that the parity tests can compare every
- * GPU stage with the oracle; mpn_map_batch is the product call.
+ * Stage entry points (mpn_sketch_batch, mpn_seed_chain_batch, mpn_chain_batch, mpn_hit_select_batch, mpn_ext_plan_batch,
+ * mpn_ext_dp_batch, mpn_stitch_batch, mpn_aln_finish_batch, mpn_aln_tags_batch) exist so that the parity tests can compare every
+ * GPU stage with the oracle or a restatement of it; mpn_map_batch is the product call.
  *
  * Difference strings (minimap2 --cs, --cs=long, --MD, --eqx): mpn_map_opt.out_tags.  The strings are made on the GPU when the
  * alignment is finished, because only there are the read, the fixed CIGAR and the packed target together; they are written
@@ -124,11 +125,34 @@ int64_t mpn_sketch_batch(int32_t n, const char *seqs, const int64_t *seq_off, co
  * Outputs (caller allocated; CSR over reads):
  *   n_anchor[i], rep_len[i]               anchors found / repetitive-minimizer span (minimap2 rl:i)
  *   chain_off[n+1], chains u[] (score<<32|cnt), achor_off[n+1], chained anchors b[] as (x, y) pairs
- * Returns 0, or negative error (-3: a capacity is too small). */
+ * Returns 0, or negative error (-3: a capacity is too small; -1 also for opt->max_gap above 66076418, the largest for which the
+ * chain DP's 32-bit running coordinate cannot wrap: every mapping call refuses it the same way). */
 int mpn_seed_chain_batch(const mpn_index *idx, const mpn_map_opt *opt, int32_t n, const char *seqs,
                          const int64_t *seq_off, const int32_t *seq_len, int64_t *n_anchor, int32_t *rep_len,
                          int64_t *chain_off, uint64_t *u, int64_t u_cap, int64_t *anchor_off, uint64_t *b,
                          int64_t b_cap);
+
+/* ---- stage: chaining on arbitrary sorted anchors (tests) --------------------------------------------------------------------------
+ * The second half of mpn_seed_chain_batch (minimap2's mm_chain_dp): the drop of segments too short to chain, the cut into work items,
+ * the chain DP, the chain ends, their sort and the backtrack with the chain records, run by the same function with the same launches
+ * as the mapper's.  Read i has the anchors anchors[anchor_off[i] .. anchor_off[i + 1]) as (x, y) word pairs (x = strand << 63 |
+ * rid << 32 | target position, y = flags << 40 | span << 32 | read position), sorted as the anchor sort leaves them (ascending x,
+ * then y).  The gap cost's average seed length of a read is taken over ALL the anchors given for it, also those in segments the
+ * compaction drops.  Of opt only max_gap, bw, max_chain_skip, max_chain_iter, min_cnt and min_chain_score are read.
+ * chain_item: 0 = the mapper's value (or MPN_CHAIN_ITEM), else the anchors from which a run of segments is a work item (held to
+ * 16 .. 4096); bt_par_min: 0 = the mapper's value (or MPN_BT_PAR_MIN), else the number of chain ends from which the backtrack runs a
+ * lane per end; grid_cap: 0 = the mapper's grids, else at most that many blocks for every launch that walks its reads, pieces or
+ * queue with a stride (the per-read table kernel and the scans have a thread per element and are not capped).
+ * Validated on the host before any launch (-1): offsets that start at 0 and do not decrease; within a read x never decreasing;
+ * every read position (the low 32 bits of y) in 0 .. 2^31 - 1; no negative option; max_chain_iter >= 1; max_gap <= 66076418 (see
+ * mpn_seed_chain_batch); chain_item, bt_par_min, grid_cap >= 0.
+ * Out: n_chain[n], n_chained[n]; per read in the order of mpn_seed_chain_batch (chains by their first anchor), read after read:
+ * u (score << 32 | cnt) and recs, 6 words per chain: fx, fy, lx, ly (first and last anchor, bit for bit), mlen, blen
+ * (mm_cal_fuzzy_len), room for u_cap chains each; b: the chained anchors as (x, y) pairs, chain after chain, room for b_cap.
+ * Returns 0, -3 if a capacity is too small (n_chain and n_chained are filled), or -1. */
+int mpn_chain_batch(const mpn_map_opt *opt, int32_t n, const int64_t *anchor_off, const uint64_t *anchors, int32_t chain_item,
+                    int32_t bt_par_min, int32_t grid_cap, int32_t *n_chain, int64_t *n_chained, uint64_t *u, int64_t *recs,
+                    int64_t u_cap, uint64_t *b, int64_t b_cap);
 
 /* ---- stage: the banded dual-affine extension DP on arbitrary pairs of 0..4 code strings (parity tests) -------
  * flag bits as in ksw2: 0x02 approximate max, 0x08 right-align gaps, 0x40 extension only, 0x80 reversed CIGAR.

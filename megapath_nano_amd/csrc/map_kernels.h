@@ -1371,6 +1371,16 @@ __global__ __launch_bounds__(64) void chain_segments_kernel(const u128 *__restri
 // consecutive anchors clamped to max_dist_x + 1 (mod 2^32): inside a segment -- where every step is at most max_dist_x -- differences
 // are the true ones, across a segment boundary (another target, another strand) they exceed max_dist_x like the true ones; the
 // predecessors an anchor can see are at most max_iter anchors back, so a difference never wraps.  The DP then runs on 32-bit numbers.
+// For which max_dist_x that holds: only differences to ring slots are taken modulo 2^32 (a predecessor that has left the ring is
+// measured on the 64-bit coordinates), so a difference spans at most CHAIN_CW = 128 steps of at most max_dist_x + 1 each.  A wrapped
+// difference does harm only where it reads as in range (<= max_dist_x) while the true one is 2^32 or more, and only in a tile that is
+// evaluated: the first tile of 64 always is, the second only if every lane of the first was in range, i.e. the 64 steps before the
+// anchor sum to max_dist_x at most.  The largest true difference a lane can meet is therefore max_dist_x + 64 (max_dist_x + 1) in
+// the second tile (64 (max_dist_x + 1) in the first, which is smaller), and every verdict is right iff 65 max_dist_x + 64 < 2^32:
+// max_dist_x <= 66076418.  One more admits 66076419 + 64 * 66076420 = 2^32 + 3, which reads as 3.  The bound is applied whatever
+// max_iter is (with fewer than 65 predecessors in reach it would be 2^26 - 2); the host refuses larger values before any launch.
+constexpr int CHAIN_MAX_GAP = 66076418;
+static_assert(65ll * CHAIN_MAX_GAP + 64 < (1ll << 32) && 65ll * (CHAIN_MAX_GAP + 1) + 64 >= (1ll << 32), "the ring coordinate's bound");
 struct ChainSlot { uint32_t x; int32_t y, f, p; };
 
 __global__ __launch_bounds__(64) void chain_dp_kernel(const u128 *__restrict__ anchors, const int64_t *__restrict__ anchor_off,
@@ -1444,7 +1454,7 @@ __global__ __launch_bounds__(64) void chain_dp_kernel(const u128 *__restrict__ a
                     dr = ~0u; dq = 0; fj = 0; pj = -1;
                     const uint64_t ri64 = readlane_u64(cx64, li);
                     if (in) {
-                        if (j >= win_lo) {
+                        if (j >= win_lo) {   // (not reached: tiles of 64 are aligned with the ring of 128, a tile is inside it as a whole or not at all)
                             const uint4 sl = *reinterpret_cast<const uint4 *>(&ring[j & M]);
                             dr = ri - sl.x; dq = qi - (int32_t)sl.y; fj = (int32_t)sl.z; pj = (int32_t)sl.w; tj = wt[j & M];
                         } else {

@@ -242,9 +242,115 @@ int sketch_reads(int k, int w, int n, const uint8_t *d_seqs, const int64_t *d_of
     return 0;
 }
 
+// The 32-bit running coordinate of the chain DP's ring (ChainSlot::x, map_kernels.h) holds for max_gap up to CHAIN_MAX_GAP only
+static int chain_gap_check(const mpn_map_opt *opt, const char *who) {
+    if (opt->max_gap > CHAIN_MAX_GAP) {
+        set_error("%s: max_gap %d is beyond %d, the largest the chain DP's 32-bit ring coordinate holds", who, opt->max_gap, CHAIN_MAX_GAP);
+        return -1;
+    }
+    return 0;
+}
+
+// the per-read tables of a batch (read back in one piece by download_chains): five int64[N] tables, two int32[N], the counters
+static int alloc_chain_tables(SeedChainOut &o, int n) {
+    const size_t N = (size_t)n, o1 = (N + 1) * 8, o2 = o1 + N * 8, o3 = o2 + N * 8, o4 = o3 + N * 8, o5 = o4 + N * 4, o6 = (o5 + N * 4 + 7) & ~(size_t)7;
+    o.tables_bytes = o6 + (size_t)(2 + WORK_SLOTS) * 8;
+    if (o.tables.alloc(o.tables_bytes)) return -1;
+    auto view = [&](auto &buf, size_t off, size_t count) { buf.release(); buf.p = reinterpret_cast<decltype(buf.p)>(o.tables.p + off); buf.n = count; buf.owned = false; };
+    view(o.n_anchor, 0, N + 1); view(o.n_chained, o1, N); view(o.u_pos, o2, N); view(o.b_pos, o3, N);
+    view(o.n_chain, o4, N); view(o.rep_len, o5, N); view(o.used, o6, 2 + WORK_SLOTS);
+    return 0;
+}
+
+// the tests' knobs of chain_enqueue: 0 = the mapper's own value
+struct ChainKnobs {
+    int chain_item = 0;   // anchors from which a run of segments is a work item (MPN_CHAIN_ITEM)
+    int bt_par_min = 0;   // chain ends from which the backtrack runs a lane per end (MPN_BT_PAR_MIN)
+    int grid_cap = 0;     // at most that many blocks for every launch that walks its work with a grid-stride loop or pulls it from the queue
+};
+// the launches' scratch: the caller keeps it until it has waited for the stream
+struct ChainScratch {
+    DevBuf<int64_t> kept, piece_kept, piece_off;
+    DevBuf<float> avg_qspan;
+    DevBuf<int32_t> F, P, T, V;
+    DevBuf<uint64_t> Utmp;
+    DevBuf<ChainSeg> seg_big, seg_small;
+};
+// The chaining half of the stage, for seed_chain_device and for the stage entry mpn_chain_batch: compaction, segment cutting, the
+// chain DP, chain ends, their sort and the backtrack, enqueued on st.  In: the sorted anchors of the batch (o.anchors by
+// o.anchor_off, n_a of them), per read the anchors its average seed length is taken over (o.n_anchor) and the sum of their seed
+// lengths (span_sum); read_kept[n], seg_counters[4] and o.used zeroed; tmp: room for n_a anchors; o.n_ends[n].  Out: o.c_off, o.u,
+// o.u_compact, o.chained, o.recs and the per-read tables, all valid once the caller has waited for st.  kn: the tests' knobs, 0 =
+// the mapper's own value; cs: the launches' scratch.
+static int chain_enqueue(const mpn_map_opt *opt, int n, int64_t n_a, SeedChainOut &o, u128 *tmp, unsigned long long *read_kept,
+                         const unsigned long long *span_sum, unsigned int *seg_counters, const ChainKnobs &kn, ChainScratch &cs, StreamLease &st,
+                         EvTimer &ev) {
+    auto &[kept, piece_kept, piece_off, avg_qspan, F, P, T, V, Utmp, seg_big, seg_small] = cs;
+    ChainParams cp;
+    cp.max_dist_x = opt->max_gap; cp.max_dist_y = opt->max_gap; cp.bw = opt->bw; cp.max_skip = opt->max_chain_skip;
+    cp.max_iter = opt->max_chain_iter; cp.min_cnt = opt->min_cnt; cp.min_sc = opt->min_chain_score;
+    const auto capped = [&](int64_t grid) { return (int)(kn.grid_cap > 0 ? std::min<int64_t>(grid, kn.grid_cap) : grid); };   // (the mapper: no cap)
+    const int g = capped(std::max(1, std::min(n, 256 * 32)));
+    // anchors of segments too short to chain are dropped; everything below runs on the compact list (c_off, tmp)
+    const int64_t n_pieces = (n_a + COMPACT_PIECE - 1) / COMPACT_PIECE;
+    if (kept.alloc((size_t)n + 1) || o.c_off.alloc((size_t)n + 1) || avg_qspan.alloc(n) || piece_kept.alloc((size_t)n_pieces + 1) ||
+        piece_off.alloc((size_t)n_pieces + 1))
+        return -1;
+    const int gp = capped(std::max<int64_t>(1, std::min<int64_t>(n_pieces, 256 * 64)));
+    if (n_a > 0) {
+        hipLaunchKernelGGL(anchor_compact_kernel<false>, dim3(gp), dim3(64), 0, st, (const u128 *)o.anchors.p, (const int64_t *)o.anchor_off.p, n, n_a,
+                           cp.max_dist_x, cp.min_cnt, piece_kept.p, read_kept, (const int64_t *)nullptr, (u128 *)nullptr);
+        MPN_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(anchor_compact_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const int64_t *)o.n_anchor.p, n,
+                       (const unsigned long long *)read_kept, span_sum, kept.p, avg_qspan.p);
+    hipLaunchKernelGGL(scan_i64x2_kernel, dim3(2), dim3(1024), 0, st, (const int64_t *)kept.p, o.c_off.p, n, (const int64_t *)piece_kept.p, piece_off.p, (int)n_pieces);
+    MPN_HIP_CHECK(hipGetLastError());
+    int64_t n_c = 0;
+    if (read_i64(o.c_off.p + n, &n_c, st)) return -1;
+    g_stats[45] += n_c;
+    // (a surviving chain holds at least min_cnt anchors)
+    if (F.alloc(n_c) || P.alloc(n_c) || T.alloc(n_c) || V.alloc(n_c) || o.u.alloc(n_c) || Utmp.alloc(n_c) || o.chained.alloc(n_c) ||
+        o.recs.alloc((size_t)(n_c / std::max(1, opt->min_cnt)) + 1))
+        return -1;
+    u128 *ca = tmp;  // the sort's bounce buffer is free now: it receives the compact anchors
+    if (n_a > 0) {
+        hipLaunchKernelGGL(anchor_compact_kernel<true>, dim3(gp), dim3(64), 0, st, (const u128 *)o.anchors.p, (const int64_t *)o.anchor_off.p, n, n_a,
+                           cp.max_dist_x, cp.min_cnt, (int64_t *)nullptr, (unsigned long long *)nullptr, (const int64_t *)piece_off.p, ca);
+        MPN_HIP_CHECK(hipGetLastError());
+    }
+    ev.mark(46);
+    // work items of the chain DP: runs of whole independent segments of each read's anchor list, cut on the device
+    static const int chain_item_env = []() { const char *e = getenv("MPN_CHAIN_ITEM"); return e ? std::min(CHAIN_BIG, std::max(16, atoi(e))) : CHAIN_ITEM; }();
+    const int chain_item = kn.chain_item > 0 ? std::min(CHAIN_BIG, std::max(16, kn.chain_item)) : chain_item_env;
+    if (seg_big.alloc((size_t)n_c / CHAIN_BIG + (size_t)n + 1) || seg_small.alloc((size_t)n_c / chain_item + (size_t)n + 1)) return -1;
+    hipLaunchKernelGGL(chain_segments_kernel, dim3(g), dim3(64), 0, st, (const u128 *)ca, (const int64_t *)o.c_off.p, n, cp, avg_qspan.p, 1, seg_big.p,
+                       seg_small.p, seg_counters, chain_item);
+    MPN_HIP_CHECK(hipGetLastError());
+    ev.mark(13);
+    hipLaunchKernelGGL(chain_dp_kernel, dim3(capped(256 * 32)), dim3(64), 0, st, (const u128 *)ca, (const int64_t *)o.c_off.p, (const float *)avg_qspan.p,
+                       (const ChainSeg *)seg_big.p, (const ChainSeg *)seg_small.p, seg_counters, cp, F.p, P.p, T.p, V.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    ev.mark(13, 37);
+    hipLaunchKernelGGL(chain_ends_kernel, dim3(g), dim3(64), 0, st, (const int64_t *)o.c_off.p, n, cp, F.p, P.p, T.p, V.p, o.u.p, o.n_ends.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(chain_sort_ends_kernel, dim3(capped(std::max(1, std::min(n, 256 * 8)))), dim3(256), 0, st, o.u.p, Utmp.p,
+                       (const int64_t *)o.c_off.p, o.n_ends.p, n);
+    MPN_HIP_CHECK(hipGetLastError());
+    // chained anchors and surviving chains go to compact pools
+    o.u_compact.p = Utmp.p; o.u_compact.n = Utmp.n; o.u_compact.owned = Utmp.owned; Utmp.p = nullptr; Utmp.n = 0;
+    static const int bt_par_min_env = []() { const char *e = getenv("MPN_BT_PAR_MIN"); return e ? std::max(1, atoi(e)) : BT_PAR_MIN; }();   // (tests force either path)
+    const int bt_par_min = kn.bt_par_min > 0 ? kn.bt_par_min : bt_par_min_env;
+    hipLaunchKernelGGL(chain_backtrack_kernel, dim3(g), dim3(64), 0, st, (const u128 *)ca, (const int64_t *)o.c_off.p, n, cp, F.p, P.p, T.p, V.p,
+                       o.u.p, o.n_ends.p, o.chained.p, o.u_compact.p, o.used.p, o.u_pos.p, o.b_pos.p, o.n_chain.p, o.n_chained.p, o.recs.p, bt_par_min);
+    MPN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // seeds -> sorted anchors -> chains for a batch resident on the device; pre: the batch's sketch if the caller has it (same k, w)
 int seed_chain_device(const mpn_index *idx, const mpn_map_opt *opt, int n, const uint8_t *d_seqs, const int64_t *d_off,
                       const int32_t *d_len, const int32_t *h_len, SeedChainOut &o, StreamLease &st, const ReadSketch *pre) {
+    if (chain_gap_check(opt, "seed + chain stage")) return -1;
     int64_t n_mz = 0;
     DevBuf<int64_t> mz_off;
     DevBuf<u128> mz;
@@ -266,14 +372,7 @@ int seed_chain_device(const mpn_index *idx, const mpn_map_opt *opt, int n, const
     DevBuf<int32_t> occ;
     DevBuf<int64_t> pos_start, rel_off, full_off, n_blk, blk_base;
     DevBuf<unsigned long long> span_sum;
-    {   // layout of the read-back block (download_chains copies it in one piece): five int64[N] tables, two int32[N], the counters
-        const size_t N = (size_t)n, o1 = (N + 1) * 8, o2 = o1 + N * 8, o3 = o2 + N * 8, o4 = o3 + N * 8, o5 = o4 + N * 4, o6 = (o5 + N * 4 + 7) & ~(size_t)7;
-        o.tables_bytes = o6 + (size_t)(2 + WORK_SLOTS) * 8;
-        if (o.tables.alloc(o.tables_bytes)) return -1;
-        auto view = [&](auto &buf, size_t off, size_t count) { buf.release(); buf.p = reinterpret_cast<decltype(buf.p)>(o.tables.p + off); buf.n = count; buf.owned = false; };
-        view(o.n_anchor, 0, N + 1); view(o.n_chained, o1, N); view(o.u_pos, o2, N); view(o.b_pos, o3, N);
-        view(o.n_chain, o4, N); view(o.rep_len, o5, N); view(o.used, o6, 2 + WORK_SLOTS);
-    }
+    if (alloc_chain_tables(o, n)) return -1;
     if (occ.alloc(n_mz) || pos_start.alloc(n_mz) || rel_off.alloc(n_mz) || full_off.alloc((size_t)n + 1) ||
         n_blk.alloc((size_t)n + 1) || blk_base.alloc((size_t)n + 1) || span_sum.alloc(n) || o.anchor_off.alloc((size_t)n + 1))
         return -1;
@@ -401,66 +500,8 @@ int seed_chain_device(const mpn_index *idx, const mpn_map_opt *opt, int n, const
         MPN_HIP_CHECK(hipGetLastError());
         ev.mark(12, 49);
     }
-    ChainParams cp;
-    cp.max_dist_x = opt->max_gap; cp.max_dist_y = opt->max_gap; cp.bw = opt->bw; cp.max_skip = opt->max_chain_skip;
-    cp.max_iter = opt->max_chain_iter; cp.min_cnt = opt->min_cnt; cp.min_sc = opt->min_chain_score;
-    const int g = std::max(1, std::min(n, 256 * 32));
-    // anchors of segments too short to chain are dropped; everything below runs on the compact list (c_off, tmp)
-    const int64_t n_pieces = (n_a + COMPACT_PIECE - 1) / COMPACT_PIECE;
-    DevBuf<int64_t> kept, piece_kept, piece_off;
-    DevBuf<float> avg_qspan;
-    if (kept.alloc((size_t)n + 1) || o.c_off.alloc((size_t)n + 1) || avg_qspan.alloc(n) || piece_kept.alloc((size_t)n_pieces + 1) ||
-        piece_off.alloc((size_t)n_pieces + 1))
-        return -1;
-    const int gp = (int)std::max<int64_t>(1, std::min<int64_t>(n_pieces, 256 * 64));
-    if (n_a > 0) {
-        hipLaunchKernelGGL(anchor_compact_kernel<false>, dim3(gp), dim3(64), 0, st, (const u128 *)o.anchors.p, (const int64_t *)o.anchor_off.p, n, n_a,
-                           cp.max_dist_x, cp.min_cnt, piece_kept.p, read_kept.p, (const int64_t *)nullptr, (u128 *)nullptr);
-        MPN_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(anchor_compact_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const int64_t *)o.n_anchor.p, n,
-                       (const unsigned long long *)read_kept.p, (const unsigned long long *)span_sum.p, kept.p, avg_qspan.p);
-    hipLaunchKernelGGL(scan_i64x2_kernel, dim3(2), dim3(1024), 0, st, (const int64_t *)kept.p, o.c_off.p, n, (const int64_t *)piece_kept.p, piece_off.p, (int)n_pieces);
-    MPN_HIP_CHECK(hipGetLastError());
-    int64_t n_c = 0;
-    if (read_i64(o.c_off.p + n, &n_c, st)) return -1;
-    g_stats[45] += n_c;
-    DevBuf<int32_t> F, P, T, V;
-    DevBuf<uint64_t> Utmp;
-    // (a surviving chain holds at least min_cnt anchors)
-    if (F.alloc(n_c) || P.alloc(n_c) || T.alloc(n_c) || V.alloc(n_c) || o.u.alloc(n_c) || Utmp.alloc(n_c) || o.chained.alloc(n_c) ||
-        o.recs.alloc((size_t)(n_c / std::max(1, opt->min_cnt)) + 1))
-        return -1;
-    u128 *ca = tmp.p;  // the sort's bounce buffer is free now: it receives the compact anchors
-    if (n_a > 0) {
-        hipLaunchKernelGGL(anchor_compact_kernel<true>, dim3(gp), dim3(64), 0, st, (const u128 *)o.anchors.p, (const int64_t *)o.anchor_off.p, n, n_a,
-                           cp.max_dist_x, cp.min_cnt, (int64_t *)nullptr, (unsigned long long *)nullptr, (const int64_t *)piece_off.p, ca);
-        MPN_HIP_CHECK(hipGetLastError());
-    }
-    ev.mark(46);
-    // work items of the chain DP: runs of whole independent segments of each read's anchor list, cut on the device
-    DevBuf<ChainSeg> seg_big, seg_small;
-    static const int chain_item = []() { const char *e = getenv("MPN_CHAIN_ITEM"); return e ? std::min(CHAIN_BIG, std::max(16, atoi(e))) : CHAIN_ITEM; }();
-    if (seg_big.alloc((size_t)n_c / CHAIN_BIG + (size_t)n + 1) || seg_small.alloc((size_t)n_c / chain_item + (size_t)n + 1)) return -1;
-    hipLaunchKernelGGL(chain_segments_kernel, dim3(g), dim3(64), 0, st, (const u128 *)ca, (const int64_t *)o.c_off.p, n, cp, avg_qspan.p, 1, seg_big.p,
-                       seg_small.p, seg_counters.p, chain_item);
-    MPN_HIP_CHECK(hipGetLastError());
-    ev.mark(13);
-    hipLaunchKernelGGL(chain_dp_kernel, dim3(256 * 32), dim3(64), 0, st, (const u128 *)ca, (const int64_t *)o.c_off.p, (const float *)avg_qspan.p,
-                       (const ChainSeg *)seg_big.p, (const ChainSeg *)seg_small.p, seg_counters.p, cp, F.p, P.p, T.p, V.p);
-    MPN_HIP_CHECK(hipGetLastError());
-    ev.mark(13, 37);
-    hipLaunchKernelGGL(chain_ends_kernel, dim3(g), dim3(64), 0, st, (const int64_t *)o.c_off.p, n, cp, F.p, P.p, T.p, V.p, o.u.p, o.n_ends.p);
-    MPN_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(chain_sort_ends_kernel, dim3(std::max(1, std::min(n, 256 * 8))), dim3(256), 0, st, o.u.p, Utmp.p,
-                       (const int64_t *)o.c_off.p, o.n_ends.p, n);
-    MPN_HIP_CHECK(hipGetLastError());
-    // chained anchors and surviving chains go to compact pools
-    o.u_compact.p = Utmp.p; o.u_compact.n = Utmp.n; o.u_compact.owned = Utmp.owned; Utmp.p = nullptr; Utmp.n = 0;
-    static const int bt_par_min = []() { const char *e = getenv("MPN_BT_PAR_MIN"); return e ? std::max(1, atoi(e)) : BT_PAR_MIN; }();   // (tests force either path)
-    hipLaunchKernelGGL(chain_backtrack_kernel, dim3(g), dim3(64), 0, st, (const u128 *)ca, (const int64_t *)o.c_off.p, n, cp, F.p, P.p, T.p, V.p,
-                       o.u.p, o.n_ends.p, o.chained.p, o.u_compact.p, o.used.p, o.u_pos.p, o.b_pos.p, o.n_chain.p, o.n_chained.p, o.recs.p, bt_par_min);
-    MPN_HIP_CHECK(hipGetLastError());
+    ChainScratch cs;
+    if (chain_enqueue(opt, n, n_a, o, tmp.p, read_kept.p, span_sum.p, seg_counters.p, ChainKnobs{}, cs, st, ev)) return -1;
     ev.mark(14);
     MPN_HIP_CHECK(stream_sync(st));
     ev.resolve();
@@ -1068,6 +1109,100 @@ int mpn_seed_chain_batch(const mpn_index *idx, const mpn_map_opt *opt, int32_t n
     memcpy(anchor_off, h.b_off.data(), ((size_t)n + 1) * 8);
     if (h.chain_off[n] > u_cap || h.b_off[n] > b_cap) return -3;
     for (int i = 0; i < n; ++i) h.read_chains(i, u + h.chain_off[i], (u128 *)b + h.b_off[i]);
+    return 0;
+}
+
+// stage entry point for the tests of the chaining stage: the kernels from the compaction to the backtrack, launched by chain_enqueue
+// as seed_chain_device launches them, on arbitrary sorted anchors.  recs: 6 int64 per chain (fx, fy, lx, ly bit for bit, mlen, blen).
+int mpn_chain_batch(const mpn_map_opt *opt, int32_t n, const int64_t *anchor_off, const uint64_t *anchors, int32_t chain_item,
+                    int32_t bt_par_min, int32_t grid_cap, int32_t *n_chain, int64_t *n_chained, uint64_t *u, int64_t *recs, int64_t u_cap,
+                    uint64_t *b, int64_t b_cap) {
+    if (!opt || n < 0) { set_error("mpn_chain_batch: options missing or a negative count"); return -1; }
+    // everything is checked here, before any launch
+    if (opt->max_gap < 0 || opt->bw < 0 || opt->max_chain_skip < 0 || opt->max_chain_iter < 0 || opt->min_cnt < 0 || opt->min_chain_score < 0) {
+        set_error("mpn_chain_batch: a negative option"); return -1;
+    }
+    if (opt->max_chain_iter < 1) { set_error("mpn_chain_batch: max_chain_iter below 1"); return -1; }
+    if (chain_gap_check(opt, "mpn_chain_batch")) return -1;
+    if (chain_item < 0 || bt_par_min < 0 || grid_cap < 0 || u_cap < 0 || b_cap < 0) { set_error("mpn_chain_batch: chain_item, bt_par_min, grid_cap or a capacity negative"); return -1; }
+    if (n == 0) return 0;
+    if (!anchor_off || !n_chain || !n_chained) { set_error("mpn_chain_batch: an array missing"); return -1; }
+    if (anchor_off[0] != 0) { set_error("mpn_chain_batch: offsets do not start at 0"); return -1; }
+    for (int i = 0; i < n; ++i)
+        if (anchor_off[i + 1] < anchor_off[i] || anchor_off[i + 1] - anchor_off[i] > 0x3fffffff) { set_error("mpn_chain_batch: read %d: offsets out of order", i); return -1; }
+    const int64_t n_a = anchor_off[n];
+    if (n_a > 0 && !anchors) { set_error("mpn_chain_batch: an array missing"); return -1; }
+    // per read: the anchors its average seed length is taken over (all of them) and the sum of their seed lengths
+    std::vector<int64_t> cnt((size_t)n + 1, 0);
+    std::vector<unsigned long long> sums((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        unsigned long long s = 0;
+        for (int64_t k = anchor_off[i]; k < anchor_off[i + 1]; ++k) {
+            const uint64_t x = anchors[2 * k], y = anchors[2 * k + 1];
+            if (k > anchor_off[i] && x < anchors[2 * (k - 1)]) { set_error("mpn_chain_batch: read %d: anchor %lld: x decreases", i, (long long)(k - anchor_off[i])); return -1; }
+            if (y & 0x80000000ull) { set_error("mpn_chain_batch: read %d: anchor %lld: query position outside 0 .. 2^31 - 1", i, (long long)(k - anchor_off[i])); return -1; }
+            s += y >> 32 & 0xff;
+        }
+        cnt[(size_t)i] = anchor_off[i + 1] - anchor_off[i];
+        sums[(size_t)i] = s;
+    }
+    hipStream_t st = 0;
+    memset(g_stats, 0, sizeof(g_stats));
+    SeedChainOut o;
+    StreamLease sl(st);
+    EvTimer ev(sl);
+    DevBuf<u128> tmp;
+    DevBuf<unsigned long long> span_sum, read_kept;
+    DevBuf<unsigned int> seg_counters;
+    if (alloc_chain_tables(o, n) || o.anchor_off.upload(anchor_off, (size_t)n + 1, st) || o.anchors.upload(reinterpret_cast<const u128 *>(anchors), (size_t)n_a, st) ||
+        tmp.alloc((size_t)n_a) || o.n_ends.alloc((size_t)n) || span_sum.upload(sums.data(), (size_t)n, st) || read_kept.alloc((size_t)n) || seg_counters.alloc(4))
+        return -1;
+    MPN_HIP_CHECK(hipMemcpyAsync(o.n_anchor.p, cnt.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    {
+        ZeroList z{};
+        zero_list_push(z, o.used.p, o.used.n * sizeof(unsigned long long));
+        zero_list_push(z, seg_counters.p, 4 * sizeof(unsigned int));
+        zero_list_push(z, read_kept.p, (size_t)n * 8);
+        zero_list_push(z, o.rep_len.p, (size_t)n * 4);
+        MPN_HIP_CHECK(zero_regions(z, st));
+    }
+    o.n_anchors = n_a;
+    ChainKnobs kn;
+    kn.chain_item = chain_item; kn.bt_par_min = bt_par_min; kn.grid_cap = grid_cap;
+    ChainScratch cs;
+    if (chain_enqueue(opt, n, n_a, o, tmp.p, read_kept.p, span_sum.p, seg_counters.p, kn, cs, sl, ev)) return -1;
+    ev.mark(14);
+    MPN_HIP_CHECK(stream_sync(sl));
+    ev.resolve();
+    HostChains h;
+    PoolBuf pin_u{nullptr, 0, true}, pin_b{nullptr, 0, true};
+    struct Free { PoolBuf &a, &b; ~Free() { a.release(); b.release(); } } free_pins{pin_u, pin_b};
+    if (download_chains(n, o, h, pin_u, pin_b, sl, 2)) return -1;
+    if (h.n_pool_chains < 0 || (size_t)h.n_pool_chains > o.recs.n || (size_t)h.b_off[(size_t)n] > o.chained.n || h.chain_off[(size_t)n] != h.n_pool_chains) {
+        set_error("mpn_chain_batch: the kernels counted %lld chains and %lld chained anchors, %zu and %zu at most expected", (long long)h.n_pool_chains,
+                  (long long)h.b_off[(size_t)n], o.recs.n, o.chained.n);
+        return -1;
+    }
+    std::vector<ChainRec> rv((size_t)h.n_pool_chains + 1);
+    if (o.recs.download(rv.data(), (size_t)h.n_pool_chains, st)) return -1;
+    MPN_HIP_CHECK(stream_sync(st));
+    h.rec_all = rv.data();
+    for (int i = 0; i < n; ++i) { n_chain[i] = h.n_chain[(size_t)i]; n_chained[i] = h.n_chained[(size_t)i]; }
+    if (h.chain_off[(size_t)n] > u_cap || h.b_off[(size_t)n] > b_cap) return -3;
+    if ((h.chain_off[(size_t)n] > 0 && (!u || !recs)) || (h.b_off[(size_t)n] > 0 && !b)) { set_error("mpn_chain_batch: an array missing"); return -1; }
+    std::vector<int32_t> order;
+    std::vector<int64_t> src;
+    for (int i = 0; i < n; ++i) {
+        const int nc = h.n_chain[(size_t)i];
+        h.read_chains(i, u + h.chain_off[(size_t)i], (u128 *)b + h.b_off[(size_t)i]);
+        order.resize((size_t)nc + 1); src.resize((size_t)nc + 1);
+        h.chain_order(i, order.data(), src.data());
+        for (int c = 0; c < nc; ++c) {
+            const ChainRec &r = h.rec_all[h.u_pos[(size_t)i] + order[(size_t)c]];
+            int64_t *q = recs + (size_t)(h.chain_off[(size_t)i] + c) * 6;
+            q[0] = (int64_t)r.fx; q[1] = (int64_t)r.fy; q[2] = (int64_t)r.lx; q[3] = (int64_t)r.ly; q[4] = r.mlen; q[5] = r.blen;
+        }
+    }
     return 0;
 }
 

@@ -137,6 +137,8 @@ def _bind():
         lib.mpn_stitch_batch.argtypes = [ct.c_int32, P, P, ct.c_int32, P, ct.c_int64, P, P, ct.c_int64, P, ct.c_int32, ct.c_int32, P, ct.c_int64, P, P,
                                          P, P]
         lib.mpn_stitch_batch.restype = ct.c_int
+        lib.mpn_chain_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, P, P, ct.c_int32, ct.c_int32, ct.c_int32, P, P, P, P, ct.c_int64, P, ct.c_int64]
+        lib.mpn_chain_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
         lib.mpn_reads_split_plan.argtypes = [ct.c_int32, P, ct.c_int64, P, P, ct.c_int32, ct.c_int64, P, P, P, P, P, P]
@@ -360,6 +362,40 @@ def seed_chain_batch(idx, opt, seqs):
         break
     return [dict(n_anchor=int(n_anchor[i]), rep_len=int(rep_len[i]), u=u[chain_off[i]:chain_off[i + 1]].copy(),
                  b=b[anchor_off[i]:anchor_off[i + 1]].copy()) for i in range(n)]
+
+
+CHAIN_REC_KEYS = ('fx', 'fy', 'lx', 'ly', 'mlen', 'blen')
+
+
+def chain_batch(opt, anchor_off, anchors, chain_item=0, bt_par_min=0, grid_cap=0):
+    """The chaining stage on arbitrary sorted anchors (mpn_chain_batch).  anchor_off[n + 1] into anchors uint64 [total, 2] (x, y), every
+    read's anchors in ascending (x, y) order.  chain_item, bt_par_min: 0 = the mapper's values (MPN_CHAIN_ITEM, MPN_BT_PAR_MIN);
+    grid_cap: 0 = the mapper's grids, else at most that many blocks per launch.  -> list of dict(n_chain, n_chained, u (uint64[n_chain]),
+    b ((n_chained, 2) uint64), recs (int64 [n_chain, 6] in CHAIN_REC_KEYS order, x / y words bit for bit)) per read, chains in the order
+    of seed_chain_batch."""
+    lib = _bind()
+    anchor_off = np.ascontiguousarray(anchor_off, dtype=np.int64)
+    anchors = np.ascontiguousarray(anchors, dtype=np.uint64).reshape(-1, 2)
+    n = len(anchor_off) - 1
+    assert n >= 0 and (n == 0 or len(anchors) >= int(anchor_off[-1]))
+    n_chain = np.zeros(n + 1, dtype=np.int32)
+    n_chained = np.zeros(n + 1, dtype=np.int64)
+    u_cap, b_cap = len(anchors) // 4 + 16, len(anchors) + 16
+    while True:
+        u = np.zeros(u_cap, dtype=np.uint64)
+        recs = np.zeros((u_cap, 6), dtype=np.int64)
+        b = np.zeros((b_cap, 2), dtype=np.uint64)
+        rc = lib.mpn_chain_batch(ct.byref(opt), n, anchor_off.ctypes.data, anchors.ctypes.data, int(chain_item), int(bt_par_min), int(grid_cap),
+                                 n_chain.ctypes.data, n_chained.ctypes.data, u.ctypes.data, recs.ctypes.data, u_cap, b.ctypes.data, b_cap)
+        if rc == -3:
+            u_cap, b_cap = max(u_cap, int(n_chain.sum()) + 1), max(b_cap, int(n_chained.sum()) + 1)
+            continue
+        _ffi.check(rc, 'mpn_chain_batch')
+        break
+    c_off = np.concatenate([[0], np.cumsum(n_chain[:n].astype(np.int64))])
+    b_off = np.concatenate([[0], np.cumsum(n_chained[:n])])
+    return [dict(n_chain=int(n_chain[i]), n_chained=int(n_chained[i]), u=u[c_off[i]:c_off[i + 1]].copy(), b=b[b_off[i]:b_off[i + 1]].copy(),
+                 recs=recs[c_off[i]:c_off[i + 1]].copy()) for i in range(n)]
 
 
 def map_batch(idx, opt, names, seqs):
