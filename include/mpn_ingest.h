@@ -7,6 +7,14 @@
  *   mpn_fasta_scan     FASTA text in HBM -> the bases of all records without gaps + a record table (csrc/fasta_kernels.hip),
  *                      with the semantics of megapath_nano_amd/fastx.py iter_fastx.
  *
+ * and of BAM files as read input (the BGZF blocks of the file are the streams of mpn_gzip_inflate_device; csrc/bam_in_kernels.hip):
+ *
+ *   mpn_bam_flatten    the inflated slots of a group of blocks -> one contiguous BAM text, behind the unconsumed tail of the group before
+ *   mpn_bam_walk       the text -> a table with a row per record (the walk itself is csrc/bam_walk_core.h, which also compiles
+ *                      for the host)
+ *   mpn_bam_decode     the rows of a batch of reads -> ASCII bases, Phred+33 qualities and names, reads that are stored as their
+ *                      reverse complement restored, in the layout of mapper.PackedReads.from_arrays
+ *
  * Grouping of files, slot sizing, the fallbacks to the host path and the cutting into index parts are in
  * megapath_nano_amd/ingest.py.  Calling rules as for mpn_bgzf_compress: a call returns when its results are on the host, the
  * default stream is used, -1 = device error (mpn_last_error()), -2 = bad arguments.
@@ -30,7 +38,11 @@ enum {
     MPN_INFLATE_BAD_CRC = 6,
     MPN_INFLATE_BAD_SIZE = 7,     /* ISIZE is not the member's length mod 2^32 */
     MPN_INFLATE_OVERFLOW = 8,     /* well-formed, but longer than its slot: out_len is exact, the slot holds its first bytes */
-    MPN_FASTA_UNSUPPORTED = 9     /* mpn_fasta_scan only: text iter_fastx would not read as plain FASTA records */
+    MPN_FASTA_UNSUPPORTED = 9,    /* mpn_fasta_scan only: text iter_fastx would not read as plain FASTA records */
+    MPN_BAM_TRUNCATED = 10,       /* mpn_bam_walk only, as are the next three: the header or a record passes the end of the last text */
+    MPN_BAM_BAD_MAGIC = 11,       /* the text does not start with BAM\1 */
+    MPN_BAM_BAD_HEADER = 12,      /* a negative l_text or n_ref, a reference name of less than one byte */
+    MPN_BAM_BAD_RECORD = 13       /* block_size < 32, l_read_name < 1, l_seq < 0, or name, CIGAR, bases and qualities longer than block_size */
 };
 
 /* n streams: stream i is in[in_off[i] .. in_off[i + 1]), a whole file: zero or more gzip members back to back, zero bytes
@@ -65,6 +77,51 @@ int32_t mpn_fasta_scan(int64_t n, const void *d_text, const int64_t *text_off, c
 /* Device time of the calling thread's last mpn_gzip_inflate[_device] and last mpn_fasta_scan by HIP events, in milliseconds.
  * Either pointer may be NULL. */
 void mpn_ingest_last_device_ms(double *inflate_ms, double *scan_ms);
+
+/* ---- BAM as read input ---------------------------------------------------------------------------------------------------------
+ * A row of the record table: where the record starts in the text (at its block_size field) and what its 32 fixed bytes say. */
+typedef struct {
+    int64_t off;
+    int32_t l_seq;
+    uint16_t flag;
+    uint8_t l_read_name;     /* with the NUL */
+    uint8_t has_qual;        /* 1: l_seq > 0 and the first quality byte is not 0xFF */
+} mpn_bam_row;
+
+/* n pieces of inflated text, piece i at d_slots[slot_off[i] .. + slot_len[i]) (DEVICE pointer; host arrays), are copied one behind
+ * the other to d_text (DEVICE, 16-byte aligned), behind the carry_len bytes at d_carry (DEVICE; any alignment, must not overlap
+ * d_text): d_text[0 .. carry_len + sum of slot_len), and zeros up to the next multiple of 16, which text_cap must hold.  *text_len:
+ * the bytes of text.  A wave per MPN_BAM_CHUNK bytes of output. */
+#define MPN_BAM_CHUNK 1024
+int32_t mpn_bam_flatten(int64_t n, const void *d_slots, const int64_t *slot_off, const int64_t *slot_len, const void *d_carry,
+                        int64_t carry_len, void *d_text, int64_t text_cap, int64_t *text_len);
+
+/* Walks d_text[start .. text_len) (DEVICE pointer): with at_header the BAM header first (magic, l_text, n_ref, the reference
+ * entries), then at most max_records records along their block_size fields.  rows[0 .. *n_records) (host, max_records entries) are
+ * the records that were whole and well-formed, *next is the offset of the first byte that was not consumed and *status is
+ *   MPN_INFLATE_OK       the walk reached the end of the text, max_records, or -- without final -- a header or record that passes
+ *                        the end of the text: *next is its start, and the caller carries text[*next ..) to the front of the next
+ *                        text.  With at_header, *next > start exactly when the header was whole.
+ *   MPN_BAM_TRUNCATED    with final: a header or record passes the end of the text
+ *   MPN_BAM_BAD_MAGIC, MPN_BAM_BAD_HEADER, MPN_BAM_BAD_RECORD    (*next: the offending header or record)
+ * Malformed input ends in a status and never in an access outside the text.  One wave: lane 0 follows the chain, the lanes read the
+ * fixed fields of 64 records at a time.  Returns 0. */
+int32_t mpn_bam_walk(const void *d_text, int64_t text_len, int64_t start, int32_t at_header, int32_t final, int64_t max_records,
+                     mpn_bam_row *rows, int64_t *n_records, int64_t *next, int32_t *status);
+
+/* The reads of n rows (host; of mpn_bam_walk on this d_text, the caller has dropped the records it skips): read r's bases go to
+ * d_seq[out_off[r] .. + l_seq) (DEVICE; out_off: host, the exclusive sum of l_seq) as ASCII through =ACMGRSVTWYHKDBN, a record with
+ * flag 0x10 reversed and complemented; with d_qual (DEVICE, or NULL) its qualities + 33 to the same place of d_qual, reversed
+ * alike, '!' for a row without has_qual.  Both buffers are 16-byte aligned and hold total = out_off[n - 1] + l_seq[n - 1] bytes, + 16,
+ * rounded up to a multiple of 16: what follows the last base is zeroed.  The names (l_read_name - 1 bytes each) go one behind the
+ * other to name_pool (host, name_pool_cap bytes).  Returns 0, -2 for arguments or rows that do not fit the text (nothing outside it
+ * is read), -3 if name_pool_cap is too small. */
+int32_t mpn_bam_decode(const void *d_text, int64_t text_len, int64_t n, const mpn_bam_row *rows, const int64_t *out_off, void *d_seq,
+                       void *d_qual, char *name_pool, int64_t name_pool_cap);
+
+/* Device time of the calling thread's last mpn_bam_flatten, mpn_bam_walk and mpn_bam_decode, as mpn_ingest_last_device_ms gives it
+ * for the first two stages.  Any pointer may be NULL. */
+void mpn_bam_last_device_ms(double *flatten_ms, double *walk_ms, double *decode_ms);
 
 #ifdef __cplusplus
 }

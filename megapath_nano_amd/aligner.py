@@ -129,6 +129,8 @@ def iter_target_records(paths):
         try:
             if kind == 'index':
                 raise ValueError(f'{path}: a saved index cannot be mixed with sequence targets')
+            if kind == 'bam':
+                raise ValueError(f'{path}: a BAM file is taken as read input only, not as a target')
             for name, seq, _ in fastx.iter_fastx(stream):
                 yield name, seq
         finally:
@@ -187,6 +189,8 @@ def load_target(path, k, w):
     The path is opened exactly once (it is a FIFO in the reference's human/decoy call, aligner.py:143-144)."""
     kind, stream = fastx.open_once(path)
     try:
+        if kind == 'bam':
+            raise ValueError(f'{path}: a BAM file is taken as read input only, not as a target')
         if kind != 'index':
             return mapper.Index([(n, sq) for n, sq, _ in fastx.iter_fastx(stream)], k=k, w=w)
         if not fastx.is_fifo(path):
@@ -215,7 +219,9 @@ def _is_saved_index(paths):
 
 # ---- reads ---------------------------------------------------------------------------------------------------------------
 def iter_read_batches(query_paths, batch_bases=200_000_000, device=None):
-    """PackedReads of at most batch_bases each, qualities included, in file order."""
+    """PackedReads of at most batch_bases each, qualities included, in file order.  A BAM file among the paths is inflated and decoded
+    on the GPU (ingest.iter_bam_read_batches); its batches are its own: the FASTA / FASTQ reads collected before it are flushed
+    first, and its last batch is not filled up from the file behind it."""
     names, seqs, quals, acc = [], [], [], 0
 
     def flush():
@@ -225,6 +231,13 @@ def iter_read_batches(query_paths, batch_bases=200_000_000, device=None):
         try:
             if kind == 'index':
                 raise ValueError(f'{path}: a saved index is not a read file')
+            if kind == 'bam':
+                from . import ingest
+                if names:
+                    yield flush()
+                    names, seqs, quals, acc = [], [], [], 0
+                yield from ingest.iter_bam_read_batches(stream, batch_bases, device=device or 'cuda')
+                continue
             for name, seq, qual in fastx.iter_fastx(stream):
                 if names and acc + len(seq) > batch_bases:
                     yield flush()

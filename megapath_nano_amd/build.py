@@ -20,6 +20,10 @@ def headers():
 def build(force=False, verbose=False):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     hdr_t = max([os.path.getmtime(h) for h in headers()] + [0])
+    # a library that is newer than every source and header is up to date, whether the object files are still there or not (they
+    # are intermediates: a copy of the tree may leave them out)
+    if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= max([os.path.getmtime(s) for s in sources()] + [hdr_t]):
+        return LIB
     objs, todo = [], []
     for src in sources():
         obj = os.path.join(CSRC, os.path.splitext(os.path.basename(src))[0] + '.o')

@@ -3,13 +3,17 @@
 The reference hands minimap2 its target as a FIFO that `cat` fills with concatenated `.fna.gz` members
 (/root/reference/bin/lib/aligner.py:143-144,209-217) or as one `.fna.gz` (:221).  A FIFO can be opened ONCE: closing the
 read end makes the writer fail with EPIPE and the head of the stream is gone.  So every path is opened exactly once,
-the format (saved index / gzip / plain) is sniffed from the first bytes of that one stream (`peek`, nothing consumed),
+the format (saved index / BAM / gzip / plain) is sniffed from the first bytes of that one stream (`peek`, nothing consumed),
 and records are parsed incrementally from it; concatenated gzip members are handled by the decompressor.
+
+A BAM file (what ONT's basecaller writes: unaligned BAM) is read input only.  Its blocks are inflated and its records decoded on
+the GPU (ingest.iter_bam_read_batches); nothing here decodes it, and a BAM given where targets are expected raises ValueError.
 """
 import gzip
 import io
 import os
 import stat
+import zlib
 
 INDEX_MAGIC = b'MPNIDX01'
 
@@ -21,16 +25,42 @@ def is_fifo(path):
         return False
 
 
+def _is_bam(peeked):
+    """peeked: the first bytes of a gzip stream.  True for a BGZF block (extra subfield BC) whose text starts with BAM\\1; the first
+    bytes of the block are enough to inflate those four."""
+    if len(peeked) < 18 or peeked[:4] != b'\x1f\x8b\x08\x04':
+        return False
+    xlen, p, found = int.from_bytes(peeked[10:12], 'little'), 12, False
+    while p + 4 <= min(12 + xlen, len(peeked)):
+        found |= peeked[p:p + 2] == b'BC'
+        p += 4 + int.from_bytes(peeked[p + 2:p + 4], 'little')
+    if not found:
+        return False
+    try:
+        return zlib.decompressobj(-15).decompress(peeked[12 + xlen:], 4) == b'BAM\x01'
+    except zlib.error:
+        return False
+
+
 def open_once(path):
-    """-> (kind, binary stream); kind is 'index' (a saved mpn index: the stream is positioned at its first byte),
-    'gzip' or 'plain' (both: a stream of decompressed bytes).  The path is opened exactly once."""
+    """-> (kind, binary stream); kind is 'index' (a saved mpn index: the stream is positioned at its first byte), 'bam' (the stream
+    is positioned at the first byte of the file, compressed: ingest.iter_bam_read_batches takes it; told by the BAM magic at the
+    start of the first BGZF block's text), 'gzip' or 'plain' (both: a stream of decompressed bytes).  The path is opened exactly once."""
     raw = io.BufferedReader(open(path, 'rb', buffering=0), buffer_size=1 << 20)
-    head = raw.peek(8)[:8]
+    peeked = raw.peek(8)
+    head = peeked[:8]
     if head == INDEX_MAGIC:
         return 'index', raw
     if head[:2] == b'\x1f\x8b':
+        if _is_bam(peeked):
+            return 'bam', raw
         return 'gzip', io.BufferedReader(gzip.GzipFile(fileobj=raw, mode='rb'), buffer_size=1 << 20)
     return 'plain', raw
+
+
+def _no_bam(kind, path, what):
+    if kind == 'bam':
+        raise ValueError(f'{path}: a BAM file is taken as read input only, not {what}')
 
 
 def iter_fastx(stream):
@@ -75,7 +105,11 @@ def read_fastx(path, with_qual=False):
     try:
         if kind == 'index':
             raise ValueError(f'{path}: a saved index, not sequences')
-        recs = list(iter_fastx(stream))
+        if kind == 'bam':
+            from . import ingest
+            recs = ingest.read_bam(stream)
+        else:
+            recs = list(iter_fastx(stream))
     finally:
         stream.close()
     return recs if with_qual else [(n, s) for n, s, _ in recs]
@@ -130,6 +164,7 @@ def subseq(in_path, names, out):
     try:
         if kind == 'index':
             raise ValueError(f'{in_path}: a saved index, not sequences')
+        _no_bam(kind, in_path, 'by subseq')
         for name, comment, seq, qual in iter_fastx_full(stream):
             if name not in wanted:
                 continue
@@ -173,6 +208,7 @@ def nanosplit(read_list_path, in_paths, device=None):
         try:
             if kind == 'index':
                 raise ValueError(f'{path}: a saved index, not sequences')
+            _no_bam(kind, path, 'by nanosplit')
             for name, comment, seq, qual in iter_fastx_full(stream):
                 groups = wanted.get(name)
                 if groups is None:

@@ -10,6 +10,15 @@ What stays on the host path (fastx.open_once / iter_fastx, which defines the rec
 it (aligner.target_ingest_on_device: a FIFO can be read once and its member boundaries are unknown before decoding), a file whose
 inflate or scan status is not OK (read again through the host path, which yields the same records or raises its own error), and the
 inflate of a stream larger than MPN_INGEST_MAX_STREAM compressed bytes (zlib on the host; its text still goes through the scan).
+
+BAM files as READ input take the same inflate kernel, a BGZF block being a gzip member of its own (iter_bam_read_batches, at the end
+of this module):
+
+    file --framing (18-byte block headers, no byte decoded)--> pinned group buffer --H2D--> mpn_gzip_inflate_device, a wave per block
+      --mpn_bam_flatten--> one text --mpn_bam_walk--> record table --(skip 0x900, cut batches like aligner.iter_read_batches)-->
+      mpn_bam_decode --> mapper.PackedReads with its device copy
+
+There is no host path for them: a block whose status is not OK, or a text that is no BAM, raises ValueError.
 """
 import ctypes as ct
 import gzip
@@ -22,7 +31,9 @@ import numpy as np
 from . import _ffi, fastx
 
 OK, OVERFLOW, UNSUPPORTED = 0, 8, 9
-STATUS_NAMES = ('OK', 'TRUNCATED', 'BAD_MAGIC', 'BAD_BLOCK', 'BAD_CODE', 'BAD_DISTANCE', 'BAD_CRC', 'BAD_SIZE', 'OVERFLOW', 'UNSUPPORTED')
+STATUS_NAMES = ('OK', 'TRUNCATED', 'BAD_MAGIC', 'BAD_BLOCK', 'BAD_CODE', 'BAD_DISTANCE', 'BAD_CRC', 'BAD_SIZE', 'OVERFLOW', 'UNSUPPORTED',
+                'BAM_TRUNCATED', 'BAM_BAD_MAGIC', 'BAM_BAD_HEADER', 'BAM_BAD_RECORD')
+BAM_TRUNCATED, BAM_BAD_MAGIC, BAM_BAD_HEADER, BAM_BAD_RECORD = 10, 11, 12, 13
 
 # One launch must not run long on a shared device.  A wave inflates a single stream at 1.85 MB/s of compressed input (6.0 MB/s of
 # text; profiles/r15_ingest/README.md), so the longest stream one launch may hold takes about a second; larger ones are inflated by
@@ -67,6 +78,14 @@ def _lib():
         lib.mpn_fasta_scan.restype = ct.c_int32
         lib.mpn_ingest_last_device_ms.argtypes = [ct.POINTER(ct.c_double), ct.POINTER(ct.c_double)]
         lib.mpn_ingest_last_device_ms.restype = None
+        lib.mpn_bam_flatten.argtypes = [I64, P, P, P, P, I64, P, I64, P]
+        lib.mpn_bam_flatten.restype = ct.c_int32
+        lib.mpn_bam_walk.argtypes = [P, I64, I64, ct.c_int32, ct.c_int32, I64, P, P, P, P]
+        lib.mpn_bam_walk.restype = ct.c_int32
+        lib.mpn_bam_decode.argtypes = [P, I64, I64, P, P, P, P, P, I64]
+        lib.mpn_bam_decode.restype = ct.c_int32
+        lib.mpn_bam_last_device_ms.argtypes = [ct.POINTER(ct.c_double)] * 3
+        lib.mpn_bam_last_device_ms.restype = None
         _bound = True
     return lib
 
@@ -292,6 +311,8 @@ def _host_records(path):
     try:
         if kind == 'index':
             raise ValueError(f'{path}: a saved index cannot be mixed with sequence targets')
+        if kind == 'bam':
+            raise ValueError(f'{path}: a BAM file is taken as read input only, not as a target')
         return [(name, seq) for name, seq, _ in fastx.iter_fastx(stream)]
     finally:
         stream.close()
@@ -421,3 +442,294 @@ def iter_target_parts_device(paths, batch_bases, k=15, w=10, device='cuda', timi
             timings['index'] = timings.get('index', 0) + (time.perf_counter() - t0)
         part.start += total
         yield idx
+
+
+# ---- BAM as read input --------------------------------------------------------------------------------------------------------------
+BAM_ROW = np.dtype([('off', '<i8'), ('l_seq', '<i4'), ('flag', '<u2'), ('l_read_name', 'u1'), ('has_qual', 'u1')])    # mpn_bam_row
+BAM_SKIP = 0x900            # secondary and supplementary records: `samtools fastq` leaves them out
+BGZF_MAX_TEXT = 1 << 16     # ISIZE of a BGZF block
+# Records per launch of the walk.  Its one wave pays a dependent read per record, 0.4 us if each is an HBM miss (the records of
+# long reads are several KiB apart); 65 536 records keep a launch below 30 ms.  Measured: profiles/r16_bam_ingest/README.md.
+BAM_WALK_RECORDS_DEFAULT = 1 << 16
+
+
+def bam_walk_records():
+    return int(os.environ.get('MPN_BAM_WALK_RECORDS', BAM_WALK_RECORDS_DEFAULT))
+
+
+def last_bam_device_ms():
+    """-> (flatten ms, walk ms, decode ms) of the calling thread's last native calls"""
+    v = [ct.c_double(0) for _ in range(3)]
+    _lib().mpn_bam_last_device_ms(*[ct.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def _tick(timings, key, value):
+    if timings is not None:
+        timings[key] = timings.get(key, 0) + value
+
+
+def bgzf_block_size(head, offset=0):
+    """head: the first 12 + XLEN bytes of a BGZF block (or more) -> its whole size, BSIZE + 1.  ValueError for anything else."""
+    if len(head) < 12 or head[:4] != b'\x1f\x8b\x08\x04':
+        raise ValueError(f'not a BGZF block at file offset {offset}: header {bytes(head[:4]).hex()}')
+    xlen = int.from_bytes(head[10:12], 'little')
+    p = 12
+    while p + 4 <= 12 + xlen and p + 4 <= len(head):
+        slen = int.from_bytes(head[p + 2:p + 4], 'little')
+        if head[p:p + 2] == b'BC' and slen == 2 and p + 6 <= len(head):
+            size = int.from_bytes(head[p + 4:p + 6], 'little') + 1
+            if size < 12 + xlen + 2 + 8:
+                raise ValueError(f'BGZF block at file offset {offset}: BSIZE {size - 1} is smaller than the block\'s own header and trailer')
+            return size
+        p += 4 + slen
+    raise ValueError(f'not a BGZF block at file offset {offset}: no BC subfield')
+
+
+class _BgzfGroups:
+    """Framing: the BGZF blocks of one stream, group by group, in a pinned buffer.  No byte is decoded."""
+
+    def __init__(self, stream, group_text):
+        import torch
+        self.torch = torch
+        self.stream = stream if hasattr(stream, 'peek') else io.BufferedReader(stream)
+        self.group_text = max(1, int(group_text))
+        # compressed bytes a group may hold: half its text (BGZF of bases and qualities is ~0.4x) and room for one block
+        self.cap = self.group_text // 2 + (1 << 17)
+        self.staging = torch.empty(min(self.cap, 4 << 20), dtype=torch.uint8).pin_memory()
+        self.pos = 0            # file offset of the next block
+        self.blocks = 0         # blocks before the next group
+        self.eof = False
+
+    def _room(self, used, more):
+        if used + more <= self.staging.numel():
+            return
+        new = self.torch.empty(min(max(2 * self.staging.numel(), used + more), max(self.cap, used + more)), dtype=self.torch.uint8).pin_memory()
+        new[:used] = self.staging[:used]
+        self.staging = new
+
+    def _fill(self, view):
+        got = 0
+        while got < len(view):
+            k = self.stream.readinto(memoryview(view)[got:])
+            if not k:
+                return got
+            got += k
+        return got
+
+    def next_group(self):
+        """-> (uint8 pinned tensor of the blocks' bytes, in_off [n + 1], isize [n], file offset of every block); n = 0 at the end"""
+        used, text, in_off, isize, where = 0, 0, [0], [], []
+        while not self.eof:
+            head = self.stream.read(12)
+            if not head:
+                self.eof = True
+                break
+            if head[:4] != b'\x1f\x8b\x08\x04'[:len(head)]:
+                raise ValueError(f'not a BGZF block at file offset {self.pos}: header {head[:4].hex()}')
+            xlen = int.from_bytes(head[10:12], 'little') if len(head) == 12 else 0
+            extra = self.stream.read(xlen)
+            if len(head) < 12 or len(extra) < xlen:
+                raise ValueError(f'the file ends inside the BGZF block at file offset {self.pos}')
+            head += extra
+            size = bgzf_block_size(head, self.pos)
+            self._room(used, size)
+            view = self.staging.numpy()
+            view[used:used + len(head)] = np.frombuffer(head, dtype=np.uint8)
+            if self._fill(view[used + len(head):used + size]) < size - len(head):
+                raise ValueError(f'the file ends inside the BGZF block at file offset {self.pos}')
+            n_text = int.from_bytes(view[used + size - 4:used + size].tobytes(), 'little')
+            if n_text > BGZF_MAX_TEXT:
+                raise ValueError(f'BGZF block at file offset {self.pos}: ISIZE {n_text} is more than a block holds')
+            where.append(self.pos)
+            isize.append(n_text)
+            used += size
+            in_off.append(used)
+            self.pos += size
+            text += n_text
+            if text >= self.group_text or used + (1 << 16) > self.cap:
+                self.eof = not self.stream.peek(1)
+                break
+        first = self.blocks
+        self.blocks += len(isize)
+        return self.staging[:used], np.array(in_off, dtype=np.int64), np.array(isize, dtype=np.int64), where, first
+
+
+def bam_flatten(slots, slot_off, slot_len, carry, device):
+    """mpn_bam_flatten: -> (text tensor, padded to 16, and its length).  carry: a uint8 device tensor (any view) or None."""
+    import torch
+    lib = _lib()
+    slot_off, slot_len = np.ascontiguousarray(slot_off, dtype=np.int64), np.ascontiguousarray(slot_len, dtype=np.int64)
+    n_carry = 0 if carry is None else carry.numel()
+    total = n_carry + int(slot_len.sum())
+    text = torch.empty(max(_align16(total), 16), dtype=torch.uint8, device=device)
+    got = ct.c_int64(0)
+    rc = lib.mpn_bam_flatten(len(slot_off), slots.data_ptr(), _ptr(slot_off), _ptr(slot_len), carry.data_ptr() if n_carry else None, n_carry,
+                             text.data_ptr(), text.numel(), ct.byref(got))
+    if rc:
+        raise _ffi.MpnError(f'mpn_bam_flatten rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    assert got.value == total
+    return text, total
+
+
+def bam_walk(text, text_len, start, at_header, final, max_records):
+    """mpn_bam_walk -> (rows as a BAM_ROW array, next, status)"""
+    lib = _lib()
+    rows = np.zeros(max_records, dtype=BAM_ROW)
+    n, nxt, status = ct.c_int64(0), ct.c_int64(0), ct.c_int32(0)
+    rc = lib.mpn_bam_walk(text.data_ptr(), int(text_len), int(start), int(bool(at_header)), int(bool(final)), int(max_records), _ptr(rows),
+                          ct.byref(n), ct.byref(nxt), ct.byref(status))
+    if rc:
+        raise _ffi.MpnError(f'mpn_bam_walk rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    return rows[:n.value], nxt.value, status.value
+
+
+def bam_decode(text, text_len, rows, with_qual):
+    """mpn_bam_decode on the (kept) rows -> (bases tensor, qualities tensor or None, both of total + 16 bytes rounded up to 16, names)"""
+    import torch
+    lib = _lib()
+    rows = np.ascontiguousarray(rows, dtype=BAM_ROW)
+    lens = rows['l_seq'].astype(np.int64)
+    off = np.zeros(len(rows), dtype=np.int64)
+    off[1:] = np.cumsum(lens[:-1])
+    size = _align16(int(lens.sum()) + 16)
+    seq = torch.empty(size, dtype=torch.uint8, device=text.device)
+    qual = torch.empty(size, dtype=torch.uint8, device=text.device) if with_qual else None
+    name_len = rows['l_read_name'].astype(np.int64) - 1
+    pool = np.zeros(max(int(name_len.sum()), 1), dtype=np.uint8)
+    rc = lib.mpn_bam_decode(text.data_ptr(), int(text_len), len(rows), _ptr(rows), _ptr(off), seq.data_ptr(), qual.data_ptr() if with_qual else None,
+                            pool.ctypes.data, pool.size)
+    if rc:
+        raise _ffi.MpnError(f'mpn_bam_decode rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    raw, ends = pool.tobytes(), np.cumsum(name_len)
+    names = [raw[e - l:e].decode() for e, l in zip(ends.tolist(), name_len.tolist())]
+    return seq, qual, names
+
+
+def _bam_batch(pieces, device, timings):
+    """pieces: [(text, text_len, kept rows)] in file order, the reads of one batch -> mapper.PackedReads with its device copy"""
+    import time
+    import torch
+    from . import mapper
+    t0 = time.perf_counter()
+    with_qual = any(bool(rows['has_qual'].any()) for _, _, rows in pieces)
+    parts, names = [], []
+    for text, text_len, rows in pieces:
+        seq, qual, nm = bam_decode(text, text_len, rows, with_qual)
+        _tick(timings, 'decode_device_ms', last_bam_device_ms()[2])
+        parts.append((seq, qual, int(rows['l_seq'].astype(np.int64).sum())))
+        names += nm
+    lens = np.concatenate([rows['l_seq'] for _, _, rows in pieces]).astype(np.int32)
+    total = int(lens.astype(np.int64).sum())
+    if len(parts) == 1:
+        seq, qual = parts[0][0][:total + 16], (parts[0][1][:total + 16] if with_qual else None)
+    else:     # a batch whose records lie in the texts of several groups: its pieces are joined, device to device
+        pad = torch.zeros(16, dtype=torch.uint8, device=device)
+        seq = torch.cat([s[:k] for s, _, k in parts] + [pad])
+        qual = torch.cat([q[:k] for _, q, k in parts] + [pad]) if with_qual else None
+    off = np.zeros(len(lens), dtype=np.int64)
+    off[1:] = np.cumsum(lens[:-1].astype(np.int64))
+    t1 = time.perf_counter()
+    buf = seq.cpu().numpy()       # the host copy SAM output and the writers need: one download
+    qbuf = qual.cpu().numpy() if with_qual else None
+    dev = (seq, torch.from_numpy(off).to(device), torch.from_numpy(lens).to(device))
+    torch.cuda.synchronize()
+    _tick(timings, 'decode', t1 - t0)
+    _tick(timings, 'd2h', time.perf_counter() - t1)
+    return mapper.PackedReads.from_arrays(names, buf, off, lens, dev=dev, qbuf=qbuf)
+
+
+def iter_bam_read_batches(stream_or_path, batch_bases=200_000_000, device='cuda', walk_records=None, timings=None):
+    """The reads of one BAM file as mapper.PackedReads of at most batch_bases each (cut as aligner.iter_read_batches cuts FASTQ
+    records), resident on the device, with the semantics of `samtools fastq`.  stream_or_path: a path, or
+    the binary stream fastx.open_once returned for kind 'bam' (read to its end, not closed)."""
+    import time
+    import torch
+    lib = _lib()
+    device = device or 'cuda'
+    own = isinstance(stream_or_path, (str, bytes, os.PathLike))
+    stream = io.BufferedReader(open(stream_or_path, 'rb', buffering=0), buffer_size=1 << 20) if own else stream_or_path
+    walk_records = max(1, bam_walk_records() if walk_records is None else int(walk_records))
+    try:
+        groups = _BgzfGroups(stream, batch_bytes())
+        carry, at_header, text_base = None, True, 0       # text_base: the offset of text[0] in the whole inflated stream
+        pieces, acc, count = [], 0, 0
+        while True:
+            t0 = time.perf_counter()
+            staged, in_off, isize, where, first = groups.next_group()
+            final = groups.eof
+            t1 = time.perf_counter()
+            n = len(isize)
+            d_in = staged.to(device, non_blocking=True)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            so = np.zeros(n + 1, dtype=np.int64)
+            so[1:] = np.cumsum((isize + 15) & ~15)
+            slots = torch.empty(max(int(so[-1]), 16), dtype=torch.uint8, device=device)
+            length, members, status = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+            if n:
+                rc = lib.mpn_gzip_inflate_device(n, d_in.data_ptr(), in_off.ctypes.data, slots.data_ptr(), so.ctypes.data, isize.ctypes.data,
+                                                 length.ctypes.data, members.ctypes.data, status.ctypes.data)
+                if rc:
+                    raise _ffi.MpnError(f'mpn_gzip_inflate_device rc={rc}: {_ffi.hint(_ffi.last_error())}')
+                _tick(timings, 'inflate_device_ms', last_device_ms()[0])
+                bad = np.flatnonzero((status != OK) | (length != isize) | (members != 1))
+                if len(bad):
+                    b = int(bad[0])
+                    what = STATUS_NAMES[status[b]] if status[b] != OK else f'{members[b]} gzip members of {length[b]} bytes, ISIZE {isize[b]}'
+                    raise ValueError(f'BGZF block {first + b} at file offset {where[b]}: {what}')
+            t3 = time.perf_counter()
+            text, text_len = bam_flatten(slots, so[:n], isize, carry, device)
+            _tick(timings, 'flatten_device_ms', last_bam_device_ms()[0])
+            t4 = time.perf_counter()
+            del d_in, slots, carry
+            start, got = 0, []
+            while True:
+                rows, nxt, st = bam_walk(text, text_len, start, at_header, final, walk_records)
+                _tick(timings, 'walk_device_ms', last_bam_device_ms()[1])
+                _tick(timings, 'walk_launches', 1)
+                if st != OK:
+                    raise ValueError(f'BAM text at offset {text_base + nxt} of the inflated stream: {STATUS_NAMES[st]}')
+                if at_header and nxt > start:
+                    at_header = False
+                got.append(rows)
+                start = nxt
+                if len(rows) < walk_records:
+                    break
+            rows = np.concatenate(got)
+            _tick(timings, 'records', len(rows))
+            rows = rows[(rows['flag'] & BAM_SKIP) == 0]
+            t5 = time.perf_counter()
+            for key, dt in (('read', t1 - t0), ('h2d', t2 - t1), ('inflate', t3 - t2), ('flatten', t4 - t3), ('walk', t5 - t4)):
+                _tick(timings, key, dt)
+            lo = 0
+            for i, l in enumerate(rows['l_seq'].tolist()):
+                if count and acc + l > batch_bases:
+                    if i > lo:
+                        pieces.append((text, text_len, rows[lo:i]))
+                    yield _bam_batch(pieces, device, timings)
+                    pieces, acc, count, lo = [], 0, 0, i
+                acc += l
+                count += 1
+            if lo < len(rows):
+                pieces.append((text, text_len, rows[lo:]))
+            if final:
+                break
+            carry = text[start:text_len]
+            text_base += start
+        if count:
+            yield _bam_batch(pieces, device, timings)
+    finally:
+        if own:
+            stream.close()
+
+
+def read_bam(stream_or_path, device='cuda'):
+    """-> list of (name, bases, qualities or None) like fastx.read_fastx(with_qual=True); qualities follow the rule of a PackedReads
+    batch: None if no read of the file has any, '!' for a read without them otherwise."""
+    out = []
+    for b in iter_bam_read_batches(stream_or_path, device=device):
+        for i in range(b.n):
+            a, z = int(b.off[i]), int(b.off[i]) + int(b.lens[i])
+            out.append((b.names[i], b.buf[a:z].tobytes(), None if b.qbuf is None else b.qbuf[a:z].tobytes()))
+    return out
