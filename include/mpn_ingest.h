@@ -3,13 +3,15 @@
  * compressed bytes to the concatenated bases mpn_index_build_device (mpn_map.h) reads, without existing as host strings.
  *
  *   mpn_gzip_inflate   many gzip files (RFC 1952 members of RFC 1951 deflate streams) -> their bytes, one wave per file
- *                      (csrc/inflate_kernels.hip; the serial decoder is csrc/inflate_core.h, which also compiles for the host).
+ *                      (csrc/inflate_kernels.hip; the serial decoder is csrc/inflate_core.h and the CRC-32 arithmetic it shares
+ *                      with the BGZF writer csrc/crc32_poly.h, which both also compile for the host).
  *   mpn_fasta_scan     FASTA text in HBM -> the bases of all records without gaps + a record table (csrc/fasta_kernels.hip),
  *                      with the semantics of megapath_nano_amd/fastx.py iter_fastx.
  *
  * and of BAM files as read input (the BGZF blocks of the file are the streams of mpn_gzip_inflate_device; csrc/bam_in_kernels.hip):
  *
  *   mpn_bam_flatten    the inflated slots of a group of blocks -> one contiguous BAM text, behind the unconsumed tail of the group before
+ *                      (a chunked gather: its search, 16-byte load and launch shape are csrc/gather16.h, shared with mpn_reads.h)
  *   mpn_bam_walk       the text -> a table with a row per record (the walk itself is csrc/bam_walk_core.h, which also compiles
  *                      for the host)
  *   mpn_bam_decode     the rows of a batch of reads -> ASCII bases, Phred+33 qualities and names, reads that are stored as their

@@ -2,9 +2,10 @@
 // mpn_gzip_inflate_device; here their text is made contiguous, its records are found and the reads are decoded into the layout of
 // mapper.PackedReads.from_arrays.  Semantics: `samtools fastq`.
 //
-//   bam_flatten_kernel   slots (16-byte aligned, gaps between them) + the tail the group before left -> one text.  Modelled on
-//                        split_gather_kernel (read_split_kernels.hip): a wave owns an aligned MPN_BAM_CHUNK of the OUTPUT, a lane
-//                        16 bytes of it; every store is one aligned 16-byte store and every output byte is written once.
+//   bam_flatten_kernel   slots (16-byte aligned, gaps between them) + the tail the group before left -> one text.  A chunked
+//                        gather like split_gather_kernel (read_split_kernels.hip), on the pieces of gather16.h: a wave owns an
+//                        aligned MPN_BAM_CHUNK of the OUTPUT, a lane 16 bytes of it; every store is one aligned 16-byte store and
+//                        every output byte is written once.
 //   bam_walk_kernel      one wave.  The record starts are a dependent chain through block_size: lane 0 follows it for 64 records
 //                        (one 4-byte read per record: bam_walk_core.h bamw_step), then the 64 lanes read the fixed fields of
 //                        those records side by side and store a 16-byte row each (bamw_row).  Stops at the first record that is
@@ -18,7 +19,7 @@
 //                        Phred+33; a reverse read is taken from the mirrored position, nibbles and bytes in the opposite order,
 //                        through the complement table.  Lanes at a read's head or tail go byte by byte.
 // No atomics anywhere; the only flag (a row that does not fit the text) is a plain store of one value.
-#include "mpn_common.h"
+#include "gather16.h"
 #include "bam_walk_core.h"
 
 #include <string.h>
@@ -29,60 +30,28 @@ using namespace mpn_bamw;
 
 thread_local double tl_bam_ms[3] = {0, 0, 0};   // device time of the last calls on this thread: flatten, walk, decode
 
-constexpr int BI_THREADS = 256, BI_WAVES = BI_THREADS / 64;
-constexpr int BI_MAX_BLOCKS = 256 * 8;   // 8 resident blocks of 256 threads on each of 256 CUs; more output is taken in further rounds
-static_assert(MPN_BAM_CHUNK == 64 * 16, "a wave step is 64 lanes x 16 bytes");
 static_assert(sizeof(mpn_bam_row) == 16, "a row is one 16-byte store");
-
-// last j in [lo, hi] with v[j] <= q, or lo - 1 if there is none (v ascending)
-__device__ __forceinline__ int64_t bi_last_le(const int64_t *__restrict__ v, int64_t lo, int64_t hi, int64_t q) {
-    int64_t a = lo, b = hi + 1;
-    while (a < b) {
-        const int64_t mid = a + ((b - a) >> 1);
-        if (v[mid] <= q) a = mid + 1; else b = mid;
-    }
-    return a - 1;
-}
-
-// 16 bytes from any address, by the one or two aligned 16-byte vectors that hold them.  Both vectors hold at least one of the 16
-// bytes, so they lie in the allocation the bytes lie in (device allocations are 16-byte granular).
-__device__ __forceinline__ uint4 bi_load16(const uint8_t *p) {
-    const uintptr_t a = (uintptr_t)p;
-    const uint32_t sh16 = (uint32_t)(a & 15);
-    const uint4 *v = (const uint4 *)(a & ~(uintptr_t)15);
-    const uint4 lo4 = v[0], hi4 = sh16 ? v[1] : make_uint4(0, 0, 0, 0);
-    uint32_t x0, x1, x2, x3, x4;
-    switch (sh16 >> 2) {
-        case 0: x0 = lo4.x; x1 = lo4.y; x2 = lo4.z; x3 = lo4.w; x4 = hi4.x; break;
-        case 1: x0 = lo4.y; x1 = lo4.z; x2 = lo4.w; x3 = hi4.x; x4 = hi4.y; break;
-        case 2: x0 = lo4.z; x1 = lo4.w; x2 = hi4.x; x3 = hi4.y; x4 = hi4.z; break;
-        default: x0 = lo4.w; x1 = hi4.x; x2 = hi4.y; x3 = hi4.z; x4 = hi4.w; break;
-    }
-    const uint32_t sh = sh16 & 3;
-    return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x2, x1, sh), __builtin_amdgcn_alignbyte(x3, x2, sh),
-                      __builtin_amdgcn_alignbyte(x4, x3, sh));
-}
 
 // ---- flatten -------------------------------------------------------------------------------------------------------------------
 // Segment j: seg_len[j] > 0 bytes from the address seg_src[j] to text[seg_dst[j] ..); seg_dst ascending, the segments back to back
 // from 0 to text_len.  out_bytes: text_len rounded up to 16.
-__global__ __launch_bounds__(BI_THREADS) void bam_flatten_kernel(const int64_t *__restrict__ seg_dst, const int64_t *__restrict__ seg_src,
-                                                                 const int64_t *__restrict__ seg_len, int64_t n_seg, uint8_t *__restrict__ text,
-                                                                 int64_t out_bytes) {
+__global__ __launch_bounds__(G16_THREADS) void bam_flatten_kernel(const int64_t *__restrict__ seg_dst, const int64_t *__restrict__ seg_src,
+                                                                  const int64_t *__restrict__ seg_len, int64_t n_seg, uint8_t *__restrict__ text,
+                                                                  int64_t out_bytes) {
     const int lane = threadIdx.x & 63;
     const int64_t n_chunks = (out_bytes + MPN_BAM_CHUNK - 1) / MPN_BAM_CHUNK;
-    for (int64_t c = (int64_t)blockIdx.x * BI_WAVES + (threadIdx.x >> 6); c < n_chunks; c += (int64_t)gridDim.x * BI_WAVES) {
+    for (int64_t c = (int64_t)blockIdx.x * G16_WAVES + (threadIdx.x >> 6); c < n_chunks; c += (int64_t)gridDim.x * G16_WAVES) {
         const int64_t c0 = c * MPN_BAM_CHUNK;
         const int64_t c1 = (c0 + MPN_BAM_CHUNK < out_bytes ? c0 + MPN_BAM_CHUNK : out_bytes) - 1;
         // wave-uniform: the segments that can cover bytes of [c0, c1] (seg_dst[0] = 0, so jlo >= 0)
-        const int64_t jlo = bi_last_le(seg_dst, 0, n_seg - 1, c0), jhi = bi_last_le(seg_dst, jlo, n_seg - 1, c1);
+        const int64_t jlo = last_le(seg_dst, 0, n_seg - 1, c0), jhi = last_le(seg_dst, jlo, n_seg - 1, c1);
         const int64_t p = c0 + lane * 16;
         if (p >= out_bytes) continue;
-        const int64_t j = bi_last_le(seg_dst, jlo, jhi, p);
+        const int64_t j = last_le(seg_dst, jlo, jhi, p);
         const int64_t d = seg_dst[j], l = seg_len[j];
         uint4 v = make_uint4(0, 0, 0, 0);
         if (p + 16 <= d + l) {
-            v = bi_load16((const uint8_t *)(uintptr_t)seg_src[j] + (p - d));
+            v = load16((const uint8_t *)(uintptr_t)seg_src[j] + (p - d));
         } else {
             // the end of a segment, short segments, or the padding behind the text: byte by byte
             uint32_t w[4] = {0, 0, 0, 0};
@@ -90,7 +59,7 @@ __global__ __launch_bounds__(BI_THREADS) void bam_flatten_kernel(const int64_t *
 #pragma unroll 1
             for (int b = 0; b < 16; ++b) {
                 const int64_t q = p + b;
-                jj = bi_last_le(seg_dst, jj, jhi, q);
+                jj = last_le(seg_dst, jj, jhi, q);
                 const int64_t dd = seg_dst[jj];
                 uint32_t byte = 0;
                 if (q < dd + seg_len[jj]) byte = ((const uint8_t *)(uintptr_t)seg_src[jj])[q - dd];
@@ -204,17 +173,17 @@ __device__ __forceinline__ uint32_t bi_base(uint32_t nib, bool rev) {
 // four bytes + 33 each, mod 256, no carry from byte to byte
 __device__ __forceinline__ uint32_t bi_add33(uint32_t x) { return ((x & 0x7f7f7f7fu) + 0x21212121u) ^ (x & 0x80808080u); }
 
-__global__ __launch_bounds__(BI_THREADS) void bam_decode_kernel(const uint8_t *__restrict__ text, const BamRec *__restrict__ recs,
-                                                                const int64_t *__restrict__ out_off, const int32_t *__restrict__ chunk_rec,
-                                                                int64_t out_bytes, uint8_t *__restrict__ d_seq, uint8_t *__restrict__ d_qual) {
+__global__ __launch_bounds__(G16_THREADS) void bam_decode_kernel(const uint8_t *__restrict__ text, const BamRec *__restrict__ recs,
+                                                                 const int64_t *__restrict__ out_off, const int32_t *__restrict__ chunk_rec,
+                                                                 int64_t out_bytes, uint8_t *__restrict__ d_seq, uint8_t *__restrict__ d_qual) {
     const int lane = threadIdx.x & 63;
     const int64_t n_chunks = (out_bytes + MPN_BAM_CHUNK - 1) / MPN_BAM_CHUNK;
-    for (int64_t c = (int64_t)blockIdx.x * BI_WAVES + (threadIdx.x >> 6); c < n_chunks; c += (int64_t)gridDim.x * BI_WAVES) {
+    for (int64_t c = (int64_t)blockIdx.x * G16_WAVES + (threadIdx.x >> 6); c < n_chunks; c += (int64_t)gridDim.x * G16_WAVES) {
         // wave-uniform: the records that can cover bytes of the chunk (out_off[0] = 0, so the first of them is >= 0)
         const int64_t jlo = chunk_rec[c], jhi = chunk_rec[c + 1];
         const int64_t p = c * MPN_BAM_CHUNK + lane * 16;
         if (p >= out_bytes) continue;   // (out_bytes is a multiple of 16)
-        const int64_t j = bi_last_le(out_off, jlo, jhi, p);
+        const int64_t j = last_le(out_off, jlo, jhi, p);
         const int64_t d = out_off[j];
         const BamRec r = recs[j];
         uint4 vs = make_uint4(0, 0, 0, 0), vq = make_uint4(0, 0, 0, 0);
@@ -237,7 +206,7 @@ __global__ __launch_bounds__(BI_THREADS) void bam_decode_kernel(const uint8_t *_
             vs = make_uint4(o[0], o[1], o[2], o[3]);
             if (d_qual) {
                 if (r.bits & BR_QUAL) {
-                    const uint4 q = bi_load16(text + r.seq + (((int64_t)r.l_seq + 1) >> 1) + lo);
+                    const uint4 q = load16(text + r.seq + (((int64_t)r.l_seq + 1) >> 1) + lo);
                     const uint32_t a0 = bi_add33(q.x), a1 = bi_add33(q.y), a2 = bi_add33(q.z), a3 = bi_add33(q.w);
                     vq = rev ? make_uint4(__builtin_bswap32(a3), __builtin_bswap32(a2), __builtin_bswap32(a1), __builtin_bswap32(a0))
                              : make_uint4(a0, a1, a2, a3);
@@ -252,7 +221,7 @@ __global__ __launch_bounds__(BI_THREADS) void bam_decode_kernel(const uint8_t *_
 #pragma unroll 1
             for (int b = 0; b < 16; ++b) {
                 const int64_t q = p + b;
-                jj = bi_last_le(out_off, jj, jhi, q);
+                jj = last_le(out_off, jj, jhi, q);
                 const BamRec rr = recs[jj];
                 const int64_t k = q - out_off[jj];
                 if (k >= rr.l_seq || (rr.bits & BR_OUT)) continue;
@@ -275,25 +244,6 @@ __global__ __launch_bounds__(BI_THREADS) void bam_decode_kernel(const uint8_t *_
 }  // namespace mpn
 
 using namespace mpn;
-
-namespace {
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    int create() { for (hipEvent_t &x : e) MPN_HIP_CHECK(hipEventCreate(&x)); return 0; }
-    int elapsed(double *ms) {
-        float f = 0;
-        MPN_HIP_CHECK(hipEventElapsedTime(&f, e[0], e[1]));
-        *ms = f;
-        return 0;
-    }
-};
-
-int grid_for(int64_t out_bytes) {
-    const int64_t n_chunks = (out_bytes + MPN_BAM_CHUNK - 1) / MPN_BAM_CHUNK;
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n_chunks + BI_WAVES - 1) / BI_WAVES, BI_MAX_BLOCKS));
-}
-}  // namespace
 
 extern "C" void mpn_bam_last_device_ms(double *flatten_ms, double *walk_ms, double *decode_ms) {
     if (flatten_ms) *flatten_ms = tl_bam_ms[0];
@@ -328,17 +278,15 @@ extern "C" int32_t mpn_bam_flatten(int64_t n, const void *d_slots, const int64_t
     }
     hipStream_t st = 0;
     DevBuf<int64_t> d_dst, d_src, d_len;
-    Events ev;
-    if (ev.create()) return -1;
+    DevTimer tm;
     const size_t S = dst.size();
-    if (d_dst.upload(dst.data(), S, st) || d_src.upload(src.data(), S, st) || d_len.upload(len.data(), S, st)) return -1;
-    MPN_HIP_CHECK(hipEventRecord(ev.e[0], st));
-    hipLaunchKernelGGL(bam_flatten_kernel, dim3(grid_for(out_bytes)), dim3(BI_THREADS), 0, st, (const int64_t *)d_dst.p, (const int64_t *)d_src.p,
+    if (d_dst.upload(dst.data(), S, st) || d_src.upload(src.data(), S, st) || d_len.upload(len.data(), S, st) || tm.start(st)) return -1;
+    hipLaunchKernelGGL(bam_flatten_kernel, dim3(grid_for(out_bytes)), dim3(G16_THREADS), 0, st, (const int64_t *)d_dst.p, (const int64_t *)d_src.p,
                        (const int64_t *)d_len.p, (int64_t)S, (uint8_t *)d_text, out_bytes);
     MPN_HIP_CHECK(hipGetLastError());
-    MPN_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    if (tm.stop(st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));      // the segment arrays must outlive the kernel
-    return ev.elapsed(&tl_bam_ms[0]);
+    return tm.elapsed_ms(&tl_bam_ms[0]);
 }
 
 extern "C" int32_t mpn_bam_walk(const void *d_text, int64_t text_len, int64_t start, int32_t at_header, int32_t final, int64_t max_records,
@@ -352,13 +300,12 @@ extern "C" int32_t mpn_bam_walk(const void *d_text, int64_t text_len, int64_t st
     hipStream_t st = 0;
     DevBuf<mpn_bam_row> d_rows;
     DevBuf<int64_t> d_res;
-    Events ev;
-    if (ev.create() || d_rows.alloc((size_t)max_records) || d_res.alloc(3)) return -1;
-    MPN_HIP_CHECK(hipEventRecord(ev.e[0], st));
+    DevTimer tm;
+    if (d_rows.alloc((size_t)max_records) || d_res.alloc(3) || tm.start(st)) return -1;
     hipLaunchKernelGGL(bam_walk_kernel, dim3(1), dim3(64), 0, st, (const uint8_t *)d_text, text_len, start, (int)(at_header != 0), (int)(final != 0),
                        max_records, d_rows.p, d_res.p);
     MPN_HIP_CHECK(hipGetLastError());
-    MPN_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    if (tm.stop(st)) return -1;
     int64_t res[3] = {0, 0, 0};
     if (d_res.download(res, 3, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
@@ -366,7 +313,7 @@ extern "C" int32_t mpn_bam_walk(const void *d_text, int64_t text_len, int64_t st
     if (d_rows.download(rows, (size_t)res[0], st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
     *n_records = res[0]; *next = res[1]; *status = (int32_t)res[2];
-    return ev.elapsed(&tl_bam_ms[1]);
+    return tm.elapsed_ms(&tl_bam_ms[1]);
 }
 
 extern "C" int32_t mpn_bam_decode(const void *d_text, int64_t text_len, int64_t n, const mpn_bam_row *rows, const int64_t *out_off, void *d_seq,
@@ -414,22 +361,21 @@ extern "C" int32_t mpn_bam_decode(const void *d_text, int64_t text_len, int64_t 
     DevBuf<int32_t> d_cr, d_bad;
     DevBuf<BamRec> d_recs;
     DevBuf<uint8_t> d_pool;
-    Events ev;
-    if (ev.create() || d_rows.upload(rows, (size_t)n, st) || d_off.upload(out_off, (size_t)n, st) || d_po.upload(pool_off.data(), (size_t)n, st) ||
+    DevTimer tm;
+    if (d_rows.upload(rows, (size_t)n, st) || d_off.upload(out_off, (size_t)n, st) || d_po.upload(pool_off.data(), (size_t)n, st) ||
         d_cr.upload(chunk_rec.data(), (size_t)n_chunks + 1, st) || d_recs.alloc((size_t)n) || d_pool.alloc((size_t)pool) || d_bad.alloc(1) ||
-        d_bad.zero(st))
+        d_bad.zero(st) || tm.start(st))
         return -1;
-    MPN_HIP_CHECK(hipEventRecord(ev.e[0], st));
     hipLaunchKernelGGL(bam_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, text_len,
                        (const mpn_bam_row *)d_rows.p, (const int64_t *)d_po.p, n, d_recs.p, d_pool.p, d_bad.p);
-    hipLaunchKernelGGL(bam_decode_kernel, dim3(grid_for(out_bytes)), dim3(BI_THREADS), 0, st, (const uint8_t *)d_text, (const BamRec *)d_recs.p,
+    hipLaunchKernelGGL(bam_decode_kernel, dim3(grid_for(out_bytes)), dim3(G16_THREADS), 0, st, (const uint8_t *)d_text, (const BamRec *)d_recs.p,
                        (const int64_t *)d_off.p, (const int32_t *)d_cr.p, out_bytes, (uint8_t *)d_seq, (uint8_t *)d_qual);
     MPN_HIP_CHECK(hipGetLastError());
-    MPN_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    if (tm.stop(st)) return -1;
     int32_t bad = 0;
     if (d_bad.download(&bad, 1, st) || d_pool.download((uint8_t *)name_pool, (size_t)pool, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
-    if (ev.elapsed(&tl_bam_ms[2])) return -1;
+    if (tm.elapsed_ms(&tl_bam_ms[2])) return -1;
     if (bad) { set_error("mpn_bam_decode: a row's bases and qualities pass the end of the text"); return -2; }
     return 0;
 }

@@ -16,12 +16,14 @@
 //      not smaller than the stored form (5 + n bytes), the stored form is written.
 //   D  emission: header items and tokens are one list; a wave scan + 4 wave totals place each item's bits, lanes OR them into a
 //      1.6 KiB LDS window (double-buffered: two barriers per 256 items) and the window's complete bytes go to the block's slot.
-//   E  CRC-32: a slice per lane with the byte table, slices joined by multiplying with x^(8 * bytes behind the slice) mod P.
+//   E  CRC-32: a slice per lane with the byte table, slices joined by multiplying with x^(8 * bytes behind the slice) mod P
+//      (crc32_poly.h, shared with the inflate kernel).
 // Blocks land in slots of worst-case size; bgzf_scan_kernel turns the sizes into addresses and bgzf_pack_kernel moves them together.
 //
 // Per 65280-byte block: 64 KiB read about 3 times (match, CRC, emission) + 255 KiB of tokens written and read once: ~0.7 MB through
 // L2 for 64 KiB of payload.  LDS 46 KiB per workgroup (below the 64 KiB every runtime grants; 3 workgroups share a CU).
 #include "mpn_common.h"
+#include "crc32_poly.h"
 #include "../../include/mpn_bam.h"
 
 #include <cstring>
@@ -76,25 +78,6 @@ __device__ __forceinline__ int bz_match_len(const uint8_t *__restrict__ p, int a
     }
     while (k < maxl && p[a + k] == p[b + k]) ++k;
     return k;
-}
-
-// product of two polynomials mod the CRC-32 polynomial, reflected: bit 31 is x^0
-__device__ __forceinline__ uint32_t bz_crc_mul(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) r ^= b;
-        b = (b & 1) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return r;
-}
-// x^(8k) mod P
-__device__ __forceinline__ uint32_t bz_crc_xpow8(uint32_t k) {
-    uint32_t r = 0x80000000u, b = 0x00800000u;
-    for (int i = 0; i < 17 && k; ++i, k >>= 1) {
-        if (k & 1) r = bz_crc_mul(r, b);
-        b = bz_crc_mul(b, b);
-    }
-    return r;
 }
 
 struct BzShared {
@@ -223,11 +206,7 @@ __global__ __launch_bounds__(BZ_THREADS) void bgzf_deflate_kernel(const uint8_t 
     for (int k = tid; k < BZ_WIN_WORDS; k += BZ_THREADS) { s.win[0][k] = 0; s.win[1][k] = 0; }
     for (int k = tid; k < BZ_SYM_PAD; k += BZ_THREADS) s.hist_ll[k] = 0;
     if (tid < 32) { s.hist_d[tid] = 0; s.hist_cl[tid] = 0; }
-    {
-        uint32_t c = (uint32_t)tid;
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        s.crc_tab[tid] = c;
-    }
+    s.crc_tab[tid] = mpn_crc::crc_entry((uint32_t)tid);
     if (tid == 0) { s.bits = 0; s.crc = 0; s.hlit = 257; s.hdist = 1; }
     __syncthreads();
 
@@ -237,8 +216,8 @@ __global__ __launch_bounds__(BZ_THREADS) void bgzf_deflate_kernel(const uint8_t 
         const int a = min(n, tid * per), b = min(n, a + per);
         uint32_t c = 0;
         for (int k = a; k < b; ++k) c = s.crc_tab[(c ^ p[k]) & 0xff] ^ (c >> 8);
-        uint32_t part = bz_crc_mul(c, bz_crc_xpow8((uint32_t)(n - b)));
-        if (tid == 0) part ^= bz_crc_mul(0xFFFFFFFFu, bz_crc_xpow8((uint32_t)n));
+        uint32_t part = mpn_crc::crc_slice(c, (uint32_t)(n - b));
+        if (tid == 0) part = mpn_crc::crc_join(0xFFFFFFFFu, (uint32_t)n, part);     // the register a member starts with
         atomicXor(&s.crc, part);
     }
 
@@ -465,17 +444,11 @@ __global__ __launch_bounds__(BZ_THREADS) void bgzf_pack_kernel(const uint8_t *__
     for (int k = threadIdx.x; k < len; k += BZ_THREADS) d[k] = src[k];
 }
 
+thread_local double tl_bgzf_ms[2] = {0, 0};   // device time of the last call on this thread: deflate + scan, pack
+
 }  // namespace mpn
 
 using namespace mpn;
-
-namespace {
-thread_local double tl_bgzf_ms[2] = {0, 0};   // device time of the last call on this thread: deflate + scan, pack
-struct EventPair {                            // three HIP events around the launches; destroyed on every way out
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~EventPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-}  // namespace
 
 extern "C" void mpn_bgzf_last_device_ms(double *deflate_ms, double *pack_ms) {
     if (deflate_ms) *deflate_ms = tl_bgzf_ms[0];
@@ -507,14 +480,12 @@ extern "C" int64_t mpn_bgzf_compress(int64_t n_blocks, const uint8_t *payload, c
     DevBuf<int32_t> d_sizes;
     DevBuf<int> d_flag;
     const int64_t chunk = std::min<int64_t>(n_blocks, BZ_CHUNK);
-    EventPair ev;
+    DevTimer tm_deflate, tm_pack;
     tl_bgzf_ms[0] = tl_bgzf_ms[1] = 0;
-    for (hipEvent_t &x : ev.e) MPN_HIP_CHECK(hipEventCreate(&x));
     if (d_pay.upload(payload + pay_off[0], (size_t)pay_bytes, st) || d_po.upload(pay_off, (size_t)n_blocks + 1, st) ||
         d_slots.alloc((size_t)(pay_bytes + BZ_SLOT_EXTRA * n_blocks)) || d_oo.alloc((size_t)n_blocks + 1) || d_sizes.alloc((size_t)n_blocks) ||
-        d_flag.alloc(1) || (mode != MPN_BGZF_STORED && d_tok.alloc((size_t)chunk * BZ_TOK_STRIDE)))
+        d_flag.alloc(1) || (mode != MPN_BGZF_STORED && d_tok.alloc((size_t)chunk * BZ_TOK_STRIDE)) || tm_deflate.start(st))
         return -1;
-    MPN_HIP_CHECK(hipEventRecord(ev.e[0], st));
     for (int64_t b0 = 0; b0 < n_blocks; b0 += chunk) {   // launches on one stream run one after another: they share the token rows
         const int g = (int)std::min<int64_t>(chunk, n_blocks - b0);
         hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(g), dim3(BZ_THREADS), 0, st, (const uint8_t *)d_pay.p, (const int64_t *)d_po.p, b0, d_slots.p, d_tok.p,
@@ -522,25 +493,21 @@ extern "C" int64_t mpn_bgzf_compress(int64_t n_blocks, const uint8_t *payload, c
     }
     hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)d_sizes.p, n_blocks, d_oo.p, d_flag.p);
     MPN_HIP_CHECK(hipGetLastError());
-    MPN_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    if (tm_deflate.stop(st)) return -1;
     int flag = 0;
     if (d_oo.download(out_off, (size_t)n_blocks + 1, st) || d_flag.download(&flag, 1, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0;
-    MPN_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    tl_bgzf_ms[0] = ms;
+    if (tm_deflate.elapsed_ms(&tl_bgzf_ms[0])) return -1;
     if (flag) { set_error("mpn_bgzf_compress: a block's emitted bits disagree with its computed size"); return -1; }
     const int64_t total = out_off[n_blocks];
     if (total > out_cap) { set_error("mpn_bgzf_compress: out_cap %lld is below the %lld bytes needed", (long long)out_cap, (long long)total); return -3; }
-    if (d_out.alloc((size_t)total)) return -1;
-    MPN_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    if (d_out.alloc((size_t)total) || tm_pack.start(st)) return -1;
     hipLaunchKernelGGL(bgzf_pack_kernel, dim3((unsigned)n_blocks), dim3(BZ_THREADS), 0, st, (const uint8_t *)d_slots.p, (const int64_t *)d_po.p,
                        (const int64_t *)d_oo.p, d_out.p);
     MPN_HIP_CHECK(hipGetLastError());
-    MPN_HIP_CHECK(hipEventRecord(ev.e[2], st));
+    if (tm_pack.stop(st)) return -1;
     if (d_out.download(out, (size_t)total, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
-    MPN_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
-    tl_bgzf_ms[1] = ms;
+    if (tm_pack.elapsed_ms(&tl_bgzf_ms[1])) return -1;
     return total;
 }

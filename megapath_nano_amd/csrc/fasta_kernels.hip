@@ -19,8 +19,6 @@
 
 namespace mpn {
 
-extern thread_local double tl_ingest_ms[2];
-
 constexpr int FA_THREADS = 256, FA_PER = 16, FA_TILE = FA_THREADS * FA_PER;
 constexpr int FA_SCAN_THREADS = 1024;
 constexpr int FA_SEQ = 0, FA_HDR = 1, FA_INHERIT = 2;
@@ -237,13 +235,6 @@ __global__ __launch_bounds__(256) void fa_names_kernel(const uint8_t *__restrict
 
 using namespace mpn;
 
-namespace {
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-}  // namespace
-
 extern "C" int32_t mpn_fasta_scan(int64_t n, const void *d_text, const int64_t *text_off, const int64_t *text_len, void *d_seq, int64_t seq_cap,
                                   int64_t *n_records, int64_t *n_bases, int32_t *status, int64_t rec_cap, int32_t *rec_stream,
                                   int64_t *rec_name_off, int32_t *rec_name_len, int64_t *rec_seq_len, char *name_pool, int64_t name_pool_cap) {
@@ -268,14 +259,12 @@ extern "C" int32_t mpn_fasta_scan(int64_t n, const void *d_text, const int64_t *
     DevBuf<FaTileSum> d_sums;
     DevBuf<uint8_t> d_kind, d_pool;
     DevBuf<int32_t> d_stat, d_rs, d_rnl;
-    Events ev;
-    for (hipEvent_t &x : ev.e) MPN_HIP_CHECK(hipEventCreate(&x));
+    DevTimer tm;
     if (d_off.upload(text_off, (size_t)n, st) || d_len.upload(text_len, (size_t)n, st) || d_tf.upload(tile_first.data(), (size_t)n + 1, st) ||
         d_sums.alloc((size_t)T) || d_sb.alloc((size_t)T + 1) || d_rb.alloc((size_t)T + 1) || d_kind.alloc((size_t)T) || d_stat.alloc((size_t)n) ||
-        d_stat.zero(st))
+        d_stat.zero(st) || tm.start(st))
         return -1;
     const uint8_t *text = (const uint8_t *)d_text;
-    MPN_HIP_CHECK(hipEventRecord(ev.e[0], st));
     hipLaunchKernelGGL(fa_summary_kernel, dim3((unsigned)T), dim3(FA_THREADS), 0, st, text, (const int64_t *)d_off.p, (const int64_t *)d_len.p,
                        (const int64_t *)d_tf.p, (int)n, d_sums.p);
     hipLaunchKernelGGL(fa_scan_kernel, dim3(1), dim3(FA_SCAN_THREADS), 0, st, (const FaTileSum *)d_sums.p, T, d_sb.p, d_rb.p, d_kind.p);
@@ -294,7 +283,7 @@ extern "C" int32_t mpn_fasta_scan(int64_t n, const void *d_text, const int64_t *
                        (const int64_t *)d_tf.p, (int)n, (const int64_t *)d_sb.p, (const int64_t *)d_rb.p, (const uint8_t *)d_kind.p,
                        full ? (uint8_t *)d_seq : nullptr, d_stat.p, full ? d_rs.p : nullptr, d_rno.p, d_rnl.p, d_rss.p, B, R);
     MPN_HIP_CHECK(hipGetLastError());
-    MPN_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    if (tm.stop(st)) return -1;
     if (d_stat.download(status, (size_t)n, st)) return -1;
     std::vector<int64_t> starts((size_t)R);
     if (full && R > 0 &&
@@ -302,9 +291,7 @@ extern "C" int32_t mpn_fasta_scan(int64_t n, const void *d_text, const int64_t *
          d_rss.download(starts.data(), (size_t)R, st)))
         return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0;
-    MPN_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    tl_ingest_ms[1] = ms;
+    if (tm.elapsed_ms(&tl_ingest_ms[1])) return -1;
     if (!full || R == 0) return 0;
     std::vector<int64_t> pool_off((size_t)R);
     int64_t pool = 0;

@@ -5,11 +5,12 @@
 // inf_run() decodes until the 32 KiB window ring holds INF_HALF bytes that have not been flushed, until a member's deflate stream
 // has ended, or until the stream is finished (status set).  The caller then flushes ring[flushed .. out_pos) -- stores what the
 // slot can take, folds the bytes into the member's CRC-32 -- and calls again.  After the flush that follows a member's last block
-// the next call checks the trailer against that CRC.  Bounds: every read of the input is checked against in_end, every ring index
-// is masked, and each pass of the symbol loop consumes at least one bit or leaves.
+// the next call checks the trailer against that CRC (the CRC arithmetic is in crc32_poly.h).  Bounds: every read of the input is
+// checked against in_end, every ring index is masked, and each pass of the symbol loop consumes at least one bit or leaves.
 #pragma once
 #include <stdint.h>
 #include "../../include/mpn_ingest.h"
+#include "crc32_poly.h"
 
 #if defined(__HIPCC__)
 #define INF_HD __host__ __device__ inline
@@ -51,28 +52,6 @@ INF_HD void inf_init(InfState *s, int64_t in_begin, int64_t in_end) {
     s->ip = in_begin; s->in_end = in_end; s->buf = 0; s->nb = 0;
     s->out_pos = 0; s->member_start = 0; s->flushed = 0; s->crc = 0xFFFFFFFFu; s->stored_left = 0;
     s->phase = INF_PH_HEADER; s->last = 0; s->members = 0; s->status = MPN_INFLATE_OK;
-}
-
-// ---- CRC-32 (RFC 1952 section 8), reflected: bit 31 of a register is x^0 ----
-INF_HD uint32_t inf_crc_entry(uint32_t c) {
-    for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-    return c;
-}
-INF_HD uint32_t inf_crc_mul(uint32_t a, uint32_t b) {      // product of two polynomials mod P
-    uint32_t r = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) r ^= b;
-        b = (b & 1) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return r;
-}
-INF_HD uint32_t inf_crc_xpow8(uint32_t k) {                // x^(8k) mod P
-    uint32_t r = 0x80000000u, b = 0x00800000u;
-    for (int i = 0; i < 32 && k; ++i, k >>= 1) {
-        if (k & 1) r = inf_crc_mul(r, b);
-        b = inf_crc_mul(b, b);
-    }
-    return r;
 }
 
 // ---- codes ----
@@ -339,7 +318,7 @@ INF_HD void inf_flush_serial(InfState *s, const uint8_t *ring, uint8_t *slot, in
     for (int64_t p = s->flushed; p < s->out_pos; ++p) {
         const uint8_t b = ring[p & INF_MASK];
         if (p < cap) slot[p] = b;
-        s->crc = inf_crc_entry((s->crc ^ b) & 0xff) ^ (s->crc >> 8);
+        s->crc = mpn_crc::crc_entry((s->crc ^ b) & 0xff) ^ (s->crc >> 8);
     }
     s->flushed = s->out_pos;
 }

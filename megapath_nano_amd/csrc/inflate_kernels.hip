@@ -7,8 +7,8 @@
 //               trailers) into a 32 KiB ring in LDS: back-references read LDS, never global memory this workgroup has written.
 //   all lanes   flush the ring whenever 16 KiB are pending or a member ends: 16-byte stores to the stream's slot (as far as the
 //               slot's capacity reaches: an overflowing stream is decoded to its end without stores, its exact length is reported),
-//               and the CRC-32 of the flushed bytes, a slice per lane joined by x^(8 * bytes behind the slice) mod P as in
-//               bgzf_kernels.hip stage E, folded into the member's register.
+//               and the CRC-32 of the flushed bytes, a slice per lane joined by x^(8 * bytes behind the slice) mod P
+//               (crc32_poly.h, as bgzf_kernels.hip stage E does), folded into the member's register.
 //
 // LDS per workgroup: 32 KiB ring + 2 x 2.6 KiB codes + 1 KiB CRC table + 0.3 KiB code lengths = 39 448 B (4 workgroups share a
 // CU's 160 KiB; below the 64 KiB every runtime grants).  Every loop runs to the stream's remaining input, to
@@ -45,9 +45,9 @@ __device__ __forceinline__ uint32_t inf_flush_wave(const InfShared &s, int lane,
     const int a = min(L, lane * per), b = min(L, a + per);
     uint32_t c = 0;
     for (int k = a; k < b; ++k) c = s.crc_tab[(c ^ s.ring[(f + k) & INF_MASK]) & 0xff] ^ (c >> 8);
-    uint32_t part = inf_crc_mul(c, inf_crc_xpow8((uint32_t)(L - b)));
+    uint32_t part = mpn_crc::crc_slice(c, (uint32_t)(L - b));
     for (int off = 32; off >= 1; off >>= 1) part ^= (uint32_t)__shfl_xor((int)part, off);
-    const uint32_t out_crc = inf_crc_mul(crc, inf_crc_xpow8((uint32_t)L)) ^ part;
+    const uint32_t out_crc = mpn_crc::crc_join(crc, (uint32_t)L, part);
 
     const int head = min(L, (int)((16 - (f & 15)) & 15));
     if (lane < head) { const long long p = f + lane; if (p < cap) slot[p] = s.ring[p & INF_MASK]; }
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(INF_THREADS) void gzip_inflate_kernel(const uint8_t
     const int64_t in_len = in_off[i + 1] - in_off[i];
     uint8_t *__restrict__ slot = out + slot_off[i];
     const long long cap = slot_cap[i];
-    for (int k = lane; k < 256; k += INF_THREADS) s.crc_tab[k] = inf_crc_entry((uint32_t)k);
+    for (int k = lane; k < 256; k += INF_THREADS) s.crc_tab[k] = mpn_crc::crc_entry((uint32_t)k);
     InfState st;
     inf_init(&st, in_off[i] - base, in_off[i + 1] - base);
     __syncthreads();
@@ -106,11 +106,6 @@ __global__ __launch_bounds__(INF_THREADS) void gzip_inflate_kernel(const uint8_t
 using namespace mpn;
 
 namespace {
-struct Events {                                // HIP events around the launches; destroyed on every way out
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 int check_args(int64_t n, const int64_t *in_off, const int64_t *slot_off, const int64_t *slot_cap, const void *o1, const void *o2, const void *o3) {
     if (n < 0 || n > 0x7fffffff || !in_off || (n > 0 && (!slot_off || !slot_cap || !o1 || !o2 || !o3))) return -2;
     for (int64_t i = 0; i < n; ++i)
@@ -139,22 +134,17 @@ extern "C" int32_t mpn_gzip_inflate_device(int64_t n, const void *d_in, const in
     hipStream_t st = 0;
     DevBuf<int64_t> d_io, d_so, d_sc, d_len;
     DevBuf<int32_t> d_ord, d_mem, d_stat;
-    Events ev;
-    for (hipEvent_t &x : ev.e) MPN_HIP_CHECK(hipEventCreate(&x));
+    DevTimer tm;
     if (d_io.upload(in_off, (size_t)n + 1, st) || d_so.upload(slot_off, (size_t)n, st) || d_sc.upload(slot_cap, (size_t)n, st) ||
-        d_ord.upload(order.data(), (size_t)n, st) || d_len.alloc((size_t)n) || d_mem.alloc((size_t)n) || d_stat.alloc((size_t)n))
+        d_ord.upload(order.data(), (size_t)n, st) || d_len.alloc((size_t)n) || d_mem.alloc((size_t)n) || d_stat.alloc((size_t)n) || tm.start(st))
         return -1;
-    MPN_HIP_CHECK(hipEventRecord(ev.e[0], st));
     hipLaunchKernelGGL(gzip_inflate_kernel, dim3((unsigned)n), dim3(INF_THREADS), 0, st, (const uint8_t *)d_in, (const int64_t *)d_io.p,
                        (const int32_t *)d_ord.p, (uint8_t *)d_out, (const int64_t *)d_so.p, (const int64_t *)d_sc.p, d_len.p, d_mem.p, d_stat.p);
     MPN_HIP_CHECK(hipGetLastError());
-    MPN_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    if (tm.stop(st)) return -1;
     if (d_len.download(out_len, (size_t)n, st) || d_mem.download(n_members, (size_t)n, st) || d_stat.download(status, (size_t)n, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0;
-    MPN_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    tl_ingest_ms[0] = ms;
-    return 0;
+    return tm.elapsed_ms(&tl_ingest_ms[0]);
 }
 
 extern "C" int32_t mpn_gzip_inflate(int64_t n, const uint8_t *in, const int64_t *in_off, uint8_t *out, const int64_t *slot_off,

@@ -975,8 +975,6 @@ __global__ __launch_bounds__(256) void sp_out_off_kernel(const int32_t *__restri
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_out; j += (int64_t)gridDim.x * blockDim.x) out_off[j] = group_byte[u_group[j]] + rel[j];
 }
 
-extern thread_local int64_t tl_split_ns[2];   // read_split_kernels.hip
-
 }  // namespace mpn
 
 using namespace mpn;
@@ -1455,11 +1453,8 @@ extern "C" int mpn_reads_split_plan(int32_t n, const int32_t *len, int64_t m, co
     if (d_len.upload(len, (size_t)n, st) || d_read.upload(mem_read, (size_t)m, st) || d_group.upload(mem_group, (size_t)m, st) || a.alloc((size_t)m) || b.alloc((size_t)m) ||
         d_out_read.alloc((size_t)m) || u_group.alloc((size_t)m) || u_len.alloc((size_t)m) || d_n.alloc(1) || rel.alloc((size_t)m) || g_bytes.alloc((size_t)n_groups) ||
         g_bytes.zero(st) || d_first.alloc((size_t)n_groups + 1) || d_gbyte.alloc((size_t)n_groups + 1) || d_off.alloc((size_t)m)) return -1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    MPN_HIP_CHECK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("mpn_reads_split_plan: hipEventCreate failed"); return -1; }
-    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
-    (void)hipEventRecord(e0, st);
+    DevTimer tm;
+    if (tm.start(st)) return -1;
     hipLaunchKernelGGL(sp_fill_kernel, dim3(ba_grid(m)), dim3(256), 0, st, (const int32_t *)d_read.p, (const int32_t *)d_group.p, m, a.p);
     MPN_HIP_CHECK(hipGetLastError());
     // digits that no record has: all of hi, the bytes of the read above n - 1 and those of the group above n_groups - 1
@@ -1480,12 +1475,13 @@ extern "C" int mpn_reads_split_plan(int32_t n, const int32_t *len, int64_t m, co
     hipLaunchKernelGGL(sp_group_byte_kernel, dim3(1), dim3(1024), 0, st, (const int64_t *)g_bytes.p, n_groups, d_gbyte.p);
     hipLaunchKernelGGL(sp_out_off_kernel, dim3(ba_grid(k)), dim3(256), 0, st, (const int32_t *)u_group.p, (const int64_t *)rel.p, (const int64_t *)d_gbyte.p, k, d_off.p);
     MPN_HIP_CHECK(hipGetLastError());
-    (void)hipEventRecord(e1, st);
+    if (tm.stop(st)) return -1;
     if (d_out_read.download(out_read, (size_t)k, st) || d_off.download(out_off, (size_t)k, st) || d_first.download(group_first, (size_t)n_groups + 1, st) ||
         d_gbyte.download(group_byte, (size_t)n_groups + 1, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) tl_split_ns[0] = (int64_t)((double)ms * 1e6);
+    double ms = 0;
+    if (tm.elapsed_ms(&ms)) return -1;
+    tl_split_ns[0] = (int64_t)(ms * 1e6);
     *n_out = k;
     *out_bytes = group_byte[n_groups] + MPN_SPLIT_ALIGN;
     return 0;

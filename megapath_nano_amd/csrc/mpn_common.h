@@ -153,6 +153,37 @@ struct DevBuf {
     }
 };
 
+// ---- device time of a span of launches (two HIP events, destroyed on every way out) -----
+// start() and stop() record on the stream; elapsed_ms() wants the stream synchronised after stop().  Every step returns -1
+// with the error set when HIP refuses it, and the entry that times itself returns that.
+struct DevTimer {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    DevTimer() = default;
+    DevTimer(const DevTimer &) = delete;
+    DevTimer &operator=(const DevTimer &) = delete;
+    ~DevTimer() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    int start(hipStream_t st) {
+        for (hipEvent_t &x : e) if (!x) MPN_HIP_CHECK(hipEventCreate(&x));
+        MPN_HIP_CHECK(hipEventRecord(e[0], st));
+        return 0;
+    }
+    int stop(hipStream_t st) {
+        MPN_HIP_CHECK(hipEventRecord(e[1], st));
+        return 0;
+    }
+    int elapsed_ms(double *ms) {
+        float f = 0;
+        MPN_HIP_CHECK(hipEventElapsedTime(&f, e[0], e[1]));
+        *ms = f;
+        return 0;
+    }
+};
+// what the timed entries leave for their mpn_*_last_* readers: the device time of the calling thread's last call
+extern thread_local double tl_ingest_ms[2];   // inflate_kernels.hip: inflate, FASTA scan
+extern thread_local double tl_bam_ms[3];      // bam_in_kernels.hip: flatten, walk, decode
+extern thread_local double tl_bgzf_ms[2];     // bgzf_kernels.hip: deflate + scan, pack
+extern thread_local int64_t tl_split_ns[2];   // read_split_kernels.hip: plan, gather
+
 // ---- wave64 cross-lane primitives (DPP; no LDS traffic) ---------------------------------
 constexpr int NEG_INF = -(1 << 28);
 

@@ -6,9 +6,9 @@
 // A wave owns an aligned MPN_SPLIT_CHUNK of the OUTPUT, a lane 16 bytes of it, so every store is one full aligned 16-byte vector
 // store, every output byte is written exactly once (padding included, as zeros) and two neighbouring reads never share a store.
 // Work is bounded in bytes, not reads: a 2 Mbp read is spread over two thousand wave steps.  The reads that cover a chunk are found
-// by a wave-uniform search in out_off for the chunk's first and last byte; a lane then searches only between those two.
-#include "mpn_common.h"
-#include "../../include/mpn_reads.h"
+// by a wave-uniform search in out_off for the chunk's first and last byte; a lane then searches only between those two.  The
+// search, the unaligned 16-byte load and the launch shape are those of gather16.h, shared with the BAM kernels.
+#include "gather16.h"
 
 #include <vector>
 
@@ -16,38 +16,24 @@ namespace mpn {
 
 thread_local int64_t tl_split_ns[2] = {0, 0};
 
-constexpr int SG_THREADS = 256, SG_WAVES = SG_THREADS / 64;
-constexpr int SG_MAX_BLOCKS = 256 * 8;   // 8 resident blocks of 256 threads on each of 256 CUs; more output is taken in further rounds
-static_assert(MPN_SPLIT_CHUNK == 64 * 16, "a wave step is 64 lanes x 16 bytes");
-
-// last j in [lo, hi] with o_dst[j] <= q, or lo - 1 if there is none (o_dst ascending; equal entries are reads of length 0)
-__device__ __forceinline__ int64_t sg_last_le(const int64_t *__restrict__ o_dst, int64_t lo, int64_t hi, int64_t q) {
-    int64_t a = lo, b = hi + 1;   // answer in [a - 1, b - 1]
-    while (a < b) {
-        const int64_t mid = a + ((b - a) >> 1);
-        if (o_dst[mid] <= q) a = mid + 1; else b = mid;
-    }
-    return a - 1;
-}
-
 struct SgSide { const uint8_t *src; uint8_t *dst; };
 
 // o_dst[j], o_src[j], o_len[j]: where output read j starts in the output, where its bytes start in the source, its length.
 // n_sides: 1 (bases) or 2 (bases and qualities, same offsets).  src_pad: the sources' size rounded up to 4: no load goes beyond it.
 // The sources are aligned to 16 bytes.
-__global__ __launch_bounds__(SG_THREADS) void split_gather_kernel(SgSide s0, SgSide s1, int n_sides, const int64_t *__restrict__ o_dst,
-                                                                  const int64_t *__restrict__ o_src, const int32_t *__restrict__ o_len,
-                                                                  int64_t n_out, int64_t out_bytes, int64_t src_pad) {
+__global__ __launch_bounds__(G16_THREADS) void split_gather_kernel(SgSide s0, SgSide s1, int n_sides, const int64_t *__restrict__ o_dst,
+                                                                   const int64_t *__restrict__ o_src, const int32_t *__restrict__ o_len,
+                                                                   int64_t n_out, int64_t out_bytes, int64_t src_pad) {
     const int lane = threadIdx.x & 63;
     const int64_t n_chunks = (out_bytes + MPN_SPLIT_CHUNK - 1) / MPN_SPLIT_CHUNK;
-    for (int64_t c = (int64_t)blockIdx.x * SG_WAVES + (threadIdx.x >> 6); c < n_chunks; c += (int64_t)gridDim.x * SG_WAVES) {
+    for (int64_t c = (int64_t)blockIdx.x * G16_WAVES + (threadIdx.x >> 6); c < n_chunks; c += (int64_t)gridDim.x * G16_WAVES) {
         const int64_t c0 = c * MPN_SPLIT_CHUNK;
         const int64_t c1 = (c0 + MPN_SPLIT_CHUNK < out_bytes ? c0 + MPN_SPLIT_CHUNK : out_bytes) - 1;   // the chunk's last byte
         // wave-uniform: the reads that can cover bytes of [c0, c1]
-        const int64_t jlo = sg_last_le(o_dst, 0, n_out - 1, c0), jhi = sg_last_le(o_dst, jlo < 0 ? 0 : jlo, n_out - 1, c1);
+        const int64_t jlo = last_le(o_dst, 0, n_out - 1, c0), jhi = last_le(o_dst, jlo < 0 ? 0 : jlo, n_out - 1, c1);
         const int64_t p = c0 + lane * 16;
         if (p >= out_bytes) continue;   // (out_bytes is a multiple of 16: a lane's 16 bytes are inside or outside as a whole)
-        const int64_t j = sg_last_le(o_dst, jlo < 0 ? 0 : jlo, jhi, p);
+        const int64_t j = last_le(o_dst, jlo < 0 ? 0 : jlo, jhi, p);
         int64_t d = 0, l = 0, s = 0;
         if (j >= 0) { d = o_dst[j]; l = o_len[j]; s = o_src[j] + (p - d); }
         const bool whole = j >= 0 && p + 16 <= d + l;   // all 16 bytes inside read j
@@ -55,23 +41,10 @@ __global__ __launch_bounds__(SG_THREADS) void split_gather_kernel(SgSide s0, SgS
         for (int t = 0; t < n_sides; ++t) {
             const SgSide sd = t ? s1 : s0;
             uint32_t v[4] = {0, 0, 0, 0};
+            // (the second vector must end inside the source: host sources are uploaded with padding to a multiple of 4 only)
             if (whole && (sh16 == 0 || (s & ~(int64_t)15) + 32 <= src_pad)) {
-                // the one or two aligned 16-byte vectors of the source that hold the lane's bytes, shifted into place; the second is
-                // touched only when its bytes are needed and it ends inside the source
-                const uint4 *a = (const uint4 *)(sd.src + (s & ~(int64_t)15));
-                const uint4 lo4 = a[0], hi4 = sh16 ? a[1] : make_uint4(0, 0, 0, 0);
-                uint32_t x0, x1, x2, x3, x4;
-                switch (sh16 >> 2) {   // (the same in every lane that copies from the same read)
-                    case 0: x0 = lo4.x; x1 = lo4.y; x2 = lo4.z; x3 = lo4.w; x4 = hi4.x; break;
-                    case 1: x0 = lo4.y; x1 = lo4.z; x2 = lo4.w; x3 = hi4.x; x4 = hi4.y; break;
-                    case 2: x0 = lo4.z; x1 = lo4.w; x2 = hi4.x; x3 = hi4.y; x4 = hi4.z; break;
-                    default: x0 = lo4.w; x1 = hi4.x; x2 = hi4.y; x3 = hi4.z; x4 = hi4.w; break;
-                }
-                const uint32_t sh = sh16 & 3;
-                v[0] = __builtin_amdgcn_alignbyte(x1, x0, sh);
-                v[1] = __builtin_amdgcn_alignbyte(x2, x1, sh);
-                v[2] = __builtin_amdgcn_alignbyte(x3, x2, sh);
-                v[3] = __builtin_amdgcn_alignbyte(x4, x3, sh);
+                const uint4 x = load16_at((const uint4 *)(sd.src + (s & ~(int64_t)15)), sh16);
+                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
             } else {
                 // a slot that holds the end of a read, the start of one, short reads or padding, or whose second vector would pass
                 // the end of the source: byte by byte
@@ -79,7 +52,7 @@ __global__ __launch_bounds__(SG_THREADS) void split_gather_kernel(SgSide s0, SgS
 #pragma unroll 1
                 for (int b = 0; b < 16; ++b) {
                     const int64_t q = p + b;
-                    jj = sg_last_le(o_dst, jj < 0 ? 0 : jj, jhi, q);
+                    jj = last_le(o_dst, jj < 0 ? 0 : jj, jhi, q);
                     uint32_t byte = 0;
                     if (jj >= 0) {
                         const int64_t dd = o_dst[jj];
@@ -156,23 +129,17 @@ extern "C" int mpn_reads_split_gather(int32_t n, const void *seqs, const void *q
         DevBuf<int64_t> d_dst, d_src;
         DevBuf<int32_t> d_len;
         if (d_dst.upload(out_off, (size_t)n_out, st) || d_src.upload(o_src.data(), (size_t)n_out, st) || d_len.upload(o_len.data(), (size_t)n_out, st)) return -1;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        MPN_HIP_CHECK(hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("mpn_reads_split_gather: hipEventCreate failed"); return -1; }
-        const int64_t n_chunks = (out_bytes + MPN_SPLIT_CHUNK - 1) / MPN_SPLIT_CHUNK;
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_chunks + SG_WAVES - 1) / SG_WAVES, SG_MAX_BLOCKS));
-        (void)hipEventRecord(e0, st);
-        hipLaunchKernelGGL(split_gather_kernel, dim3(grid), dim3(SG_THREADS), 0, st, SgSide{d_s, (uint8_t *)d_out_seqs}, SgSide{d_q, (uint8_t *)d_out_quals},
-                           with_q ? 2 : 1, (const int64_t *)d_dst.p, (const int64_t *)d_src.p, (const int32_t *)d_len.p, n_out, out_bytes,
-                           (src_bytes + 3) & ~(int64_t)3);
-        const hipError_t le = hipGetLastError();
-        (void)hipEventRecord(e1, st);
-        const hipError_t se = hipStreamSynchronize(st);   // the uploaded sources and the plan arrays must outlive the kernel
-        float ms = 0.f;
-        if (le == hipSuccess && se == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) tl_split_ns[1] = (int64_t)((double)ms * 1e6);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (le != hipSuccess || se != hipSuccess) { set_error("mpn_reads_split_gather: kernel failed: %s", hipGetErrorString(le != hipSuccess ? le : se)); return -1; }
+        DevTimer tm;
+        if (tm.start(st)) return -1;
+        hipLaunchKernelGGL(split_gather_kernel, dim3(grid_for(out_bytes)), dim3(G16_THREADS), 0, st, SgSide{d_s, (uint8_t *)d_out_seqs},
+                           SgSide{d_q, (uint8_t *)d_out_quals}, with_q ? 2 : 1, (const int64_t *)d_dst.p, (const int64_t *)d_src.p,
+                           (const int32_t *)d_len.p, n_out, out_bytes, (src_bytes + 3) & ~(int64_t)3);
+        MPN_HIP_CHECK(hipGetLastError());
+        if (tm.stop(st)) return -1;
+        MPN_HIP_CHECK(hipStreamSynchronize(st));   // the uploaded sources and the plan arrays must outlive the kernel
+        double ms = 0;
+        if (tm.elapsed_ms(&ms)) return -1;
+        tl_split_ns[1] = (int64_t)(ms * 1e6);
     }
     if (h_out_seqs) MPN_HIP_CHECK(hipMemcpyAsync(h_out_seqs, d_out_seqs, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
     if (h_out_quals) MPN_HIP_CHECK(hipMemcpyAsync(h_out_quals, d_out_quals, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
