@@ -17,6 +17,13 @@
  *   mpn_bam_decode     the rows of a batch of reads -> ASCII bases, Phred+33 qualities and names, reads that are stored as their
  *                      reverse complement restored, in the layout of mapper.PackedReads.from_arrays
  *
+ * and of FASTQ files as read input (MPN_READ_INGEST=device; csrc/fastq_scan_kernels.hip -- csrc/fastq_kernels.hip is the quality
+ * filter of mpn_fastq.h).  The text comes from the file as it is, from zlib on the host, or from mpn_gzip_inflate_device and
+ * mpn_bam_flatten when the file is BGZF:
+ *
+ *   mpn_fastq_scan     the text -> a table with a row per plain four-line record, for the longest prefix of such records
+ *   mpn_fastq_gather   the rows of a batch of reads -> bases, qualities and names in the layout of mpn_bam_decode (gather16.h)
+ *
  * Grouping of files, slot sizing, the fallbacks to the host path and the cutting into index parts are in
  * megapath_nano_amd/ingest.py.  Calling rules as for mpn_bgzf_compress: a call returns when its results are on the host, the
  * default stream is used, -1 = device error (mpn_last_error()), -2 = bad arguments.
@@ -44,7 +51,8 @@ enum {
     MPN_BAM_TRUNCATED = 10,       /* mpn_bam_walk only, as are the next three: the header or a record passes the end of the last text */
     MPN_BAM_BAD_MAGIC = 11,       /* the text does not start with BAM\1 */
     MPN_BAM_BAD_HEADER = 12,      /* a negative l_text or n_ref, a reference name of less than one byte */
-    MPN_BAM_BAD_RECORD = 13       /* block_size < 32, l_read_name < 1, l_seq < 0, or name, CIGAR, bases and qualities longer than block_size */
+    MPN_BAM_BAD_RECORD = 13,      /* block_size < 32, l_read_name < 1, l_seq < 0, or name, CIGAR, bases and qualities longer than block_size */
+    MPN_FASTQ_UNSUPPORTED = 14    /* mpn_fastq_scan only: the record at *consumed is not a plain four-line record (or, with final, is cut short) */
 };
 
 /* n streams: stream i is in[in_off[i] .. in_off[i + 1]), a whole file: zero or more gzip members back to back, zero bytes
@@ -124,6 +132,48 @@ int32_t mpn_bam_decode(const void *d_text, int64_t text_len, int64_t n, const mp
 /* Device time of the calling thread's last mpn_bam_flatten, mpn_bam_walk and mpn_bam_decode, as mpn_ingest_last_device_ms gives it
  * for the first two stages.  Any pointer may be NULL. */
 void mpn_bam_last_device_ms(double *flatten_ms, double *walk_ms, double *decode_ms);
+
+/* ---- FASTQ as read input -------------------------------------------------------------------------------------------------------
+ * A row of the record table: where the bases, the qualities (len bytes each) and the name (name_len bytes) lie in the text. */
+typedef struct {
+    int64_t seq_off, qual_off, name_off;
+    int32_t len, name_len;
+} mpn_fastq_row;
+
+/* The scan works on tiles of this many bytes (lines may be of any length; the tests place their edge cases by it). */
+#define MPN_FASTQ_TILE 4096
+int32_t mpn_fastq_tile(void);
+
+/* d_text[0 .. text_len) (DEVICE pointer) starts at a record start.  The kind of a line is its index modulo 4, counted in line feeds
+ * from the start of the text.  A record is PLAIN when
+ *   line 0  starts with '@' (the name is the first word behind it, with the separators of Python's bytes.split());
+ *   line 1  starts with none of '@', '>', '+' and holds no blank, TAB, VT or FF (it may be empty);
+ *   line 2  starts with '+' (the rest of it is ignored);
+ *   line 3  has exactly as many bytes as line 1 (it may start with '@', '+' or '>');
+ *   a CR in lines 0, 1 and 3 stands directly before the LF (and is dropped with it);
+ *   the read is no longer than 2^31 - 1 bases.
+ * The scan takes the longest prefix of plain records: rows[0 .. *n_records) (host, rec_cap entries), *consumed = the offset behind
+ * the last line end of that prefix, and *status is
+ *   MPN_INFLATE_OK          the text ended at *consumed -- or, without final, inside the record that starts at *consumed: the caller
+ *                           carries text[*consumed ..) to the front of the next text.  With final, a last line without LF is whole.
+ *   MPN_FASTQ_UNSUPPORTED   the record at *consumed is not plain; with final also: it is cut short.  fastx.iter_fastx continues there.
+ * Counting call (rows = NULL, rec_cap = 0): n_records, consumed and status only.  Returns 0, or -3 if rec_cap is too small
+ * (*n_records, *consumed and *status are complete, rows is not).  Malformed input ends in a status and never in an access outside
+ * the text.  Device memory: 8 bytes per line and 32 per record next to the text. */
+int32_t mpn_fastq_scan(const void *d_text, int64_t text_len, int32_t final, int64_t rec_cap, mpn_fastq_row *rows, int64_t *n_records,
+                       int64_t *consumed, int32_t *status);
+
+/* The reads of n rows (host; of mpn_fastq_scan on this d_text, any subset in any order): read r's bases go to
+ * d_seq[out_off[r] .. + len) (DEVICE; out_off: host, the exclusive sum of len) and, with d_qual (DEVICE, or NULL), its qualities to the
+ * same place of d_qual, both unchanged.  Layout and return codes as mpn_bam_decode: both buffers are 16-byte aligned and hold
+ * total + 16 bytes rounded up to a multiple of 16, what follows the last base is zeroed, the names go one behind the other to
+ * name_pool (host); -2 for arguments or rows that do not lie inside the text (nothing outside it is read), -3 if name_pool_cap is
+ * too small. */
+int32_t mpn_fastq_gather(const void *d_text, int64_t text_len, int64_t n, const mpn_fastq_row *rows, const int64_t *out_off, void *d_seq,
+                         void *d_qual, char *name_pool, int64_t name_pool_cap);
+
+/* Device time of the calling thread's last mpn_fastq_scan and mpn_fastq_gather in milliseconds.  Either pointer may be NULL. */
+void mpn_fastq_last_device_ms(double *scan_ms, double *gather_ms);
 
 #ifdef __cplusplus
 }

@@ -221,7 +221,12 @@ def _is_saved_index(paths):
 def iter_read_batches(query_paths, batch_bases=200_000_000, device=None):
     """PackedReads of at most batch_bases each, qualities included, in file order.  A BAM file among the paths is inflated and decoded
     on the GPU (ingest.iter_bam_read_batches); its batches are its own: the FASTA / FASTQ reads collected before it are flushed
-    first, and its last batch is not filled up from the file behind it."""
+    first, and its last batch is not filled up from the file behind it.  With MPN_READ_INGEST=device the FASTQ files are scanned on
+    the GPU as well (_iter_read_batches_device)."""
+    from . import ingest
+    if ingest.read_ingest_mode() == 'device':
+        yield from _iter_read_batches_device(query_paths, batch_bases, device)
+        return
     names, seqs, quals, acc = [], [], [], 0
 
     def flush():
@@ -250,6 +255,32 @@ def iter_read_batches(query_paths, batch_bases=200_000_000, device=None):
             stream.close()
     if names:
         yield flush()
+
+
+def _iter_read_batches_device(query_paths, batch_bases, device):
+    """iter_read_batches under MPN_READ_INGEST=device.  Every query is opened once and told by its first bytes: a file whose text
+    starts with '@' goes to ingest.iter_fastq_read_batches -- plain, gzip or BGZF, regular file or FIFO; the batches are cut by the
+    rule of the host loop and run on over consecutive such files.  Before a BAM, or a file the host reads from its first byte (FASTA,
+    an empty file, a stream whose first bytes do not tell), the pending batch is flushed."""
+    from . import ingest
+    batcher = ingest.ReadBatcher(batch_bases, device or 'cuda')
+    for path in query_paths:
+        kind, stream, first = fastx.open_query(path)
+        try:
+            if kind == 'index':
+                raise ValueError(f'{path}: a saved index is not a read file')
+            if kind == 'bam':
+                yield from batcher.flush()
+                yield from ingest.iter_bam_read_batches(stream, batch_bases, device=device or 'cuda')
+            elif first == b'@':
+                yield from ingest.iter_fastq_read_batches(stream, batch_bases, device=device or 'cuda', form=kind, batcher=batcher)
+            else:
+                yield from batcher.flush()
+                for name, seq, qual in fastx.iter_fastx(stream if kind == 'plain' else fastx.gzip_text(stream)):
+                    yield from batcher.add_host(name, seq, qual)
+        finally:
+            stream.close()
+    yield from batcher.flush()
 
 
 # ---- the engine shared by Align() and bin/mpn-aligner ----------------------------------------------------------------------

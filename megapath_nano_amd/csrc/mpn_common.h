@@ -181,6 +181,7 @@ struct DevTimer {
 // what the timed entries leave for their mpn_*_last_* readers: the device time of the calling thread's last call
 extern thread_local double tl_ingest_ms[2];   // inflate_kernels.hip: inflate, FASTA scan
 extern thread_local double tl_bam_ms[3];      // bam_in_kernels.hip: flatten, walk, decode
+extern thread_local double tl_fastq_ms[2];    // fastq_scan_kernels.hip: scan, gather
 extern thread_local double tl_bgzf_ms[2];     // bgzf_kernels.hip: deflate + scan, pack
 extern thread_local int64_t tl_split_ns[2];   // read_split_kernels.hip: plan, gather
 

@@ -25,37 +25,73 @@ def is_fifo(path):
         return False
 
 
-def _is_bam(peeked):
-    """peeked: the first bytes of a gzip stream.  True for a BGZF block (extra subfield BC) whose text starts with BAM\\1; the first
-    bytes of the block are enough to inflate those four."""
+def _bgzf_data_start(peeked):
+    """peeked: the first bytes of a gzip stream.  -> where the deflate data of its first member starts if that member is a BGZF block
+    (extra subfield BC), else 0."""
     if len(peeked) < 18 or peeked[:4] != b'\x1f\x8b\x08\x04':
-        return False
+        return 0
     xlen, p, found = int.from_bytes(peeked[10:12], 'little'), 12, False
     while p + 4 <= min(12 + xlen, len(peeked)):
         found |= peeked[p:p + 2] == b'BC'
         p += 4 + int.from_bytes(peeked[p + 2:p + 4], 'little')
-    if not found:
+    return 12 + xlen if found else 0
+
+
+def _is_bam(peeked):
+    """peeked: the first bytes of a gzip stream.  True for a BGZF block (extra subfield BC) whose text starts with BAM\\1; the first
+    bytes of the block are enough to inflate those four."""
+    start = _bgzf_data_start(peeked)
+    if not start:
         return False
     try:
-        return zlib.decompressobj(-15).decompress(peeked[12 + xlen:], 4) == b'BAM\x01'
+        return zlib.decompressobj(-15).decompress(peeked[start:], 4) == b'BAM\x01'
     except zlib.error:
         return False
+
+
+def _open_raw(path):
+    """-> (the file's own bytes as a buffered stream, opened once; its first bytes, peeked: nothing is consumed)"""
+    raw = io.BufferedReader(open(path, 'rb', buffering=0), buffer_size=1 << 20)
+    return raw, raw.peek(8)
+
+
+def gzip_text(raw):
+    """the decompressed bytes of a gzip stream (concatenated members included) from where `raw` stands"""
+    return io.BufferedReader(gzip.GzipFile(fileobj=raw, mode='rb'), buffer_size=1 << 20)
 
 
 def open_once(path):
     """-> (kind, binary stream); kind is 'index' (a saved mpn index: the stream is positioned at its first byte), 'bam' (the stream
     is positioned at the first byte of the file, compressed: ingest.iter_bam_read_batches takes it; told by the BAM magic at the
     start of the first BGZF block's text), 'gzip' or 'plain' (both: a stream of decompressed bytes).  The path is opened exactly once."""
-    raw = io.BufferedReader(open(path, 'rb', buffering=0), buffer_size=1 << 20)
-    peeked = raw.peek(8)
+    raw, peeked = _open_raw(path)
     head = peeked[:8]
     if head == INDEX_MAGIC:
         return 'index', raw
     if head[:2] == b'\x1f\x8b':
         if _is_bam(peeked):
             return 'bam', raw
-        return 'gzip', io.BufferedReader(gzip.GzipFile(fileobj=raw, mode='rb'), buffer_size=1 << 20)
+        return 'gzip', gzip_text(raw)
     return 'plain', raw
+
+
+def open_query(path):
+    """What the read input on the device (MPN_READ_INGEST=device, ingest.iter_fastq_read_batches) wants to know of a query file:
+    -> (kind, stream, first).  kind is 'index', 'bam', 'bgzf' (a gzip stream whose first member is a BGZF block, no BAM), 'gzip' or
+    'plain'; the stream is ALWAYS the file's own bytes, positioned at its first byte (gzip_text decompresses it); first is the first
+    byte of the text, b'' for an empty file or where the bytes at hand do not say.  The path is opened exactly once."""
+    raw, peeked = _open_raw(path)
+    if peeked[:8] == INDEX_MAGIC:
+        return 'index', raw, b''
+    if peeked[:2] != b'\x1f\x8b':
+        return 'plain', raw, peeked[:1]
+    if _is_bam(peeked):
+        return 'bam', raw, b''
+    try:
+        first = zlib.decompressobj(31).decompress(peeked, 1)
+    except zlib.error:
+        first = b''
+    return ('bgzf' if _bgzf_data_start(peeked) else 'gzip'), raw, first
 
 
 def _no_bam(kind, path, what):

@@ -19,6 +19,15 @@ of this module):
       mpn_bam_decode --> mapper.PackedReads with its device copy
 
 There is no host path for them: a block whose status is not OK, or a text that is no BAM, raises ValueError.
+
+FASTQ files as READ input (MPN_READ_INGEST=device, iter_fastq_read_batches): the text comes from the file as it is, from zlib on the
+host for an ordinary gzip stream, or through the front half of the BAM path (_BgzfTexts) for BGZF:
+
+    text in HBM, behind the carry of the text before --mpn_fastq_scan--> a row per plain four-line record
+      --(cut batches like aligner.iter_read_batches: ReadBatcher)--> mpn_fastq_gather --> mapper.PackedReads with its device copy
+
+At the first record that is not plain the rest of the file -- the tail of the text and what the stream still holds -- goes through
+fastx.iter_fastx, and its records keep filling the same batches.
 """
 import ctypes as ct
 import gzip
@@ -34,6 +43,7 @@ OK, OVERFLOW, UNSUPPORTED = 0, 8, 9
 STATUS_NAMES = ('OK', 'TRUNCATED', 'BAD_MAGIC', 'BAD_BLOCK', 'BAD_CODE', 'BAD_DISTANCE', 'BAD_CRC', 'BAD_SIZE', 'OVERFLOW', 'UNSUPPORTED',
                 'BAM_TRUNCATED', 'BAM_BAD_MAGIC', 'BAM_BAD_HEADER', 'BAM_BAD_RECORD')
 BAM_TRUNCATED, BAM_BAD_MAGIC, BAM_BAD_HEADER, BAM_BAD_RECORD = 10, 11, 12, 13
+FASTQ_UNSUPPORTED = 14      # mpn_fastq_scan only; never reported to a user: the host reads what the scan does not take
 
 # One launch must not run long on a shared device.  A wave inflates a single stream at 1.85 MB/s of compressed input (6.0 MB/s of
 # text; profiles/r15_ingest/README.md), so the longest stream one launch may hold takes about a second; larger ones are inflated by
@@ -52,6 +62,14 @@ def ingest_mode():
     how = os.environ.get('MPN_TARGET_INGEST', 'host')
     if how not in ('host', 'device'):
         raise ValueError(f'MPN_TARGET_INGEST={how}: expected host or device')
+    return how
+
+
+def read_ingest_mode():
+    """MPN_READ_INGEST: unset or `host` = FASTQ reads parsed by fastx on the host, `device` = iter_fastq_read_batches."""
+    how = os.environ.get('MPN_READ_INGEST', 'host')
+    if how not in ('host', 'device'):
+        raise ValueError(f'MPN_READ_INGEST={how}: expected host or device')
     return how
 
 
@@ -86,6 +104,14 @@ def _lib():
         lib.mpn_bam_decode.restype = ct.c_int32
         lib.mpn_bam_last_device_ms.argtypes = [ct.POINTER(ct.c_double)] * 3
         lib.mpn_bam_last_device_ms.restype = None
+        lib.mpn_fastq_tile.argtypes = []
+        lib.mpn_fastq_tile.restype = ct.c_int32
+        lib.mpn_fastq_scan.argtypes = [P, I64, ct.c_int32, I64, P, P, P, P]
+        lib.mpn_fastq_scan.restype = ct.c_int32
+        lib.mpn_fastq_gather.argtypes = [P, I64, I64, P, P, P, P, P, I64]
+        lib.mpn_fastq_gather.restype = ct.c_int32
+        lib.mpn_fastq_last_device_ms.argtypes = [ct.POINTER(ct.c_double)] * 2
+        lib.mpn_fastq_last_device_ms.restype = None
         _bound = True
     return lib
 
@@ -606,24 +632,17 @@ def bam_decode(text, text_len, rows, with_qual):
     return seq, qual, names
 
 
-def _bam_batch(pieces, device, timings):
-    """pieces: [(text, text_len, kept rows)] in file order, the reads of one batch -> mapper.PackedReads with its device copy"""
+def _join_batch(parts, names, lens, with_qual, device, timings, t0, stage):
+    """parts: [(bases tensor, qualities tensor or None, bytes of it that count)] in read order, the pieces of one batch as
+    mpn_bam_decode / mpn_fastq_gather lay them out -> mapper.PackedReads with its device copy.  t0: when the batch was begun (the
+    time up to the download is booked on `stage`)."""
     import time
     import torch
     from . import mapper
-    t0 = time.perf_counter()
-    with_qual = any(bool(rows['has_qual'].any()) for _, _, rows in pieces)
-    parts, names = [], []
-    for text, text_len, rows in pieces:
-        seq, qual, nm = bam_decode(text, text_len, rows, with_qual)
-        _tick(timings, 'decode_device_ms', last_bam_device_ms()[2])
-        parts.append((seq, qual, int(rows['l_seq'].astype(np.int64).sum())))
-        names += nm
-    lens = np.concatenate([rows['l_seq'] for _, _, rows in pieces]).astype(np.int32)
     total = int(lens.astype(np.int64).sum())
     if len(parts) == 1:
         seq, qual = parts[0][0][:total + 16], (parts[0][1][:total + 16] if with_qual else None)
-    else:     # a batch whose records lie in the texts of several groups: its pieces are joined, device to device
+    else:     # a batch whose records lie in several texts: its pieces are joined, device to device
         pad = torch.zeros(16, dtype=torch.uint8, device=device)
         seq = torch.cat([s[:k] for s, _, k in parts] + [pad])
         qual = torch.cat([q[:k] for _, q, k in parts] + [pad]) if with_qual else None
@@ -634,9 +653,69 @@ def _bam_batch(pieces, device, timings):
     qbuf = qual.cpu().numpy() if with_qual else None
     dev = (seq, torch.from_numpy(off).to(device), torch.from_numpy(lens).to(device))
     torch.cuda.synchronize()
-    _tick(timings, 'decode', t1 - t0)
+    _tick(timings, stage, t1 - t0)
     _tick(timings, 'd2h', time.perf_counter() - t1)
     return mapper.PackedReads.from_arrays(names, buf, off, lens, dev=dev, qbuf=qbuf)
+
+
+def _bam_batch(pieces, device, timings):
+    """pieces: [(text, text_len, kept rows)] in file order, the reads of one batch -> mapper.PackedReads with its device copy"""
+    import time
+    t0 = time.perf_counter()
+    with_qual = any(bool(rows['has_qual'].any()) for _, _, rows in pieces)
+    parts, names = [], []
+    for text, text_len, rows in pieces:
+        seq, qual, nm = bam_decode(text, text_len, rows, with_qual)
+        _tick(timings, 'decode_device_ms', last_bam_device_ms()[2])
+        parts.append((seq, qual, int(rows['l_seq'].astype(np.int64).sum())))
+        names += nm
+    lens = np.concatenate([rows['l_seq'] for _, _, rows in pieces]).astype(np.int32)
+    return _join_batch(parts, names, lens, with_qual, device, timings, t0, 'decode')
+
+
+class _BgzfTexts:
+    """The text of a BGZF stream in HBM, group by group: framing (_BgzfGroups), upload, mpn_gzip_inflate_device with a wave per block,
+    mpn_bam_flatten behind the carry.  What BAM and BGZF-compressed FASTQ share."""
+
+    def __init__(self, stream, device, timings=None):
+        self.groups, self.device, self.timings = _BgzfGroups(stream, batch_bytes()), device, timings
+
+    def next_text(self, carry):
+        """carry: the unconsumed tail of the text before (a uint8 device tensor, any view) or None
+        -> (text tensor, padded to 16; its length; whether it is the last of the stream)"""
+        import time
+        import torch
+        lib, device, timings = _lib(), self.device, self.timings
+        t0 = time.perf_counter()
+        staged, in_off, isize, where, first = self.groups.next_group()
+        final = self.groups.eof
+        t1 = time.perf_counter()
+        n = len(isize)
+        d_in = staged.to(device, non_blocking=True)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        so = np.zeros(n + 1, dtype=np.int64)
+        so[1:] = np.cumsum((isize + 15) & ~15)
+        slots = torch.empty(max(int(so[-1]), 16), dtype=torch.uint8, device=device)
+        length, members, status = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        if n:
+            rc = lib.mpn_gzip_inflate_device(n, d_in.data_ptr(), in_off.ctypes.data, slots.data_ptr(), so.ctypes.data, isize.ctypes.data,
+                                             length.ctypes.data, members.ctypes.data, status.ctypes.data)
+            if rc:
+                raise _ffi.MpnError(f'mpn_gzip_inflate_device rc={rc}: {_ffi.hint(_ffi.last_error())}')
+            _tick(timings, 'inflate_device_ms', last_device_ms()[0])
+            bad = np.flatnonzero((status != OK) | (length != isize) | (members != 1))
+            if len(bad):
+                b = int(bad[0])
+                what = STATUS_NAMES[status[b]] if status[b] != OK else f'{members[b]} gzip members of {length[b]} bytes, ISIZE {isize[b]}'
+                raise ValueError(f'BGZF block {first + b} at file offset {where[b]}: {what}')
+        t3 = time.perf_counter()
+        text, text_len = bam_flatten(slots, so[:n], isize, carry, device)
+        _tick(timings, 'flatten_device_ms', last_bam_device_ms()[0])
+        t4 = time.perf_counter()
+        for key, dt in (('read', t1 - t0), ('h2d', t2 - t1), ('inflate', t3 - t2), ('flatten', t4 - t3)):
+            _tick(timings, key, dt)
+        return text, text_len, final
 
 
 def iter_bam_read_batches(stream_or_path, batch_bases=200_000_000, device='cuda', walk_records=None, timings=None):
@@ -644,45 +723,18 @@ def iter_bam_read_batches(stream_or_path, batch_bases=200_000_000, device='cuda'
     records), resident on the device, with the semantics of `samtools fastq`.  stream_or_path: a path, or
     the binary stream fastx.open_once returned for kind 'bam' (read to its end, not closed)."""
     import time
-    import torch
-    lib = _lib()
     device = device or 'cuda'
     own = isinstance(stream_or_path, (str, bytes, os.PathLike))
     stream = io.BufferedReader(open(stream_or_path, 'rb', buffering=0), buffer_size=1 << 20) if own else stream_or_path
     walk_records = max(1, bam_walk_records() if walk_records is None else int(walk_records))
     try:
-        groups = _BgzfGroups(stream, batch_bytes())
+        texts = _BgzfTexts(stream, device, timings)
         carry, at_header, text_base = None, True, 0       # text_base: the offset of text[0] in the whole inflated stream
         pieces, acc, count = [], 0, 0
         while True:
-            t0 = time.perf_counter()
-            staged, in_off, isize, where, first = groups.next_group()
-            final = groups.eof
-            t1 = time.perf_counter()
-            n = len(isize)
-            d_in = staged.to(device, non_blocking=True)
-            torch.cuda.synchronize()
-            t2 = time.perf_counter()
-            so = np.zeros(n + 1, dtype=np.int64)
-            so[1:] = np.cumsum((isize + 15) & ~15)
-            slots = torch.empty(max(int(so[-1]), 16), dtype=torch.uint8, device=device)
-            length, members, status = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
-            if n:
-                rc = lib.mpn_gzip_inflate_device(n, d_in.data_ptr(), in_off.ctypes.data, slots.data_ptr(), so.ctypes.data, isize.ctypes.data,
-                                                 length.ctypes.data, members.ctypes.data, status.ctypes.data)
-                if rc:
-                    raise _ffi.MpnError(f'mpn_gzip_inflate_device rc={rc}: {_ffi.hint(_ffi.last_error())}')
-                _tick(timings, 'inflate_device_ms', last_device_ms()[0])
-                bad = np.flatnonzero((status != OK) | (length != isize) | (members != 1))
-                if len(bad):
-                    b = int(bad[0])
-                    what = STATUS_NAMES[status[b]] if status[b] != OK else f'{members[b]} gzip members of {length[b]} bytes, ISIZE {isize[b]}'
-                    raise ValueError(f'BGZF block {first + b} at file offset {where[b]}: {what}')
-            t3 = time.perf_counter()
-            text, text_len = bam_flatten(slots, so[:n], isize, carry, device)
-            _tick(timings, 'flatten_device_ms', last_bam_device_ms()[0])
+            text, text_len, final = texts.next_text(carry)
             t4 = time.perf_counter()
-            del d_in, slots, carry
+            del carry
             start, got = 0, []
             while True:
                 rows, nxt, st = bam_walk(text, text_len, start, at_header, final, walk_records)
@@ -699,9 +751,7 @@ def iter_bam_read_batches(stream_or_path, batch_bases=200_000_000, device='cuda'
             rows = np.concatenate(got)
             _tick(timings, 'records', len(rows))
             rows = rows[(rows['flag'] & BAM_SKIP) == 0]
-            t5 = time.perf_counter()
-            for key, dt in (('read', t1 - t0), ('h2d', t2 - t1), ('inflate', t3 - t2), ('flatten', t4 - t3), ('walk', t5 - t4)):
-                _tick(timings, key, dt)
+            _tick(timings, 'walk', time.perf_counter() - t4)
             lo = 0
             for i, l in enumerate(rows['l_seq'].tolist()):
                 if count and acc + l > batch_bases:
@@ -733,3 +783,230 @@ def read_bam(stream_or_path, device='cuda'):
             a, z = int(b.off[i]), int(b.off[i]) + int(b.lens[i])
             out.append((b.names[i], b.buf[a:z].tobytes(), None if b.qbuf is None else b.qbuf[a:z].tobytes()))
     return out
+
+
+# ---- FASTQ as read input ------------------------------------------------------------------------------------------------------------
+FASTQ_ROW = np.dtype([('seq_off', '<i8'), ('qual_off', '<i8'), ('name_off', '<i8'), ('len', '<i4'), ('name_len', '<i4')])    # mpn_fastq_row
+# Host-to-device pieces of a plain or host-inflated text: one pinned buffer of this size is filled and uploaded in turns.
+FASTQ_STAGING = 16 << 20
+
+
+def fastq_tile():
+    """MPN_FASTQ_TILE of the library that is loaded"""
+    return int(_lib().mpn_fastq_tile())
+
+
+def last_fastq_device_ms():
+    """-> (scan ms, gather ms) of the calling thread's last native calls"""
+    a, b = ct.c_double(0), ct.c_double(0)
+    _lib().mpn_fastq_last_device_ms(ct.byref(a), ct.byref(b))
+    return a.value, b.value
+
+
+def fastq_scan(text, text_len, final, rec_cap=None):
+    """mpn_fastq_scan on text[:text_len] (a uint8 device tensor) -> (rows as a FASTQ_ROW array, consumed, status, device ms).  rec_cap: the
+    size of the table of the first attempt (a guess from the text's length by default); a table that is too small is made
+    again with the count the call reported."""
+    lib = _lib()
+    text_len = int(text_len)
+    if text_len > text.numel():
+        raise ValueError('fastq_scan: the text is shorter than text_len')
+    cap = text_len // 64 + 1024 if rec_cap is None else int(rec_cap)
+    n, consumed, status = ct.c_int64(0), ct.c_int64(0), ct.c_int32(0)
+    ms = 0.0
+    while True:
+        rows = np.empty(cap, dtype=FASTQ_ROW)
+        rc = lib.mpn_fastq_scan(text.data_ptr(), text_len, int(bool(final)), cap, _ptr(rows), ct.byref(n), ct.byref(consumed), ct.byref(status))
+        ms += last_fastq_device_ms()[0]
+        if rc == -3 and n.value > cap:
+            cap = n.value
+            continue
+        if rc:
+            raise _ffi.MpnError(f'mpn_fastq_scan rc={rc}: {_ffi.hint(_ffi.last_error())}')
+        return rows[:n.value], consumed.value, status.value, ms
+
+
+def fastq_gather(text, text_len, rows, with_qual=True):
+    """mpn_fastq_gather on the rows -> (bases tensor, qualities tensor or None, both of total + 16 bytes rounded up to 16, names)"""
+    import torch
+    lib = _lib()
+    rows = np.ascontiguousarray(rows, dtype=FASTQ_ROW)
+    lens = rows['len'].astype(np.int64)
+    off = np.zeros(len(rows), dtype=np.int64)
+    off[1:] = np.cumsum(lens[:-1])
+    size = _align16(int(lens.sum()) + 16)
+    seq = torch.empty(size, dtype=torch.uint8, device=text.device)
+    qual = torch.empty(size, dtype=torch.uint8, device=text.device) if with_qual else None
+    name_len = rows['name_len'].astype(np.int64)
+    pool = np.zeros(max(int(name_len.sum()), 1), dtype=np.uint8)
+    rc = lib.mpn_fastq_gather(text.data_ptr(), int(text_len), len(rows), _ptr(rows), _ptr(off), seq.data_ptr(), qual.data_ptr() if with_qual else None,
+                              pool.ctypes.data, pool.size)
+    if rc:
+        raise _ffi.MpnError(f'mpn_fastq_gather rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    raw, ends = pool.tobytes(), np.cumsum(name_len)
+    names = [raw[e - l:e].decode() for e, l in zip(ends.tolist(), name_len.tolist())]
+    return seq, qual, names
+
+
+class ReadBatcher:
+    """Cuts reads into batches by the rule of the host loop of aligner.iter_read_batches (a read that would take a batch that is
+    not empty past batch_bases starts the next one).  The reads come as rows of scanned texts in HBM (add_rows) or as host records
+    (add_host: the part of a file fastx.iter_fastx read); a batch may hold both, from several texts and files, and is joined device
+    to device.  add_rows, add_host and flush are generators of the batches that became full."""
+
+    def __init__(self, batch_bases, device='cuda', timings=None):
+        self.batch_bases, self.device, self.timings = batch_bases, device or 'cuda', timings
+        self.pieces, self.acc, self.count = [], 0, 0      # pieces: ('rows', text, text_len, rows) or ('host', names, seqs, quals)
+
+    def add_rows(self, text, text_len, rows):
+        lo = 0
+        for i, l in enumerate(rows['len'].tolist()):
+            if self.count and self.acc + l > self.batch_bases:
+                if i > lo:
+                    self.pieces.append(('rows', text, text_len, rows[lo:i]))
+                yield self._build()
+                lo = i
+            self.acc += l
+            self.count += 1
+        if lo < len(rows):
+            self.pieces.append(('rows', text, text_len, rows[lo:]))
+
+    def add_host(self, name, seq, qual):
+        if self.count and self.acc + len(seq) > self.batch_bases:
+            yield self._build()
+        if not self.pieces or self.pieces[-1][0] != 'host':
+            self.pieces.append(('host', [], [], []))
+        _, names, seqs, quals = self.pieces[-1]
+        names.append(name)
+        seqs.append(seq)
+        quals.append(qual)
+        self.acc += len(seq)
+        self.count += 1
+
+    def flush(self):
+        if self.count:
+            yield self._build()
+
+    def _build(self):
+        import time
+        import torch
+        from . import mapper
+        pieces, self.pieces, self.acc, self.count = self.pieces, [], 0, 0
+        if all(p[0] == 'host' for p in pieces):       # nothing of it is on the device yet: the batch of the host loop
+            return mapper.PackedReads([n for p in pieces for n in p[1]], [s for p in pieces for s in p[2]], device=self.device,
+                                      quals=[q for p in pieces for q in p[3]])
+        t0 = time.perf_counter()
+        parts, names, lens = [], [], []
+        for p in pieces:
+            if p[0] == 'rows':
+                _, text, text_len, rows = p
+                seq, qual, nm = fastq_gather(text, text_len, rows)
+                _tick(self.timings, 'gather_device_ms', last_fastq_device_ms()[1])
+                parts.append((seq, qual, int(rows['len'].astype(np.int64).sum())))
+                lens.append(rows['len'].astype(np.int32))
+            else:     # host records next to '@' records: the batch has qualities, a read without them gets '!' (mapper.PackedReads)
+                _, nm, seqs, quals = p
+                buf, _, ln = mapper.pack_seqs(seqs)
+                qbuf = mapper.pack_seqs([q if q is not None else b'!' * int(l) for q, l in zip(quals, ln)])[0]
+                parts.append((torch.from_numpy(buf).to(self.device), torch.from_numpy(qbuf).to(self.device), int(ln.astype(np.int64).sum())))
+                lens.append(ln)
+            names += nm
+        return _join_batch(parts, names, np.concatenate(lens), True, self.device, self.timings, t0, 'gather')
+
+
+class _ChunkTexts:
+    """The text of a stream of FASTQ bytes (a plain file, or what zlib inflates of a gzip stream) in HBM, MPN_INGEST_BATCH_BYTES at a
+    time, behind the carry.  read_key: where the time spent in the stream's read is booked ('read', or 'inflate' for zlib)."""
+
+    def __init__(self, stream, device, timings=None, read_key='read'):
+        import torch
+        self.torch, self.stream, self.device, self.timings, self.read_key = torch, stream, device, timings, read_key
+        self.chunk = max(1, batch_bytes())
+        self.staging = torch.empty(min(self.chunk, FASTQ_STAGING), dtype=torch.uint8).pin_memory()
+
+    def next_text(self, carry):
+        import time
+        torch = self.torch
+        parts = [] if carry is None or not carry.numel() else [carry]
+        got, eof, view = 0, False, self.staging.numpy()
+        while got < self.chunk and not eof:
+            t0 = time.perf_counter()
+            want, k = min(len(view), self.chunk - got), 0
+            while k < want:
+                m = self.stream.readinto(memoryview(view)[k:want])
+                if not m:
+                    eof = True
+                    break
+                k += m
+            t1 = time.perf_counter()
+            if k:
+                parts.append(self.staging[:k].to(self.device))      # (returns when the copy is done: the buffer is filled again)
+                got += k
+            _tick(self.timings, self.read_key, t1 - t0)
+            _tick(self.timings, 'h2d', time.perf_counter() - t1)
+        final = eof or not self.stream.peek(1)
+        pad = torch.zeros(16, dtype=torch.uint8, device=self.device)
+        text = torch.cat(parts + [pad])
+        return text, text.numel() - 16, final
+
+
+class _TailThenStream:
+    """readline() over `tail` (bytes) and then over `stream`: what fastx.iter_fastx reads when the device hands a file over."""
+
+    def __init__(self, tail, stream):
+        self.tail, self.stream = io.BytesIO(tail), stream
+
+    def readline(self):
+        line = self.tail.readline() if self.tail is not None else b''
+        if line.endswith(b'\n'):
+            return line
+        self.tail = None
+        return line + self.stream.readline()
+
+
+def iter_fastq_read_batches(stream, batch_bases=200_000_000, device='cuda', timings=None, form='plain', batcher=None):
+    """The reads of one FASTQ stream as mapper.PackedReads of at most batch_bases each, resident on the device, with the records of
+    fastx.iter_fastx.  stream: the file's own bytes from their first one (fastx.open_query; read to its end, not closed); form: what
+    they are, 'plain', 'gzip' (inflated by zlib here, as a stream) or 'bgzf' (inflated on the device, block by block).  With a
+    ReadBatcher of the caller's the reads join the batch it holds and the last batch stays in it, for the next file to fill."""
+    import time
+    device = device or 'cuda'
+    own = batcher is None
+    if own:
+        batcher = ReadBatcher(batch_bases, device, timings)
+    if form == 'bgzf':
+        texts, rest = _BgzfTexts(stream, device, timings), None         # (the blocks that were not framed yet are a gzip stream)
+    elif form in ('plain', 'gzip'):
+        rest = stream if form == 'plain' else fastx.gzip_text(stream)
+        texts = _ChunkTexts(rest, device, timings, 'read' if form == 'plain' else 'inflate')
+    else:
+        raise ValueError(f'iter_fastq_read_batches: form {form!r}')
+    carry = None
+    while True:
+        text, text_len, final = texts.next_text(carry)
+        t0 = time.perf_counter()
+        rows, consumed, status, ms = fastq_scan(text, text_len, final)
+        _tick(timings, 'scan', time.perf_counter() - t0)
+        _tick(timings, 'scan_device_ms', ms)
+        _tick(timings, 'records', len(rows))
+        yield from batcher.add_rows(text, text_len, rows)
+        if status == FASTQ_UNSUPPORTED:
+            # the rest of the file for the host: iter_fastx is stateless at a record start
+            t0 = time.perf_counter()
+            tail = text[consumed:text_len].cpu().numpy().tobytes()
+            del text, rows, carry
+            host = _TailThenStream(tail, rest if rest is not None else fastx.gzip_text(stream))
+            n = 0
+            for name, seq, qual in fastx.iter_fastx(host):
+                yield from batcher.add_host(name, seq, qual)
+                n += 1
+            _tick(timings, 'host_records', n)
+            _tick(timings, 'host', time.perf_counter() - t0)
+            break
+        if status != OK:
+            raise _ffi.MpnError(f'mpn_fastq_scan: status {status}')
+        if final:
+            break
+        carry = text[consumed:text_len]
+    if own:
+        yield from batcher.flush()
