@@ -10,6 +10,10 @@
  * bin/mpn-nanofastq mirror the program's stdin/stdout/stderr contract; INTEGRATION.md section 6 shows the switch.
  *
  * All pointers are HOST pointers; arrays are caller-allocated.  Returns 0, or a negative error (mpn_last_error()).
+ *
+ * The same sums from a FASTQ text that is resident on the device, with the headers and the output text of the filter
+ * (MPN_READ_INGEST=device: mpn_fastq_qsum_rows, mpn_fastq_heads, mpn_fastq_emit), are declared in mpn_ingest.h next to
+ * mpn_fastq_scan, whose rows they take.
  */
 #ifndef MPN_FASTQ_H
 #define MPN_FASTQ_H

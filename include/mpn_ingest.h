@@ -24,6 +24,12 @@
  *   mpn_fastq_scan     the text -> a table with a row per plain four-line record, for the longest prefix of such records
  *   mpn_fastq_gather   the rows of a batch of reads -> bases, qualities and names in the layout of mpn_bam_decode (gather16.h)
  *
+ * and of the read filter on such a text (csrc/fastq_filter_kernels.hip; the arithmetic is defined in mpn_fastq.h):
+ *
+ *   mpn_fastq_heads      the rows -> the headers as the host filter reads them: id, separator, comment
+ *   mpn_fastq_qsum_rows  the rows -> the error sums of mpn_fastq_qsum_batch from the qualities where they lie
+ *   mpn_fastq_emit       chosen rows, cropped -> their FASTQ text (gather16.h)
+ *
  * Grouping of files, slot sizing, the fallbacks to the host path and the cutting into index parts are in
  * megapath_nano_amd/ingest.py.  Calling rules as for mpn_bgzf_compress: a call returns when its results are on the host, the
  * default stream is used, -1 = device error (mpn_last_error()), -2 = bad arguments.
@@ -174,6 +180,57 @@ int32_t mpn_fastq_gather(const void *d_text, int64_t text_len, int64_t n, const 
 
 /* Device time of the calling thread's last mpn_fastq_scan and mpn_fastq_gather in milliseconds.  Either pointer may be NULL. */
 void mpn_fastq_last_device_ms(double *scan_ms, double *gather_ms);
+
+/* ---- The read filter on the resident text (csrc/fastq_filter_kernels.hip) -------------------------------------------------------
+ * What `nanofastq` (megapath_nano_amd/fastq_filter.py; its arithmetic is mpn_fastq.h) and `seqtk subseq` (fastx.subseq) need of a
+ * scanned text: the headers with their comments, the error sums of the qualities where they lie, and the FASTQ text of chosen
+ * records, cropped.  All four calls take d_text[0 .. text_len) (DEVICE pointer) and host rows of mpn_fastq_scan on that text (any
+ * subset in any order, or rows moved inside their lines), read nothing outside the text, and return 0, -1 (device error), -2 (bad
+ * arguments, rows that do not lie inside the text: nothing is launched) or -3 (a capacity is too small).
+ *
+ * The header of a record as the HOST FILTER reads it (fastq_filter.parse_fastx -- not the first-word rule of mpn_fastq_scan): the bytes
+ * behind the '@' that opens the line in front of the bases, up to the line end, without the CR of a CRLF.  The line start is found in
+ * the text itself, going back from seq_off - 1 to the previous line feed or to offset 0.  The id ends before the first blank or TAB
+ * (VT and FF stay inside it; it may be empty); the comment is what follows that one byte. */
+typedef struct {
+    int64_t off;          /* the offset behind the '@' */
+    int32_t id_len;
+    int32_t comment_len;  /* bytes behind the separator (from off + id_len + 1); -1: the header has no separator */
+} mpn_fastq_head;
+
+/* heads[r] for r < n.  With name_pool (host, name_pool_cap bytes; or NULL and 0) the ids go one behind the other to it, as the names
+ * of mpn_fastq_gather do; -3 if it is too small (heads is complete then).  Every row needs seq_off >= 2: a header line in front. */
+int32_t mpn_fastq_heads(const void *d_text, int64_t text_len, int64_t n, const mpn_fastq_row *rows, mpn_fastq_head *heads, char *name_pool,
+                        int64_t name_pool_cap);
+
+/* total / cropped / status [r] of the qualities text[qual_off .. + len) of row r, with the contract of mpn_fastq_qsum_batch (mpn_fastq.h):
+ * sequential IEEE-754 additions in read order, then the head and the tail subtractions one by one, bit-identical doubles; table[128]
+ * (host) as there.  One lane per read, 16-byte loads at any alignment of the line.  order (host, n entries, or NULL for 0, 1, ..):
+ * a permutation of 0 .. n - 1; lane i of the launch takes row order[i], so that the caller can put reads of similar length into one
+ * wave (a wave runs as long as its longest read).  Results are stored by row index.  fastq_filter.py passes NULL: ordering by
+ * length did not pay where it was measured (profiles/r18_read_filter/README.md). */
+int32_t mpn_fastq_qsum_rows(const void *d_text, int64_t text_len, int64_t n, const mpn_fastq_row *rows, const int32_t *order, int32_t head_crop,
+                            int32_t tail_crop, int32_t min_len, const double *table, double *total, double *cropped, uint8_t *status);
+
+/* What is written of record r: bases and qualities [start, start + m) of its row, its comment or not, its own id or a serial. */
+typedef struct {
+    int32_t start, m;        /* 0 <= start, 0 <= m, start + m <= len */
+    int32_t with_comment;    /* 1: ' ' + comment behind the id (comment_len < 0 counts as an empty comment: the blank alone) */
+    int32_t reserved;        /* 0 */
+    int64_t serial;          /* 0: the id of the header; > 0: the id is prefix + the decimal digits of serial */
+} mpn_fastq_pick;
+
+/* The FASTQ text of n records to d_out (DEVICE, 16-byte aligned): record r is
+ *   '@' id [' ' comment] LF  seq[start .. start + m)  LF '+' LF  qual[start .. start + m)  LF
+ * at d_out[out_off[r] .. out_off[r + 1]).  out_off (host, n + 1 entries) starts at 0 and is the exclusive sum of these sizes: the call
+ * checks that, and that out_cap holds out_off[n] rounded up to a multiple of 16 (what follows the last record up to there is
+ * zeroed), before anything is launched (-2 otherwise).  prefix: prefix_len bytes (host) in front of every serial.  Shaped like the other
+ * gathers (csrc/gather16.h): a wave per MPN_BAM_CHUNK bytes of output, every byte written once by aligned 16-byte stores. */
+int32_t mpn_fastq_emit(const void *d_text, int64_t text_len, int64_t n, const mpn_fastq_row *rows, const mpn_fastq_head *heads,
+                       const mpn_fastq_pick *picks, const char *prefix, int32_t prefix_len, const int64_t *out_off, void *d_out, int64_t out_cap);
+
+/* Device time of the calling thread's last mpn_fastq_heads, mpn_fastq_qsum_rows and mpn_fastq_emit.  Any pointer may be NULL. */
+void mpn_fastq_filter_last_device_ms(double *heads_ms, double *sums_ms, double *emit_ms);
 
 #ifdef __cplusplus
 }

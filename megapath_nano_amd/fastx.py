@@ -81,17 +81,23 @@ def open_query(path):
     'plain'; the stream is ALWAYS the file's own bytes, positioned at its first byte (gzip_text decompresses it); first is the first
     byte of the text, b'' for an empty file or where the bytes at hand do not say.  The path is opened exactly once."""
     raw, peeked = _open_raw(path)
+    kind, first = query_form(peeked)
+    return kind, raw, first
+
+
+def query_form(peeked):
+    """open_query's (kind, first) from the first bytes of a file (of a stream that cannot be opened by a path: the read filter's stdin)"""
     if peeked[:8] == INDEX_MAGIC:
-        return 'index', raw, b''
+        return 'index', b''
     if peeked[:2] != b'\x1f\x8b':
-        return 'plain', raw, peeked[:1]
+        return 'plain', peeked[:1]
     if _is_bam(peeked):
-        return 'bam', raw, b''
+        return 'bam', b''
     try:
         first = zlib.decompressobj(31).decompress(peeked, 1)
     except zlib.error:
         first = b''
-    return ('bgzf' if _bgzf_data_start(peeked) else 'gzip'), raw, first
+    return ('bgzf' if _bgzf_data_start(peeked) else 'gzip'), first
 
 
 def _no_bam(kind, path, what):
@@ -194,25 +200,76 @@ def subseq(in_path, names, out):
     bin/megapath_nano.py:1221-1233): the records whose name is listed, in input order, FASTQ records as
     `@name[ comment]`, sequence, `+`, quality on single lines, FASTA records as `>name[ comment]` and the sequence.
     names: iterable of read names; out: binary stream.  -> number of records written."""
+    from . import ingest
     wanted = {n if isinstance(n, str) else n.decode() for n in names}
-    kind, stream = open_once(in_path)
-    n = 0
+    if ingest.read_ingest_mode() == 'device':
+        kind, stream, first = open_query(in_path)
+        if kind in ('plain', 'gzip', 'bgzf') and first == b'@':
+            return _subseq_device(stream, kind, wanted, out)
+        if kind not in ('index', 'bam'):
+            stream = gzip_text(stream) if kind != 'plain' else stream        # open_once's stream: the path is opened once
+    else:
+        kind, stream = open_once(in_path)
     try:
         if kind == 'index':
             raise ValueError(f'{in_path}: a saved index, not sequences')
         _no_bam(kind, in_path, 'by subseq')
-        for name, comment, seq, qual in iter_fastx_full(stream):
-            if name not in wanted:
-                continue
-            head = name.encode() + ((b' ' + comment) if comment is not None else b'')
-            if qual is not None:
-                out.write(b'@' + head + b'\n' + seq + b'\n+\n' + qual + b'\n')
-            else:
-                out.write(b'>' + head + b'\n' + seq + b'\n')
-            n += 1
+        return _subseq_host(stream, wanted, out)
     finally:
         stream.close()
+
+
+def _subseq_host(stream, wanted, out):
+    n = 0
+    for name, comment, seq, qual in iter_fastx_full(stream):
+        if name not in wanted:
+            continue
+        head = name.encode() + ((b' ' + comment) if comment is not None else b'')
+        if qual is not None:
+            out.write(b'@' + head + b'\n' + seq + b'\n+\n' + qual + b'\n')
+        else:
+            out.write(b'>' + head + b'\n' + seq + b'\n')
+        n += 1
     return n
+
+
+def _subseq_device(stream, kind, wanted, out, device='cuda'):
+    """subseq on the text in HBM (MPN_READ_INGEST=device): per text the scan, the ids by the header rule of the read filter
+    (include/mpn_ingest.h: the rule of iter_fastx_full on a plain record), and the listed records as mpn_fastq_emit writes them,
+    uncropped, `@name ` keeping its blank.  From the first record the scan does not take, iter_fastx_full continues.  Closes the stream."""
+    import numpy as np
+    from . import fastq_filter, ingest
+    n = 0
+    try:
+        if kind == 'bgzf':
+            texts, rest = ingest._BgzfTexts(stream, device), None
+        else:
+            rest = stream if kind == 'plain' else gzip_text(stream)
+            texts = ingest._ChunkTexts(rest, device)
+        carry = None
+        while True:
+            text, text_len, final = texts.next_text(carry)
+            rows, consumed, status, _ = ingest.fastq_scan(text, text_len, final)
+            if len(rows):
+                heads, ids = fastq_filter.fastq_heads(text, text_len, rows)
+                keep = np.array([k for k, name in enumerate(ids) if name.decode() in wanted], dtype=np.int64)
+                picks = np.zeros(len(keep), dtype=fastq_filter.FASTQ_PICK)
+                picks['m'] = rows['len'][keep]
+                picks['with_comment'] = heads['comment_len'][keep] >= 0
+                d_out, out_off = fastq_filter.fastq_emit(text, text_len, rows[keep], heads[keep], picks)
+                out.write(memoryview(d_out[:int(out_off[-1])].cpu().numpy()))
+                n += len(keep)
+            if status == ingest.FASTQ_UNSUPPORTED:
+                tail = text[consumed:text_len].cpu().numpy().tobytes()
+                del text, rows, carry
+                return n + _subseq_host(ingest._TailThenStream(tail, rest if rest is not None else gzip_text(stream)), wanted, out)
+            if status != ingest.OK:
+                raise RuntimeError(f'mpn_fastq_scan: status {status}')
+            if final:
+                return n
+            carry = text[consumed:text_len]
+    finally:
+        stream.close()
 
 
 def read_split_list(path):

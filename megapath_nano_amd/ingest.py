@@ -28,6 +28,9 @@ host for an ordinary gzip stream, or through the front half of the BAM path (_Bg
 
 At the first record that is not plain the rest of the file -- the tail of the text and what the stream still holds -- goes through
 fastx.iter_fastx, and its records keep filling the same batches.
+
+The read filter and subseq (fastq_filter.filter_stream, fastx.subseq under the same knob) take their texts from the same sources
+(_ChunkTexts, _BgzfTexts), scan them with fastq_scan and hand kept rows to a ReadBatcher.
 """
 import ctypes as ct
 import gzip
@@ -856,20 +859,21 @@ class ReadBatcher:
 
     def __init__(self, batch_bases, device='cuda', timings=None):
         self.batch_bases, self.device, self.timings = batch_bases, device or 'cuda', timings
-        self.pieces, self.acc, self.count = [], 0, 0      # pieces: ('rows', text, text_len, rows) or ('host', names, seqs, quals)
+        self.pieces, self.acc, self.count = [], 0, 0      # pieces: ('rows', text, text_len, rows, names or None) or ('host', names, seqs, quals)
 
-    def add_rows(self, text, text_len, rows):
+    def add_rows(self, text, text_len, rows, names=None):
+        """names: what the reads are called, where that is not the name the rows point at (the read filter's -r serials)"""
         lo = 0
         for i, l in enumerate(rows['len'].tolist()):
             if self.count and self.acc + l > self.batch_bases:
                 if i > lo:
-                    self.pieces.append(('rows', text, text_len, rows[lo:i]))
+                    self.pieces.append(('rows', text, text_len, rows[lo:i], names and names[lo:i]))
                 yield self._build()
                 lo = i
             self.acc += l
             self.count += 1
         if lo < len(rows):
-            self.pieces.append(('rows', text, text_len, rows[lo:]))
+            self.pieces.append(('rows', text, text_len, rows[lo:], names and names[lo:]))
 
     def add_host(self, name, seq, qual):
         if self.count and self.acc + len(seq) > self.batch_bases:
@@ -899,8 +903,9 @@ class ReadBatcher:
         parts, names, lens = [], [], []
         for p in pieces:
             if p[0] == 'rows':
-                _, text, text_len, rows = p
+                _, text, text_len, rows, given = p
                 seq, qual, nm = fastq_gather(text, text_len, rows)
+                nm = given or nm
                 _tick(self.timings, 'gather_device_ms', last_fastq_device_ms()[1])
                 parts.append((seq, qual, int(rows['len'].astype(np.int64).sum())))
                 lens.append(rows['len'].astype(np.int32))
@@ -962,6 +967,12 @@ class _TailThenStream:
             return line
         self.tail = None
         return line + self.stream.readline()
+
+    def read(self):
+        """all that is left (the read filter's host path parses whole texts)"""
+        rest = self.tail.read() if self.tail is not None else b''
+        self.tail = None
+        return rest + self.stream.read()
 
 
 def iter_fastq_read_batches(stream, batch_bases=200_000_000, device='cuda', timings=None, form='plain', batcher=None):
