@@ -1,6 +1,7 @@
 // Host orchestration of the mapper (index build, seed + chain stages) behind include/mpn_map.h.
 #include "map_kernels.h"
 #include "mapper_internal.h"
+#include "stage_input.h"
 #include "../../include/mpn_map.h"
 
 #include <algorithm>
@@ -1127,9 +1128,7 @@ int mpn_chain_batch(const mpn_map_opt *opt, int32_t n, const int64_t *anchor_off
     if (chain_item < 0 || bt_par_min < 0 || grid_cap < 0 || u_cap < 0 || b_cap < 0) { set_error("mpn_chain_batch: chain_item, bt_par_min, grid_cap or a capacity negative"); return -1; }
     if (n == 0) return 0;
     if (!anchor_off || !n_chain || !n_chained) { set_error("mpn_chain_batch: an array missing"); return -1; }
-    if (anchor_off[0] != 0) { set_error("mpn_chain_batch: offsets do not start at 0"); return -1; }
-    for (int i = 0; i < n; ++i)
-        if (anchor_off[i + 1] < anchor_off[i] || anchor_off[i + 1] - anchor_off[i] > 0x3fffffff) { set_error("mpn_chain_batch: read %d: offsets out of order", i); return -1; }
+    if (!mpn_stage::stage_csr_ok("mpn_chain_batch", n, anchor_off, set_error)) return -1;
     const int64_t n_a = anchor_off[n];
     if (n_a > 0 && !anchors) { set_error("mpn_chain_batch: an array missing"); return -1; }
     // per read: the anchors its average seed length is taken over (all of them) and the sum of their seed lengths

@@ -800,6 +800,27 @@ class Hits:
             pass
 
 
+def _pack_pairs(queries, targets):
+    """(query, target) pairs of 0..4 codes -> (qbuf, qoff, qlen, tbuf, toff, tlen) as the stage entries take them"""
+    return pack_seqs([np.asarray(q, dtype=np.uint8) for q in queries]) + pack_seqs([np.asarray(t, dtype=np.uint8) for t in targets])
+
+
+def _pack_alns(n, q_ivals, revs, t_starts, cigars):
+    """the alignments of n pairs -> (qs, qe, rev, ts, cig, coff, ncig): the CIGARs one after the other, one spare op behind them"""
+    qs = np.ascontiguousarray([iv[0] for iv in q_ivals], dtype=np.int32)
+    qe = np.ascontiguousarray([iv[1] for iv in q_ivals], dtype=np.int32)
+    rev = np.ascontiguousarray(np.broadcast_to(np.asarray(revs, dtype=np.int32), (n,)))
+    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(t_starts, dtype=np.int32), (n,)))
+    ncig = np.array([len(c) for c in cigars], dtype=np.int32)
+    coff = np.zeros(n, dtype=np.int64)
+    if n > 1:
+        coff[1:] = np.cumsum(ncig[:-1].astype(np.int64))
+    cig = np.zeros(int(ncig.astype(np.int64).sum()) + 1, dtype=np.uint32)
+    for c, o in zip(cigars, coff):
+        cig[o:o + len(c)] = np.asarray(c, dtype=np.uint32)
+    return qs, qe, rev, ts, cig, coff, ncig
+
+
 def ext_dp_batch(opt, queries, targets, w, zdrop, end_bonus, flag, force_kernel=0):
     """DP stage on (query, target) pairs of 0..4 codes -> list of dicts (max, zdropped, max_q, max_t, mqe, mqe_t, score, reach_end, n_cigar, cigar).
 
@@ -808,8 +829,7 @@ def ext_dp_batch(opt, queries, targets, w, zdrop, end_bonus, flag, force_kernel=
     fits 1024 slots; 6 tiled strips where eligible.  Other windows go to the workgroup kernel, sized as under 0."""
     lib = _bind()
     n = len(queries)
-    qbuf, qoff, qlen = pack_seqs([np.asarray(q, dtype=np.uint8) for q in queries])
-    tbuf, toff, tlen = pack_seqs([np.asarray(t, dtype=np.uint8) for t in targets])
+    qbuf, qoff, qlen, tbuf, toff, tlen = _pack_pairs(queries, targets)
     arr = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.int32), (n,)))  # noqa: E731
     w, zdrop, end_bonus, flag = arr(w), arr(zdrop), arr(end_bonus), arr(flag)
     out = np.zeros((n, 9), dtype=np.int32)
@@ -836,19 +856,8 @@ def aln_tags_batch(queries, q_ivals, revs, targets, t_starts, cigars, out_tags, 
     that always fit.  -> list of dict(cs=str or None, md=str or None, eqx=list or None), outputs that were not asked for None."""
     lib = _bind()
     n = len(queries)
-    qbuf, qoff, qlen = pack_seqs([np.asarray(q, dtype=np.uint8) for q in queries])
-    tbuf, toff, tlen = pack_seqs([np.asarray(t, dtype=np.uint8) for t in targets])
-    qs = np.ascontiguousarray([iv[0] for iv in q_ivals], dtype=np.int32)
-    qe = np.ascontiguousarray([iv[1] for iv in q_ivals], dtype=np.int32)
-    rev = np.ascontiguousarray(np.broadcast_to(np.asarray(revs, dtype=np.int32), (n,)))
-    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(t_starts, dtype=np.int32), (n,)))
-    ncig = np.array([len(c) for c in cigars], dtype=np.int32)
-    coff = np.zeros(n, dtype=np.int64)
-    if n > 1:
-        coff[1:] = np.cumsum(ncig[:-1].astype(np.int64))
-    cig = np.zeros(int(ncig.astype(np.int64).sum()) + 1, dtype=np.uint32)
-    for c, o in zip(cigars, coff):
-        cig[o:o + len(c)] = np.asarray(c, dtype=np.uint32)
+    qbuf, qoff, qlen, tbuf, toff, tlen = _pack_pairs(queries, targets)
+    qs, qe, rev, ts, cig, coff, ncig = _pack_alns(n, q_ivals, revs, t_starts, cigars)
     cols = sum(int(x) >> 4 for c in cigars for x in c)
     ops = int(ncig.astype(np.int64).sum())
     want_cs, want_md, want_eqx = bool(out_tags & (TAG_CS | TAG_CS_LONG)), bool(out_tags & TAG_MD), bool(out_tags & TAG_EQX)
@@ -878,19 +887,8 @@ def aln_finish_batch(opt, queries, q_ivals, revs, targets, t_starts, cigars, for
     global scratch.  -> list of dict(n_cigar, qshift, tshift, blen, mlen, n_ambi, dp_max, cigar)."""
     lib = _bind()
     n = len(queries)
-    qbuf, qoff, qlen = pack_seqs([np.asarray(q, dtype=np.uint8) for q in queries])
-    tbuf, toff, tlen = pack_seqs([np.asarray(t, dtype=np.uint8) for t in targets])
-    qs = np.ascontiguousarray([iv[0] for iv in q_ivals], dtype=np.int32)
-    qe = np.ascontiguousarray([iv[1] for iv in q_ivals], dtype=np.int32)
-    rev = np.ascontiguousarray(np.broadcast_to(np.asarray(revs, dtype=np.int32), (n,)))
-    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(t_starts, dtype=np.int32), (n,)))
-    ncig = np.array([len(c) for c in cigars], dtype=np.int32)
-    coff = np.zeros(n, dtype=np.int64)
-    if n > 1:
-        coff[1:] = np.cumsum(ncig[:-1].astype(np.int64))
-    cig = np.zeros(int(ncig.astype(np.int64).sum()) + 1, dtype=np.uint32)
-    for c, o in zip(cigars, coff):
-        cig[o:o + len(c)] = np.asarray(c, dtype=np.uint32)
+    qbuf, qoff, qlen, tbuf, toff, tlen = _pack_pairs(queries, targets)
+    qs, qe, rev, ts, cig, coff, ncig = _pack_alns(n, q_ivals, revs, t_starts, cigars)
     out = np.zeros((n, 8), dtype=np.int32)
     fixed = np.zeros_like(cig)
     rc = lib.mpn_aln_finish_batch(ct.byref(opt), n, qbuf.ctypes.data, qoff.ctypes.data, qlen.ctypes.data, qs.ctypes.data, qe.ctypes.data,

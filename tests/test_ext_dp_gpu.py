@@ -69,6 +69,58 @@ def opt(libmpn, oracle_built):
     return mapper.default_opt()
 
 
+def raw_call(opt, q, t, force_kernel, q_len=None, t_off=0):
+    """mpn_ext_dp_batch on one pair with w = 4, by hand, so that a length or an offset can be given that ext_dp_batch never packs"""
+    import ctypes as ct
+    from megapath_nano_amd import _ffi, mapper
+    qbuf, qoff, qlen, tbuf, toff, tlen = mapper._pack_pairs([q], [t])
+    if q_len is not None:
+        qlen[0] = q_len
+    toff[0] = t_off
+    par = [np.array([v], dtype=np.int32) for v in (4, 400, -1, 0)]
+    out, pool, coff = np.zeros((1, 9), dtype=np.int32), np.zeros(64, dtype=np.uint32), np.zeros(1, dtype=np.int64)
+    rc = mapper._bind().mpn_ext_dp_batch(ct.byref(opt), 1, qbuf.ctypes.data, qoff.ctypes.data, qlen.ctypes.data, tbuf.ctypes.data,
+                                         toff.ctypes.data, tlen.ctypes.data, *(p.ctypes.data for p in par), force_kernel,
+                                         out.ctypes.data, pool.ctypes.data, len(pool), coff.ctypes.data)
+    _ffi.check(rc, 'mpn_ext_dp_batch')
+    return out[0].tolist(), pool[:out[0, 8]].tolist()
+
+
+@pytest.fixture(scope='module')
+def pair8():
+    rng = np.random.default_rng(5)
+    t = rng.integers(0, 4, size=8).astype(np.uint8)
+    q = t.copy()
+    q[3] = (q[3] + 1) % 4
+    return q, t
+
+
+def test_negative_query_length_is_refused(opt, pair8):
+    from megapath_nano_amd import _ffi
+    with pytest.raises(_ffi.MpnError, match=r'rc=-1'):
+        raw_call(opt, *pair8, 0, q_len=-1)
+
+
+def test_target_offset_past_the_buffer_is_refused(opt, pair8):
+    """the entry is given no buffer sizes: what it refuses without reading anything is an offset that no buffer it serves can hold
+    (beyond 2^30 - 1), here one far past the 24 bytes that the target buffer has"""
+    from megapath_nano_amd import _ffi
+    with pytest.raises(_ffi.MpnError, match=r'rc=-1'):
+        raw_call(opt, *pair8, 0, t_off=1 << 40)
+
+
+def test_valid_call_after_a_refused_one(opt, pair8):
+    """a refused call leaves no forced kernel behind: the dispatch (0) answers as it does when it is asked first"""
+    from megapath_nano_amd import _ffi, mapper
+    first = raw_call(opt, *pair8, 0)
+    assert first[0][8] >= 1 and len(first[1]) == first[0][8]
+    with pytest.raises(_ffi.MpnError, match=r'rc=-1'):
+        raw_call(opt, *pair8, 5, q_len=-1)
+    assert raw_call(opt, *pair8, 0) == first
+    d = mapper.ext_dp_batch(opt, [pair8[0]], [pair8[1]], 4, 400, -1, 0)[0]
+    assert [d[k] for k in ('max', 'zdropped', 'max_q', 'max_t', 'mqe', 'mqe_t', 'score', 'reach_end', 'n_cigar')] == first[0] and d['cigar'] == first[1]
+
+
 def test_gap_fill_windows_all_kernels(opt):
     qs, ts = make_pairs(1, [30, 64, 65, 128, 200, 230, 256, 257, 300, 400, 511])
     check(opt, qs, ts, 751, 400, -1, APPROX, [1, 3, 4, 5, 0])
