@@ -30,6 +30,12 @@
  *   mpn_fastq_qsum_rows  the rows -> the error sums of mpn_fastq_qsum_batch from the qualities where they lie
  *   mpn_fastq_emit       chosen rows, cropped -> their FASTQ text (gather16.h)
  *
+ * and of the name lists that `nanosplit` and `seqtk subseq` (fastx.py) match the records of such a text against
+ * (csrc/name_lookup_kernels.hip; the table is csrc/name_set_core.h, which also compiles for the host):
+ *
+ *   mpn_name_set_create    a list of names -> a hash table of them in HBM, built on the host
+ *   mpn_fastq_name_lookup  the headers -> the list entry each record's id is, the ids staying on the device
+ *
  * Grouping of files, slot sizing, the fallbacks to the host path and the cutting into index parts are in
  * megapath_nano_amd/ingest.py.  Calling rules as for mpn_bgzf_compress: a call returns when its results are on the host, the
  * default stream is used, -1 = device error (mpn_last_error()), -2 = bad arguments.
@@ -231,6 +237,29 @@ int32_t mpn_fastq_emit(const void *d_text, int64_t text_len, int64_t n, const mp
 
 /* Device time of the calling thread's last mpn_fastq_heads, mpn_fastq_qsum_rows and mpn_fastq_emit.  Any pointer may be NULL. */
 void mpn_fastq_filter_last_device_ms(double *heads_ms, double *sums_ms, double *emit_ms);
+
+/* ---- Read names matched on the resident text (csrc/name_lookup_kernels.hip; hash, probe step and slot layout: csrc/name_set_core.h) --
+ * A list of n names in HBM as an open-addressing table with linear probing.  Name i is pool[off[i] .. off[i + 1]) (host; any bytes,
+ * none included; n may be 0).  The table is built on the host, serially, so its layout depends on the list and on `slots` alone;
+ * equal names share one slot, which holds the SMALLEST of their indices, and first_of[i] (host, n entries, or NULL) is that index
+ * for every i.  slots = 0: the smallest power of two >= 2 x (distinct names), at least 16; any other value must be a power of two
+ * larger than the number of distinct names (-2 otherwise; a small table is how tests force long probe chains).  *set owns device
+ * memory until mpn_name_set_free (NULL is allowed there).  Returns 0, -1 (device error, out of memory) or -2. */
+typedef struct mpn_name_set mpn_name_set;
+int32_t mpn_name_set_create(int64_t n, const char *pool, const int64_t *off /* n + 1 */, int64_t slots, mpn_name_set **set,
+                            int32_t *first_of /* n, or NULL */);
+void mpn_name_set_free(mpn_name_set *set);
+
+/* found[r] (host, n entries) for the record whose header is heads[r] (host; of mpn_fastq_heads on this d_text): the smallest list index
+ * whose bytes are the id d_text[heads[r].off .. + id_len), or -1.  One lane per record; the id and the pooled name are compared by
+ * 16-byte loads at any alignment, and a slot whose hash or length differs costs no load from the pool.  Every 16-byte vector that
+ * is read from the text holds a byte of an id.  Returns 0, -1, or -2 before anything is launched: a NULL set, a negative id_len, an
+ * id that does not lie inside the text. */
+int32_t mpn_fastq_name_lookup(const void *d_text, int64_t text_len, int64_t n, const mpn_fastq_head *heads, const mpn_name_set *set,
+                              int32_t *found /* n */);
+
+/* Device time of the calling thread's last mpn_fastq_name_lookup.  The pointer may be NULL. */
+void mpn_fastq_lookup_last_device_ms(double *lookup_ms);
 
 #ifdef __cplusplus
 }

@@ -33,8 +33,10 @@ __device__ __forceinline__ int64_t last_le(const int64_t *__restrict__ v, int64_
 // them, shifted into place; the second vector is touched only when its bytes are needed.  Both vectors hold at least one of the
 // 16 bytes, so they lie in the allocation the bytes lie in (device allocations are 16-byte granular); a caller whose source may
 // end sooner checks that itself.
-__device__ __forceinline__ uint4 load16_at(const uint4 *v, uint32_t sh16) {
-    const uint4 lo4 = v[0], hi4 = sh16 ? v[1] : make_uint4(0, 0, 0, 0);
+// (load16_first: the same with only the first cnt of the 16 bytes wanted, so that the second vector is touched only when one of
+// THOSE lies in it; what the other bytes of the result are is not defined.)
+__device__ __forceinline__ uint4 load16_first(const uint4 *v, uint32_t sh16, uint32_t cnt) {
+    const uint4 lo4 = v[0], hi4 = sh16 + cnt > 16 ? v[1] : make_uint4(0, 0, 0, 0);
     uint32_t x0, x1, x2, x3, x4;
     switch (sh16 >> 2) {   // (the same in every lane that copies from the same piece)
         case 0: x0 = lo4.x; x1 = lo4.y; x2 = lo4.z; x3 = lo4.w; x4 = hi4.x; break;
@@ -45,6 +47,15 @@ __device__ __forceinline__ uint4 load16_at(const uint4 *v, uint32_t sh16) {
     const uint32_t sh = sh16 & 3;
     return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x2, x1, sh), __builtin_amdgcn_alignbyte(x3, x2, sh),
                       __builtin_amdgcn_alignbyte(x4, x3, sh));
+}
+__device__ __forceinline__ uint4 load16_at(const uint4 *v, uint32_t sh16) { return load16_first(v, sh16, 16); }
+// The first cnt (1..15) of those 16 bytes and zeros behind them: for the end of a piece that has no 16 bytes left.  Both vectors
+// that are touched hold a byte of the piece here too.
+__device__ __forceinline__ uint4 load16_head(const uint4 *v, uint32_t sh16, uint32_t cnt) {
+    const uint4 w = load16_first(v, sh16, cnt);
+    const uint32_t full = cnt >> 2, part = (1u << (8 * (cnt & 3))) - 1;     // whole words kept, the mask of the word behind them
+    return make_uint4(full > 0 ? w.x : part & w.x, full > 1 ? w.y : (full == 1 ? part & w.y : 0), full > 2 ? w.z : (full == 2 ? part & w.z : 0),
+                      full == 3 ? part & w.w : 0);
 }
 // 16 bytes from any address.  (A caller that has its source as an aligned base and an offset calls load16_at with them: the
 // compiler then still knows that the base is global memory, which an address that went through an integer no longer says.)

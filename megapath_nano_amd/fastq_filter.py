@@ -203,6 +203,14 @@ def _dev_lib():
         lib.mpn_fastq_emit.restype = I32
         lib.mpn_fastq_filter_last_device_ms.argtypes = [ct.POINTER(ct.c_double)] * 3
         lib.mpn_fastq_filter_last_device_ms.restype = None
+        lib.mpn_name_set_create.argtypes = [I64, P, P, I64, ct.POINTER(P), P]
+        lib.mpn_name_set_create.restype = I32
+        lib.mpn_name_set_free.argtypes = [P]
+        lib.mpn_name_set_free.restype = None
+        lib.mpn_fastq_name_lookup.argtypes = [P, I64, I64, P, P, P]
+        lib.mpn_fastq_name_lookup.restype = I32
+        lib.mpn_fastq_lookup_last_device_ms.argtypes = [ct.POINTER(ct.c_double)]
+        lib.mpn_fastq_lookup_last_device_ms.restype = None
         _bound = True
     return lib
 
@@ -236,6 +244,60 @@ def fastq_heads(text, text_len, rows, with_ids=True):
         return heads, None
     raw, ends = pool.tobytes(), np.cumsum(heads['id_len'].astype(np.int64))
     return heads, [raw[e - l:e] for e, l in zip(ends.tolist(), heads['id_len'].tolist())]
+
+
+class NameSet:
+    """mpn_name_set_create: a list of names (bytes) as a hash table in HBM.  first_of[i]: the smallest index with the bytes of
+    name i.  slots: 0 for the default size, or a power of two larger than the number of distinct names.  close() frees the device
+    memory (also a context manager)."""
+
+    def __init__(self, names, slots=0):
+        lib = _dev_lib()
+        names = list(names)
+        off = np.zeros(len(names) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in names], out=off[1:])
+        pool = b''.join(names)
+        self.first_of = np.zeros(len(names), dtype=np.int32)
+        self.n, self._set = len(names), ct.c_void_p()
+        rc = lib.mpn_name_set_create(len(names), pool, off.ctypes.data, int(slots), ct.byref(self._set), self.first_of.ctypes.data)
+        if rc:
+            self._set = None
+            raise _ffi.MpnError(f'mpn_name_set_create rc={rc}: {_ffi.hint(_ffi.last_error())}')
+
+    def close(self):
+        if self._set is not None:
+            _dev_lib().mpn_name_set_free(self._set)
+            self._set = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def last_lookup_device_ms():
+    """-> the device ms of the calling thread's last mpn_fastq_name_lookup"""
+    v = ct.c_double(0)
+    _dev_lib().mpn_fastq_lookup_last_device_ms(ct.byref(v))
+    return v.value
+
+
+def fastq_name_lookup(text, text_len, heads, name_set):
+    """mpn_fastq_name_lookup -> found (int32 per head): the smallest index of name_set's list whose bytes are the record's id, or -1"""
+    lib = _dev_lib()
+    heads = np.ascontiguousarray(heads, dtype=FASTQ_HEAD)
+    found = np.zeros(len(heads), dtype=np.int32)
+    rc = lib.mpn_fastq_name_lookup(text.data_ptr(), int(text_len), len(heads), heads.ctypes.data, name_set._set, found.ctypes.data)
+    if rc:
+        raise _ffi.MpnError(f'mpn_fastq_name_lookup rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    return found
 
 
 def qsum_rows(text, text_len, rows, head_crop, tail_crop, min_len, by_length=False):

@@ -240,7 +240,9 @@ def _subseq_device(stream, kind, wanted, out, device='cuda'):
     import numpy as np
     from . import fastq_filter, ingest
     n = 0
+    name_set = None
     try:
+        name_set = fastq_filter.NameSet([k.encode() for k in wanted])
         if kind == 'bgzf':
             texts, rest = ingest._BgzfTexts(stream, device), None
         else:
@@ -251,8 +253,8 @@ def _subseq_device(stream, kind, wanted, out, device='cuda'):
             text, text_len, final = texts.next_text(carry)
             rows, consumed, status, _ = ingest.fastq_scan(text, text_len, final)
             if len(rows):
-                heads, ids = fastq_filter.fastq_heads(text, text_len, rows)
-                keep = np.array([k for k, name in enumerate(ids) if name.decode() in wanted], dtype=np.int64)
+                heads, _ = fastq_filter.fastq_heads(text, text_len, rows, with_ids=False)
+                keep = np.flatnonzero(fastq_filter.fastq_name_lookup(text, text_len, heads, name_set) >= 0)
                 picks = np.zeros(len(keep), dtype=fastq_filter.FASTQ_PICK)
                 picks['m'] = rows['len'][keep]
                 picks['with_comment'] = heads['comment_len'][keep] >= 0
@@ -270,6 +272,8 @@ def _subseq_device(stream, kind, wanted, out, device='cuda'):
             carry = text[consumed:text_len]
     finally:
         stream.close()
+        if name_set is not None:
+            name_set.close()
 
 
 def read_split_list(path):
@@ -287,13 +291,175 @@ def read_split_list(path):
     return {n: sorted(s) for n, s in files.items()}, list(index)
 
 
-def nanosplit(read_list_path, in_paths, device=None):
+def split_emit_plan(found, name_ptr, name_out, n_outputs, heads, rows):
+    """What one scanned text contributes to the outputs of nanosplit, in numpy (no GPU).  found[r]: the list name record r is, or -1
+    (fastq_filter.fastq_name_lookup); name k is listed for the outputs name_out[name_ptr[k] : name_ptr[k + 1]] (ascending); heads and
+    rows: of the text's records.  -> SplitPlan: the (record, output) PAIRS sorted by (output, record) as `rec` and `out`; the emit
+    `picks` of the pairs (uncropped; the comment only where it is not empty, as the reference writes it); `out_off` [pairs + 1], the
+    exclusive sum of the record sizes mpn_fastq_emit checks; `pair_first` [n_outputs + 1]: output g owns the pairs
+    pair_first[g] .. pair_first[g + 1], that is the bytes out_off[pair_first[g]] .. out_off[pair_first[g + 1]] of the emitted text.  A
+    record whose name is listed once is one pair however often the name occurs in the text: every occurrence is its own record."""
+    import collections
+    import numpy as np
+    from . import fastq_filter
+    found, name_ptr, name_out = (np.asarray(a, dtype=np.int64) for a in (found, name_ptr, name_out))
+    hit = np.flatnonzero(found >= 0)
+    first = name_ptr[found[hit]]
+    counts = name_ptr[found[hit] + 1] - first
+    rec = np.repeat(hit, counts)
+    within = np.arange(len(rec), dtype=np.int64) - np.repeat(np.cumsum(counts) - counts, counts)
+    out = name_out[np.repeat(first, counts) + within]
+    order = np.argsort(out, kind='stable')           # pairs arise in record order: stable by output is (output, record)
+    rec, out = rec[order], out[order]
+    picks = np.zeros(len(rec), dtype=fastq_filter.FASTQ_PICK)
+    picks['m'] = rows['len'][rec]
+    picks['with_comment'] = heads['comment_len'][rec] > 0
+    out_off = np.zeros(len(rec) + 1, dtype=np.int64)
+    np.cumsum(fastq_filter.record_sizes(heads[rec], picks), out=out_off[1:])
+    pair_first = np.searchsorted(out, np.arange(n_outputs + 1, dtype=np.int64)).astype(np.int64)
+    return collections.namedtuple('SplitPlan', 'rec out picks out_off pair_first')(rec, out, picks, out_off, pair_first)
+
+
+def emit_rounds(out_off, limit):
+    """Consecutive pairs of a plan in rounds of at most `limit` bytes of output and at least one pair -> [(first pair, end pair)]"""
+    import numpy as np
+    rounds, a, n = [], 0, len(out_off) - 1
+    while a < n:
+        b = max(int(np.searchsorted(out_off, out_off[a] + max(int(limit), 0), side='right')) - 1, a + 1)
+        rounds.append((a, b))
+        a = b
+    return rounds
+
+
+def _nanosplit_device(read_list_path, in_paths, device, timings):
+    """nanosplit on the text in HBM (MPN_READ_INGEST=device).  One name set for the list; per input file, text by text
+    (MPN_INGEST_BATCH_BYTES): the scan, the headers, mpn_fastq_name_lookup -- the ids stay on the device --, split_emit_plan, and
+    mpn_fastq_emit in rounds of at most MPN_INGEST_BATCH_BYTES of output, each downloaded once and its slices appended to their
+    files.  A file is open only while it is written, so the number of outputs does not meet the descriptor limit.  Texts, rounds
+    and input files follow each other strictly, which is the order inside every output.  From the first record the scan does not
+    take, and for an input that does not start with '@', iter_fastx_full and the host's formatting continue into the same files."""
+    import time
+    import numpy as np
+    from . import fastq_filter, ingest
+    tick = ingest._tick
+    wanted, out_paths = read_split_list(read_list_path)
+    for p in out_paths:
+        open(p, 'wb').close()
+    names = list(wanted)
+    name_ptr = np.zeros(len(names) + 1, dtype=np.int64)
+    np.cumsum([len(wanted[k]) for k in names], out=name_ptr[1:])
+    name_out = np.array([g for k in names for g in wanted[k]], dtype=np.int64)
+    counts = np.zeros(len(out_paths), dtype=np.int64)
+    limit = max(1, ingest.batch_bytes())
+
+    def append(g, data):
+        with open(out_paths[g], 'ab') as f:
+            f.write(data)
+
+    def on_host(stream):
+        # as the host path formats them; what is pending per output goes out at MPN_INGEST_BATCH_BYTES and at the end of the file
+        t0 = time.perf_counter()
+        pending, held = {}, 0
+        for name, comment, seq, qual in iter_fastx_full(stream):
+            groups = wanted.get(name)
+            if groups is None:
+                continue
+            head = name.encode() + ((b' ' + comment) if comment else b'')
+            rec = b'@' + head + b'\n' + seq + b'\n+\n' + qual + b'\n' if qual is not None else b'>' + head + b'\n' + seq + b'\n'
+            for g in groups:
+                pending.setdefault(g, []).append(rec)
+                counts[g] += 1
+            held += len(rec) * len(groups)
+            if held > limit:
+                for g in sorted(pending):
+                    append(g, b''.join(pending[g]))
+                pending, held = {}, 0
+        for g in sorted(pending):
+            append(g, b''.join(pending[g]))
+        tick(timings, 'host', time.perf_counter() - t0)
+
+    with fastq_filter.NameSet([k.encode() for k in names]) as name_set:
+        for path in in_paths:
+            kind, stream, first = open_query(path)
+            try:
+                if kind == 'index':
+                    raise ValueError(f'{path}: a saved index, not sequences')
+                _no_bam(kind, path, 'by nanosplit')
+                if first != b'@':
+                    on_host(stream if kind == 'plain' else gzip_text(stream))
+                    continue
+                if kind == 'bgzf':
+                    texts, rest = ingest._BgzfTexts(stream, device, timings), None
+                else:
+                    rest = stream if kind == 'plain' else gzip_text(stream)
+                    texts = ingest._ChunkTexts(rest, device, timings, 'read' if kind == 'plain' else 'inflate')
+                carry = None
+                while True:
+                    text, text_len, final = texts.next_text(carry)
+                    t0 = time.perf_counter()
+                    rows, consumed, status, ms = ingest.fastq_scan(text, text_len, final)
+                    t1 = time.perf_counter()
+                    tick(timings, 'scan', t1 - t0)
+                    tick(timings, 'scan_device_ms', ms)
+                    tick(timings, 'records', len(rows))
+                    if len(rows):
+                        heads, _ = fastq_filter.fastq_heads(text, text_len, rows, with_ids=False)
+                        t2 = time.perf_counter()
+                        tick(timings, 'heads', t2 - t1)
+                        tick(timings, 'heads_device_ms', fastq_filter.last_filter_device_ms()[0])
+                        found = fastq_filter.fastq_name_lookup(text, text_len, heads, name_set)
+                        t3 = time.perf_counter()
+                        tick(timings, 'lookup', t3 - t2)
+                        tick(timings, 'lookup_device_ms', fastq_filter.last_lookup_device_ms())
+                        plan = split_emit_plan(found, name_ptr, name_out, len(out_paths), heads, rows)
+                        tick(timings, 'plan', time.perf_counter() - t3)
+                        for a, b in emit_rounds(plan.out_off, limit):
+                            t4 = time.perf_counter()
+                            pick = plan.rec[a:b]
+                            d_out, off = fastq_filter.fastq_emit(text, text_len, rows[pick], heads[pick], plan.picks[a:b])
+                            t5 = time.perf_counter()
+                            tick(timings, 'emit', t5 - t4)
+                            tick(timings, 'emit_device_ms', fastq_filter.last_filter_device_ms()[2])
+                            written = d_out[:int(off[-1])].cpu().numpy()
+                            t6 = time.perf_counter()
+                            tick(timings, 'd2h', t6 - t5)
+                            g = int(plan.out[a])
+                            while True:        # the outputs that have pairs in [a, b), ascending
+                                lo, hi = max(a, int(plan.pair_first[g])), min(b, int(plan.pair_first[g + 1]))
+                                append(g, memoryview(written[int(off[lo - a]):int(off[hi - a])]))
+                                counts[g] += hi - lo
+                                if hi == b:
+                                    break
+                                g = int(plan.out[hi])
+                            tick(timings, 'write', time.perf_counter() - t6)
+                    if status == ingest.FASTQ_UNSUPPORTED:
+                        tail = text[consumed:text_len].cpu().numpy().tobytes()
+                        del text, rows, carry
+                        on_host(ingest._TailThenStream(tail, rest if rest is not None else gzip_text(stream)))
+                        break
+                    if status != ingest.OK:
+                        raise RuntimeError(f'mpn_fastq_scan: status {status}')
+                    if final:
+                        break
+                    carry = text[consumed:text_len]
+            finally:
+                stream.close()
+    return [(p, int(c)) for p, c in zip(out_paths, counts)]
+
+
+def nanosplit(read_list_path, in_paths, device=None, timings=None):
     """The reference's bin/tools/nanosplit: every record of in_paths (FASTA / FASTQ, plain or gzip) is written to each output file
     its name is listed for, in the order of the input files and of the records in them; every listed output file is created.
     Names are expanded to record indices here; sequences and qualities are regrouped by mapper.split_reads -- on the GPU, or with
     device=False by the numpy statement of the same plan -- and the files are formatted from the group-contiguous buffers.
+    Under MPN_READ_INGEST=device, unless device is False, the FASTQ text is matched and regrouped where it lies in HBM instead
+    (_nanosplit_device; timings: a dict that receives its stage times); the files are the same.
     -> list of (output path, records written)"""
     from . import mapper
+    if device is not False:
+        from . import ingest
+        if ingest.read_ingest_mode() == 'device':
+            return _nanosplit_device(read_list_path, in_paths, 'cuda' if device in (None, True) else device, timings)
     wanted, out_paths = read_split_list(read_list_path)
     heads, seqs, quals, mem_read, mem_group = [], [], [], [], []
     for path in in_paths:
