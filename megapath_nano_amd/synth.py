@@ -410,3 +410,33 @@ def make_reads_device(seed, genomes_flat, genome_len, n_reads, weights, device, 
         truth = dict(genome=gi.cpu().numpy(), start=start.cpu().numpy(), end=(start + L).cpu().numpy(), rev=rev.cpu().numpy())
         return buf, offs.contiguous(), lens.to(torch.int32).contiguous(), truth
     return buf, offs.contiguous(), lens.to(torch.int32).contiguous()
+
+
+_CIGAR_LETTER = np.frombuffer(b'MID', dtype=np.uint8)
+
+
+def aligned_read(rng, genome, start, length, sub=0.04, ins=0.03, dele=0.05):
+    """A read over genome[start : start + length] WITH its alignment, at the error mix of make_reads (independent per base; no
+    homopolymer bias): -> (CIGAR text of M, I and D runs, bases as bytes).  The first and the last base are matched; an insertion
+    is a geometric number of random bases behind a base.  For the pile-up, whose input is a sorted BAM (candidates.py)."""
+    ref = genome[start:start + length]
+    n = len(ref)
+    gone = rng.random(n) < dele
+    gone[[0, -1]] = False
+    bases = ref.copy()
+    wrong = ~gone & (rng.random(n) < sub)
+    k = int(wrong.sum())
+    bases[wrong] = ALPHA[(np.searchsorted(ALPHA, ref[wrong]) + rng.integers(1, 4, size=k)) % 4]
+    extra = np.where(~gone & (rng.random(n) < ins), rng.geometric(0.5, size=n), 0)
+    extra[-1] = 0
+    slots = 1 + extra                               # per reference base: M or D, then its inserted bases
+    first = np.cumsum(slots) - slots
+    ops = np.ones(int(slots.sum()), dtype=np.uint8)
+    ops[first] = np.where(gone, 2, 0)
+    seq = ALPHA[rng.integers(0, 4, size=len(ops))]
+    seq[first] = bases
+    edge = np.flatnonzero(np.diff(ops)) + 1
+    run_op = ops[np.concatenate([[0], edge])]
+    run_len = np.diff(np.concatenate([[0], edge, [len(ops)]]))
+    cigar = ''.join(f'{l}{chr(_CIGAR_LETTER[o])}' for l, o in zip(run_len.tolist(), run_op.tolist()))
+    return cigar, seq[ops != 2].tobytes()
