@@ -6,7 +6,7 @@
 //                         stable compaction behind the centre's offset of the pair list (count, scan on the host, scatter).
 //   tens_flags_kernel     a wave per (deep centre, read) pair: the wave walks the read's operations 64 at a time
 //                         (tens_wave_ops), the lane whose operation covers the centre decides (tens_flag_op).
-//   tens_fill_kernel      a workgroup per tensor, its 1056 int32 in LDS, a wave per read at a time.  tens_wave_ops gives every
+//   tens_fill_kernel      a workgroup per tensor, its 1056 int32 in LDS, a wave per read at a time.  tens_wave_ops (tensor_wave.h) gives every
 //                         lane the reference and query offset of its operation by two wave scans, skips the steps that end before
 //                         the window and stops at the first that starts behind it; the lanes add what their operation says
 //                         (tens_op: at most 33 positions, or the bases of an insertion) with LDS atomics.  The tile goes to HBM
@@ -16,6 +16,7 @@
 //                         reference slice.
 #include "mpn_common.h"
 #include "tensor_core.h"
+#include "tensor_wave.h"
 
 namespace mpn {
 
@@ -61,42 +62,6 @@ __global__ __launch_bounds__(TENS_THREADS) void tens_join_kernel(const int32_t *
         count += __popcll(vote);
     }
     if (lane == 0) counts[c] = count;
-}
-
-// ---- the walk of a wave over a read ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t tens_scan64(int64_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t u = __shfl_up(v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// f(op, n, r0, q0) in every lane, for the operations of the steps (64 operations each) that can say something about the reference
-// positions from .. to: the steps that end before `from` are skipped, the walk stops at the first that starts behind `to`.  False
-// if an operation code is above 8.  Everything that decides a branch around a shuffle is the same in all lanes of the wave.
-template <class F>
-__device__ __forceinline__ bool tens_wave_ops(const uint8_t *__restrict__ text, const TensLayout &L, int64_t pos, int64_t from, int64_t to, int lane, F f) {
-    int64_t rbase = pos, qbase = 0;
-    bool good = true;
-    for (int32_t k0 = 0; k0 < L.n_cigar && rbase <= to; k0 += 64) {
-        const int32_t k = k0 + lane;
-        uint32_t op = OP_P, n = 0;
-        if (k < L.n_cigar) {
-            const uint32_t w = pile_u32(text, L.cigar + 4 * (int64_t)k);
-            op = w & 15u; n = w >> 4;
-        }
-        if (op > 8) { good = false; op = OP_P; n = 0; }
-        const bool match = pile_is_match(op);
-        const int64_t radv = (match || op == OP_D) ? n : 0, qadv = (match || op == OP_I || op == OP_S) ? n : 0;
-        const int64_t rincl = tens_scan64(radv, lane), qincl = tens_scan64(qadv, lane);
-        const int64_t r0 = rbase + rincl - radv, q0 = qbase + qincl - qadv;
-        rbase += __shfl(rincl, 63);
-        qbase += __shfl(qincl, 63);
-        if (rbase >= from) f(op, (int64_t)n, r0, q0);
-    }
-    return __ballot(!good) == 0ull;
 }
 
 // ---- centre flags --------------------------------------------------------------------------------------------------------------
