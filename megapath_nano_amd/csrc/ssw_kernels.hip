@@ -15,6 +15,7 @@
 // in LDS, horizontal gap state by the same scan; direction codes (1 B/cell) to an HBM scratch;
 // lane 0 walks them back.  The host doubles the band until the DP reproduces the score (ssw.c:555-615).
 #include "mpn_common.h"
+#include "ssw_resident.h"
 #include "../../include/mpn_ssw.h"
 
 #include <stdlib.h>
@@ -555,28 +556,25 @@ static int launch_score(const SswDev &d, const int32_t *order_dev, int count, hi
     return 0;
 }
 
-static int ssw_batch_impl(int32_t n_pairs, const int8_t *reads, const int64_t *read_off, const int32_t *read_len,
-                          const int8_t *refs, const int64_t *ref_off, const int32_t *ref_len, const int8_t *mat,
-                          int32_t n, int8_t score_size, uint8_t gap_open, uint8_t gap_extend, uint8_t flag,
-                          uint16_t filters, int32_t filterd, const int32_t *mask_len, uint16_t *score1,
-                          uint16_t *score2, int32_t *ref_begin1, int32_t *ref_end1, int32_t *read_begin1,
-                          int32_t *read_end1, int32_t *ref_end2, uint32_t *cigar_pool, int64_t cigar_cap,
-                          int64_t *cigar_off, int32_t *cigar_len, int32_t *status) {
+// The core: reads and references are in HBM already (csrc/ssw_resident.h); the results stay there.
+int ssw_resident(int32_t n_pairs, const int8_t *d_reads_p, const int64_t *read_off, const int32_t *read_len, const int8_t *d_refs_p,
+                 const int64_t *ref_off, const int32_t *ref_len, const int8_t *mat, int32_t n, int8_t score_size, uint8_t gap_open,
+                 uint8_t gap_extend, uint8_t flag, uint16_t filters, int32_t filterd, const int32_t *mask_len, SswResident &R) {
+    R.cig_total = 0;
+    R.res_h.clear(); R.status_h.clear(); R.cig_len_h.clear(); R.cig_end_h.clear(); R.launched.clear();
     if (n_pairs <= 0) return 0;
-    if (n < 1 || n > 8) { set_error("mpn_ssw_align_batch: matrix edge n=%d outside 1..8", n); return -2; }
+    if (n < 1 || n > 8) { set_error("ssw: matrix edge n=%d outside 1..8", n); return -2; }
     hipStream_t st = 0;
-    std::vector<int32_t> st_h(n_pairs, MPN_SSW_OK);
-    // total extents of the input buffers
-    int64_t reads_total = 0, refs_total = 0;
+    R.status_h.assign(n_pairs, MPN_SSW_OK);
+    R.cig_len_h.assign(n_pairs, 0);
+    R.launched.assign(n_pairs, 0);
+    std::vector<int32_t> &st_h = R.status_h;
     std::vector<int64_t> mcol_off(n_pairs);
     int64_t mcol_total = 0;
     std::vector<int32_t> cls[5];  // [4]: reads of more than 2048 rows (strip kernel)
     std::vector<int64_t> long_off(n_pairs, 0);
     int64_t long_total = 0;
     for (int i = 0; i < n_pairs; ++i) {
-        cigar_len[i] = 0; cigar_off[i] = 0;
-        reads_total = std::max<int64_t>(reads_total, read_off[i] + std::max(read_len[i], 0));
-        refs_total = std::max<int64_t>(refs_total, ref_off[i] + std::max(ref_len[i], 0));
         mcol_off[i] = mcol_total;
         mcol_total += ((int64_t)std::max(ref_len[i], 0) + 63) / 64 * 64;
         if (gap_open <= gap_extend) st_h[i] = MPN_SSW_EDOMAIN;
@@ -584,6 +582,7 @@ static int ssw_batch_impl(int32_t n_pairs, const int8_t *reads, const int64_t *r
         else if ((int64_t)read_len[i] > 64 * 2048) st_h[i] = MPN_SSW_ETOOLONG;  // (64 strips of 2048 rows)
         else if (score_size < 0 || score_size > 2) st_h[i] = MPN_SSW_ENULL;  // ssw.c:801-804
         else {
+            R.launched[i] = 1;
             int P = (read_len[i] + 15) / 16 * 16;
             cls[P <= 256 ? 0 : P <= 512 ? 1 : P <= 1024 ? 2 : P <= 2048 ? 3 : 4].push_back(i);
             if (P > 2048) { long_off[i] = long_total; long_total += 3 * (int64_t)std::max(ref_len[i], 1); }
@@ -591,18 +590,16 @@ static int ssw_batch_impl(int32_t n_pairs, const int8_t *reads, const int64_t *r
     }
     SswDev d;
     memset(&d, 0, sizeof(d));
-    DevBuf<int8_t> d_reads, d_refs;
-    DevBuf<int64_t> d_read_off, d_ref_off, d_mcol_off;
-    DevBuf<int32_t> d_read_len, d_ref_len, d_mask, d_res, d_order;
-    DevBuf<uint16_t> d_mcol;
-    if (d_reads.upload(reads, reads_total, st) || d_refs.upload(refs, refs_total, st) ||
-        d_read_off.upload(read_off, n_pairs, st) || d_ref_off.upload(ref_off, n_pairs, st) ||
+    DevBuf<int64_t> &d_read_off = R.read_off, &d_ref_off = R.ref_off, &d_mcol_off = R.mcol_off;
+    DevBuf<int32_t> &d_read_len = R.read_len, &d_ref_len = R.ref_len, &d_mask = R.mask, &d_res = R.res, &d_order = R.order;
+    DevBuf<uint16_t> &d_mcol = R.mcol;
+    if (d_read_off.upload(read_off, n_pairs, st) || d_ref_off.upload(ref_off, n_pairs, st) ||
         d_read_len.upload(read_len, n_pairs, st) || d_ref_len.upload(ref_len, n_pairs, st) ||
         d_mask.upload(mask_len, n_pairs, st) || d_mcol_off.upload(mcol_off.data(), n_pairs, st) ||
         d_mcol.alloc(mcol_total) || d_res.alloc((size_t)n_pairs * 9))
         return -1;
     MPN_HIP_CHECK(hipMemsetAsync(d_res.p, 0, (size_t)n_pairs * 9 * sizeof(int32_t), st));
-    d.reads = d_reads.p; d.refs = d_refs.p; d.read_off = d_read_off.p; d.ref_off = d_ref_off.p;
+    d.reads = d_reads_p; d.refs = d_refs_p; d.read_off = d_read_off.p; d.ref_off = d_ref_off.p;
     d.read_len = d_read_len.p; d.ref_len = d_ref_len.p; d.mask_len = d_mask.p;
     memcpy(d.mat, mat, (size_t)n * n);
     d.nsym = n; d.score_size = score_size; d.gapO = gap_open; d.gapE = gap_extend; d.flag = flag;
@@ -633,37 +630,36 @@ static int ssw_batch_impl(int32_t n_pairs, const int8_t *reads, const int64_t *r
                            (const int64_t *)d_long_off.p);
         MPN_HIP_CHECK(hipGetLastError());
     }
-    std::vector<int32_t> res((size_t)n_pairs * 9);
+    R.res_h.assign((size_t)n_pairs * 9, 0);
+    std::vector<int32_t> &res = R.res_h;
     if (d_res.download(res.data(), res.size(), st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
-    const int32_t *h_s1 = &res[0], *h_s2 = &res[n_pairs], *h_rb = &res[2 * (size_t)n_pairs], *h_re = &res[3 * (size_t)n_pairs];
-    const int32_t *h_qb = &res[4 * (size_t)n_pairs], *h_qe = &res[5 * (size_t)n_pairs], *h_re2 = &res[6 * (size_t)n_pairs];
+    const int32_t *h_rb = &res[2 * (size_t)n_pairs], *h_re = &res[3 * (size_t)n_pairs];
+    const int32_t *h_qb = &res[4 * (size_t)n_pairs], *h_qe = &res[5 * (size_t)n_pairs];
     const int32_t *h_st = &res[7 * (size_t)n_pairs], *h_need = &res[8 * (size_t)n_pairs];
     std::vector<int32_t> pending;
-    std::vector<int64_t> cig_end(n_pairs, 0);
+    R.cig_end_h.assign(n_pairs, 0);
+    std::vector<int64_t> &cig_end = R.cig_end_h;
     int64_t cig_total = 0;
     for (int i = 0; i < n_pairs; ++i) {
-        if (st_h[i] != MPN_SSW_OK) {
-            score1[i] = score2[i] = 0; ref_begin1[i] = read_begin1[i] = -1; ref_end1[i] = read_end1[i] = ref_end2[i] = 0;
-            continue;
-        }
+        if (!R.launched[i]) continue;              // (refused before the launch: the kernels left its row at zero)
         st_h[i] = h_st[i];
-        score1[i] = (uint16_t)h_s1[i]; score2[i] = (uint16_t)h_s2[i];
-        ref_begin1[i] = h_rb[i]; ref_end1[i] = h_re[i]; read_begin1[i] = h_qb[i]; read_end1[i] = h_qe[i]; ref_end2[i] = h_re2[i];
         if (h_st[i] == MPN_SSW_OK && h_need[i]) {
             pending.push_back(i);
             cig_total += (int64_t)(h_re[i] - h_rb[i] + 1) + (h_qe[i] - h_qb[i] + 1) + 4;
             cig_end[i] = cig_total;
         }
     }
+    R.cig_total = cig_total;
+    DevBuf<int64_t> &d_cig_end = R.cig_end;
+    DevBuf<uint32_t> &d_cig = R.cig;
+    DevBuf<int32_t> &d_ciglen = R.cig_len;
+    if (d_cig_end.upload(cig_end.data(), n_pairs, st) || d_cig.alloc(cig_total) || d_ciglen.alloc(n_pairs)) return -1;
+    MPN_HIP_CHECK(hipMemsetAsync(d_ciglen.p, 0, (size_t)n_pairs * 4, st));
     if (!pending.empty()) {
-        DevBuf<int64_t> d_cig_end;
-        DevBuf<uint32_t> d_cig;
-        DevBuf<int32_t> d_bmax, d_ciglen;
-        if (d_cig_end.upload(cig_end.data(), n_pairs, st) || d_cig.alloc(cig_total) || d_bmax.alloc(n_pairs) || d_ciglen.alloc(n_pairs))
-            return -1;
+        DevBuf<int32_t> d_bmax;
+        if (d_bmax.alloc(n_pairs)) return -1;
         MPN_HIP_CHECK(hipMemsetAsync(d_bmax.p, 0, (size_t)n_pairs * 4, st));
-        MPN_HIP_CHECK(hipMemsetAsync(d_ciglen.p, 0, (size_t)n_pairs * 4, st));
         std::vector<int32_t> bw(n_pairs, 0);
         for (int i : pending) bw[i] = abs((h_re[i] - h_rb[i] + 1) - (h_qe[i] - h_qb[i] + 1)) + 1;
         for (int round = 0; !pending.empty() && round < 40; ++round) {
@@ -713,17 +709,65 @@ static int ssw_batch_impl(int32_t n_pairs, const int8_t *reads, const int64_t *r
             pending.swap(next);
         }
         for (int i : pending) st_h[i] = MPN_SSW_EUNDEF;  // band never reproduced the score
-        std::vector<uint32_t> cig_h((size_t)cig_total);
-        std::vector<int32_t> cl(n_pairs);
-        if (d_cig.download(cig_h.data(), cig_h.size(), st) || d_ciglen.download(cl.data(), n_pairs, st)) return -1;
+        if (d_ciglen.download(R.cig_len_h.data(), n_pairs, st)) return -1;
         MPN_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    // the final status, for those who read the results on the device
+    MPN_HIP_CHECK(hipMemcpyAsync(d_res.p + 7 * (size_t)n_pairs, st_h.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+static int ssw_batch_impl(int32_t n_pairs, const int8_t *reads, const int64_t *read_off, const int32_t *read_len,
+                          const int8_t *refs, const int64_t *ref_off, const int32_t *ref_len, const int8_t *mat,
+                          int32_t n, int8_t score_size, uint8_t gap_open, uint8_t gap_extend, uint8_t flag,
+                          uint16_t filters, int32_t filterd, const int32_t *mask_len, uint16_t *score1,
+                          uint16_t *score2, int32_t *ref_begin1, int32_t *ref_end1, int32_t *read_begin1,
+                          int32_t *read_end1, int32_t *ref_end2, uint32_t *cigar_pool, int64_t cigar_cap,
+                          int64_t *cigar_off, int32_t *cigar_len, int32_t *status) {
+    if (n_pairs <= 0) return 0;
+    if (n < 1 || n > 8) { set_error("mpn_ssw_align_batch: matrix edge n=%d outside 1..8", n); return -2; }
+    hipStream_t st = 0;
+    // the upload: total extents of the input buffers
+    int64_t reads_total = 0, refs_total = 0;
+    for (int i = 0; i < n_pairs; ++i) {
+        cigar_len[i] = 0; cigar_off[i] = 0;
+        reads_total = std::max<int64_t>(reads_total, read_off[i] + std::max(read_len[i], 0));
+        refs_total = std::max<int64_t>(refs_total, ref_off[i] + std::max(ref_len[i], 0));
+    }
+    DevBuf<int8_t> d_reads, d_refs;
+    if (d_reads.upload(reads, reads_total, st) || d_refs.upload(refs, refs_total, st)) return -1;
+    SswResident R;
+    const int rc = ssw_resident(n_pairs, d_reads.p, read_off, read_len, d_refs.p, ref_off, ref_len, mat, n, score_size, gap_open, gap_extend, flag,
+                                filters, filterd, mask_len, R);
+    if (rc) return rc;
+    const std::vector<int32_t> &res = R.res_h;
+    std::vector<int32_t> &st_h = R.status_h;
+    const int32_t *h_s1 = &res[0], *h_s2 = &res[n_pairs], *h_rb = &res[2 * (size_t)n_pairs], *h_re = &res[3 * (size_t)n_pairs];
+    const int32_t *h_qb = &res[4 * (size_t)n_pairs], *h_qe = &res[5 * (size_t)n_pairs], *h_re2 = &res[6 * (size_t)n_pairs];
+    const int32_t *h_need = &res[8 * (size_t)n_pairs];
+    // a pair that was refused before the launch has no class: the kernels left need_cigar and its row at zero
+    const std::vector<char> &launched = R.launched;
+    for (int i = 0; i < n_pairs; ++i) {
+        if (!launched[i]) {
+            score1[i] = score2[i] = 0; ref_begin1[i] = read_begin1[i] = -1; ref_end1[i] = read_end1[i] = ref_end2[i] = 0;
+            continue;
+        }
+        score1[i] = (uint16_t)h_s1[i]; score2[i] = (uint16_t)h_s2[i];
+        ref_begin1[i] = h_rb[i]; ref_end1[i] = h_re[i]; read_begin1[i] = h_qb[i]; read_end1[i] = h_qe[i]; ref_end2[i] = h_re2[i];
+    }
+    if (R.cig_total > 0) {
+        std::vector<uint32_t> cig_h((size_t)R.cig_total);
+        if (R.cig.download(cig_h.data(), cig_h.size(), st)) return -1;
+        MPN_HIP_CHECK(hipStreamSynchronize(st));
+        const std::vector<int32_t> &cl = R.cig_len_h;
         int64_t used = 0;
         for (int i = 0; i < n_pairs; ++i) {
-            if (st_h[i] != MPN_SSW_OK || !h_need[i] || cl[i] <= 0) continue;
+            if (!launched[i] || st_h[i] != MPN_SSW_OK || !h_need[i] || cl[i] <= 0) continue;
             if (used + cl[i] > cigar_cap) { st_h[i] = MPN_SSW_ECIGAR_CAP; continue; }
             cigar_off[i] = used;
             cigar_len[i] = cl[i];
-            memcpy(cigar_pool + used, &cig_h[(size_t)(cig_end[i] - cl[i])], (size_t)cl[i] * 4);
+            memcpy(cigar_pool + used, &cig_h[(size_t)(R.cig_end_h[i] - cl[i])], (size_t)cl[i] * 4);
             used += cl[i];
         }
     }
