@@ -15,9 +15,9 @@
  * Semantics: minimap2 2.17 `-x map-ont` as restated in oracle/mm2_oracle.c (PARITY UNPINNED: minimap2 is not
  * vendored by the reference; DESIGN.md section 6 lists the deliberate differences).
  *
- * Stage entry points (mpn_sketch_batch, mpn_seed_chain_batch, mpn_chain_batch, mpn_hit_select_batch, mpn_ext_plan_batch,
- * mpn_ext_dp_batch, mpn_stitch_batch, mpn_aln_finish_batch, mpn_aln_tags_batch) exist so that the parity tests can compare every
- * GPU stage with the oracle or a restatement of it; mpn_map_batch is the product call.
+ * Stage entry points (mpn_sketch_batch, mpn_seed_chain_batch, mpn_seed_anchors_batch, mpn_chain_batch, mpn_hit_select_batch,
+ * mpn_ext_plan_batch, mpn_ext_dp_batch, mpn_stitch_batch, mpn_aln_finish_batch, mpn_aln_tags_batch) exist so that the parity tests can
+ * compare every GPU stage with the oracle or a restatement of it; mpn_map_batch is the product call.
  *
  * Difference strings (minimap2 --cs, --cs=long, --MD, --eqx): mpn_map_opt.out_tags.  The strings are made on the GPU when the
  * alignment is finished, because only there are the read, the fixed CIGAR and the packed target together; they are written
@@ -153,6 +153,32 @@ int mpn_seed_chain_batch(const mpn_index *idx, const mpn_map_opt *opt, int32_t n
 int mpn_chain_batch(const mpn_map_opt *opt, int32_t n, const int64_t *anchor_off, const uint64_t *anchors, int32_t chain_item,
                     int32_t bt_par_min, int32_t grid_cap, int32_t *n_chain, int64_t *n_chained, uint64_t *u, int64_t *recs,
                     int64_t u_cap, uint64_t *b, int64_t b_cap);
+
+/* ---- stage: hit lookup, stray-hit filter, anchor emission and anchor sort on a made index and made minimizers (tests) -----------
+ * The first half of mpn_seed_chain_batch (minimap2's mm_collect_matches and the sort behind it), run by the same function with the
+ * same launches, grids and scratch as the mapper's.
+ * The index: k, n_seq targets of lens[] bases, keys[n_keys] strictly ascending below 2^(2k), key_off[n_keys + 1], pos[key_off[n_keys]]
+ * in the index's own layout (rid << 32 | position << 1 | strand, ascending inside a key).  The entry builds a temporary index from
+ * them the way the loader does (the bucket table and the (key, offset) pairs are the mapper's own); no target bases are needed.
+ * The minimizers: read i has mz[mz_off[i] .. mz_off[i + 1]) as (x, y) word pairs in the sketch's layout (x = hash << 8 | span,
+ * y = read << 32 | last_pos << 1 | strand) and seq_len[i] bases.  Nothing is sketched.
+ * Of opt only mid_occ (explicit, 1 .. 2^25), min_cnt and max_gap are read.  flt_round2: 0 = the mapper's value (MPN_FLT_ROUND2, off),
+ * else the hits from which a read is counted twice by the filter; flt_wgs: 0 = the mapper's value (MPN_FLT_WGS, 256), else the
+ * filter's workgroups; grid_cap: 0 = the mapper's grids, else at most that many blocks for every launch that walks its work with a
+ * stride or pulls it from a queue (the scans, the order kernel and the per-read offset kernel are not capped).
+ * Validated on the host before any launch (-1, the message names the entry): offsets that start at 0 and do not decrease; keys
+ * ascending and inside 2k bits; every position inside its target; every minimizer's hash inside 2k bits, span in 1 .. 255 and at
+ * most last_pos + 1, last_pos below seq_len and never decreasing inside a read; mid_occ in 1 .. 2^25; no negative option, knob or
+ * capacity; max_gap <= 66076418 (see mpn_seed_chain_batch).
+ * Out, per read: n_anchor (ALL hits of its minimizers), rep_len, span_sum (the sum of the seed lengths over all hits);
+ * anchor_off[n + 1] and the sorted anchors that passed the stray-hit filter as (x, y) pairs, room for cap; counts[0..2]: the buckets
+ * the sort put on its three work lists (17..1024, 1025..4096, more anchors), counts[3]: the hits the filter walked (every hit in
+ * the first round, a read's survivors in its second).
+ * Returns 0, -3 if cap is too small (everything but the anchors is filled), or -1. */
+int mpn_seed_anchors_batch(int32_t k, int32_t n_seq, const int32_t *lens, int64_t n_keys, const uint64_t *keys, const int64_t *key_off,
+                           const uint64_t *pos, const mpn_map_opt *opt, int32_t n, const int64_t *mz_off, const uint64_t *mz,
+                           const int32_t *seq_len, int64_t flt_round2, int32_t flt_wgs, int32_t grid_cap, int64_t *n_anchor, int32_t *rep_len,
+                           int64_t *span_sum, int64_t *anchor_off, uint64_t *anchors, int64_t cap, int64_t counts[4]);
 
 /* ---- stage: the banded dual-affine extension DP on arbitrary pairs of 0..4 code strings (parity tests) -------
  * flag bits as in ksw2: 0x02 approximate max, 0x08 right-align gaps, 0x40 extension only, 0x80 reversed CIGAR.

@@ -589,7 +589,8 @@ __global__ __launch_bounds__(FLT_THREADS) void seed_filter_kernel(const u128 *__
                                                                   const int32_t *__restrict__ order, FilterParams fp,
                                                                   unsigned long long *__restrict__ keep,
                                                                   int64_t *__restrict__ blk_kept, int32_t *__restrict__ blk_read,
-                                                                  unsigned int *__restrict__ next_read) {
+                                                                  unsigned int *__restrict__ next_read,
+                                                                  unsigned long long *__restrict__ walked) {   // (stage test: hits the second rounds walk, or NULL)
     extern __shared__ uint32_t flt_lds[];
     uint32_t *bm = flt_lds;                                            // [table A1, A2, B1, B2][level][FLT_WORDS]
     // per wave: the block's minimizers that have hits, compacted -- index position of the first hit | parity << 62,
@@ -709,7 +710,10 @@ __global__ __launch_bounds__(FLT_THREADS) void seed_filter_kernel(const u128 *__
                     }
                     __builtin_amdgcn_wave_barrier();
                 }
-                if (!counting && lane == 0) { blk_kept[gb0 + b] = kept; blk_read[gb0 + b] = read; }
+                if (!counting && lane == 0) {
+                    blk_kept[gb0 + b] = kept; blk_read[gb0 + b] = read;
+                    if (walked && pass == 1 && n_pass == 4) atomicAdd(walked, (unsigned long long)kept);
+                }
                 __builtin_amdgcn_wave_barrier();
             }
             __syncthreads();

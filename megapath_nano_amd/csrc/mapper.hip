@@ -5,6 +5,7 @@
 #include "../../include/mpn_map.h"
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <string.h>
 #include <time.h>
@@ -348,6 +349,160 @@ static int chain_enqueue(const mpn_map_opt *opt, int n, int64_t n_a, SeedChainOu
     return 0;
 }
 
+// the tests' knobs of seed_enqueue: 0 = the mapper's own value
+struct SeedKnobs {
+    int64_t flt_round2 = 0;   // hits from which a read is counted twice by the stray-hit filter (MPN_FLT_ROUND2)
+    int flt_wgs = 0;          // workgroups of the stray-hit filter (MPN_FLT_WGS)
+    int grid_cap = 0;         // at most that many blocks for every launch that walks its work with a grid-stride loop or pulls it from a queue
+};
+// the launches' scratch: the caller keeps it until it has waited for the stream.  tmp, read_kept, span_sum and seg_counters are
+// what chain_enqueue takes over; n_list: the three work-list counts of the sort; walked: only where the caller asks for it
+struct SeedScratch {
+    DevBuf<int32_t> occ, blk_read, order;
+    DevBuf<int64_t> pos_start, rel_off, full_off, n_blk, blk_base, blk_kept, blk_off;
+    DevBuf<unsigned long long> span_sum, keep, read_kept, walked;
+    DevBuf<unsigned int> next_read, n_list, seg_counters;
+    DevBuf<u128> tmp;
+    DevBuf<SortSeg> list_mem;
+};
+// The seed half of the stage, for seed_chain_device and for the stage entry mpn_seed_anchors_batch: hit lookup and counting, the
+// stray-hit filter, the emission of the kept hits and their sort, enqueued on st (with the two waits for a total the allocations
+// need).  In: the minimizers of the batch (mz by mz_off, n_mz of them), the reads' lengths on the device (d_len), the occurrence
+// cut-off; o's per-read tables allocated (alloc_chain_tables).  Out: o.n_anchor, o.rep_len, ss.span_sum, o.anchor_off, o.anchors
+// (sorted once the stream has run), *n_a_out; o.used, ss.seg_counters and ss.read_kept zeroed, ss.tmp with room for the anchors,
+// o.n_ends allocated: what chain_enqueue expects.  kn: the tests' knobs, 0 = the mapper's own value; count_walked: the filter adds
+// the hits its second round walks to ss.walked (the stage entry; the mapper passes false and the kernel gets no pointer).
+static int seed_enqueue(const mpn_index *idx, const mpn_map_opt *opt, int32_t mid_occ, int n, const u128 *mz, const int64_t *mz_off, int64_t n_mz,
+                        const int32_t *d_len, SeedChainOut &o, const SeedKnobs &kn, bool count_walked, SeedScratch &ss, int64_t *n_a_out,
+                        StreamLease &st, EvTimer &ev) {
+    auto &[occ, blk_read, order, pos_start, rel_off, full_off, n_blk, blk_base, blk_kept, blk_off, span_sum, keep, read_kept, walked, next_read, n_list,
+           seg_counters, tmp, list_mem] = ss;
+    const auto capped = [&](int64_t grid) { return (int)(kn.grid_cap > 0 ? std::min<int64_t>(grid, kn.grid_cap) : grid); };   // (the mapper: no cap)
+    if (occ.alloc(n_mz) || pos_start.alloc(n_mz) || rel_off.alloc(n_mz) || full_off.alloc((size_t)n + 1) ||
+        n_blk.alloc((size_t)n + 1) || blk_base.alloc((size_t)n + 1) || span_sum.alloc(n) || o.anchor_off.alloc((size_t)n + 1))
+        return -1;
+    if (n_mz > 0) {
+        hipLaunchKernelGGL(seed_lookup_kernel, dim3(capped(grid_1d(n_mz, 256))), dim3(256), 0, st, (const u128 *)idx->kv.p,
+                           idx->n_keys, (const int64_t *)idx->bucket_start.p, idx->bucket_shift, mz, n_mz, mid_occ, occ.p, pos_start.p);
+        MPN_HIP_CHECK(hipGetLastError());
+        ev.mark(11, 35);
+    }
+    hipLaunchKernelGGL(seed_prefix_kernel, dim3(capped(std::max(1, std::min(n, 256 * 32)))), dim3(64), 0, st, mz, mz_off, n, occ.p, rel_off.p,
+                       o.n_anchor.p, o.rep_len.p, span_sum.p, n_blk.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(scan_i64x2_kernel, dim3(2), dim3(1024), 0, st, (const int64_t *)o.n_anchor.p, full_off.p, n, (const int64_t *)n_blk.p, blk_base.p, n);
+    MPN_HIP_CHECK(hipGetLastError());
+    int64_t n_full = 0;  // hits of the batch's minimizers; only those that pass the stray-hit filter become anchors
+    if (read_i64(full_off.p + n, &n_full, st)) return -1;
+    g_stats[2] += n_full;
+    // stray-hit filter: keep words over the virtual hit slots + per-block totals, then the kept hits' offsets
+    const int64_t nb_cap = n_mz / 64 + n + 1;
+    // the counters, cursors and flag arrays of the whole stage are allocated here and zeroed by ONE launch (regions must be sized
+    // in whole 4-byte words: all of them are arrays of 4- or 8-byte items)
+    if (next_read.alloc(4) || order.alloc(n) || keep.alloc((size_t)(n_full / 64 + nb_cap + 8)) || blk_kept.alloc((size_t)nb_cap + 1) || blk_off.alloc((size_t)nb_cap + 2) ||
+        blk_read.alloc((size_t)nb_cap + 1) || n_list.alloc(4) || seg_counters.alloc(4) || read_kept.alloc(n) || (count_walked && walked.alloc(1)))
+        return -1;
+    {
+        ZeroList z{};
+        zero_list_push(z, next_read.p, 4 * sizeof(unsigned int));
+        zero_list_push(z, blk_kept.p, ((size_t)nb_cap + 1) * 8);
+        zero_list_push(z, o.used.p, o.used.n * sizeof(unsigned long long));
+        zero_list_push(z, n_list.p, 4 * sizeof(unsigned int));
+        zero_list_push(z, seg_counters.p, 4 * sizeof(unsigned int));
+        zero_list_push(z, read_kept.p, (size_t)n * 8);
+        if (count_walked) zero_list_push(z, walked.p, 8);
+        MPN_HIP_CHECK(zero_regions(z, st));
+    }
+    if (nb_cap > 0x7fffffff) { set_error("sub-batch too large for the seed filter"); return -1; }
+    if (mid_occ > (1 << 25)) { set_error("occurrence cut-off %d too large (a block of 64 minimizers must hold fewer than 2^32 hits)", mid_occ); return -1; }
+    if (n_full > 0) {
+        FilterParams fp;
+        {
+            const int T = std::max(1, std::min(opt->min_cnt, 3));
+            const int64_t need = 2 * (int64_t)(T - 1) * std::max(opt->max_gap, 1);
+            int sh = 1;
+            while (sh < 32 && ((int64_t)1 << sh) < need) ++sh;
+            fp.shift = sh; fp.half = (uint32_t)((uint64_t)1 << (sh - 1)); fp.level = T - 1;
+            // second round for the reads with at least MPN_FLT_ROUND2 hits.  Off by default: at 20000 it emits 660 M anchors per
+            // bench step instead of 1609 M, but the filter takes 30 % longer and the sort stage only 16 % less: 127 -> 121 Gbp/min
+            // (profiles/r03/r03_filter_round2.txt)
+            static const int64_t round2 = []() { const char *e = getenv("MPN_FLT_ROUND2"); return e ? atoll(e) : INT64_MAX; }();
+            fp.second_round = kn.flt_round2 > 0 ? kn.flt_round2 : round2;
+        }
+        // (set on every call and checked: the call is a table update, and a failure must not be hidden behind a later "invalid value")
+        MPN_HIP_CHECK(hipFuncSetAttribute((const void *)seed_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLT_LDS_BYTES));
+        hipLaunchKernelGGL(seed_order_kernel, dim3(1), dim3(1024), 0, st, (const int64_t *)o.n_anchor.p, n, order.p);
+        static const int flt_wgs_env = []() { const char *e = getenv("MPN_FLT_WGS"); return e ? std::max(1, atoi(e)) : 256; }();
+        const int flt_wgs = kn.flt_wgs > 0 ? kn.flt_wgs : flt_wgs_env;
+        hipLaunchKernelGGL(seed_filter_kernel, dim3(capped(std::max(1, std::min(n, flt_wgs)))), dim3(FLT_THREADS), FLT_LDS_BYTES, st, mz, mz_off, n, occ.p,
+                           pos_start.p, rel_off.p, idx->pos.p, (const int64_t *)full_off.p, (const int64_t *)blk_base.p, (const int32_t *)order.p,
+                           fp, keep.p, blk_kept.p, blk_read.p, next_read.p, count_walked ? walked.p : (unsigned long long *)nullptr);
+        MPN_HIP_CHECK(hipGetLastError());
+        ev.mark(11, 50);
+    }
+    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, blk_kept.p, blk_off.p, (int)nb_cap);
+    hipLaunchKernelGGL(seed_read_off_kernel, dim3((n + 256) / 256), dim3(256), 0, st, (const int64_t *)blk_off.p, (const int64_t *)blk_base.p, n,
+                       o.anchor_off.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    int64_t n_a = 0;
+    if (read_i64(o.anchor_off.p + n, &n_a, st)) return -1;
+    o.n_anchors = n_a;
+    g_stats[51] += n_a;
+    if (o.anchors.alloc(n_a) || tmp.alloc(n_a) || o.n_ends.alloc(n)) return -1;
+    ev.mark(11);
+    if (n_a > 0) {
+        // kept hits in (minimizer, hit) order -> tmp; partition per read on the top key bits -> o.anchors; small buckets are
+        // sorted in LDS, the large ones (true loci) by radix passes with tmp as the bounce buffer
+        hipLaunchKernelGGL(seed_emit_kernel, dim3(capped(grid_1d(nb_cap, 4, 256 * 64))), dim3(256), 0, st, mz, mz_off, occ.p, pos_start.p, rel_off.p,
+                           idx->pos.p, (const int64_t *)full_off.p, (const int64_t *)blk_base.p, n, (const unsigned long long *)keep.p,
+                           (const int64_t *)blk_kept.p, (const int64_t *)blk_off.p, (const int32_t *)blk_read.p, d_len, tmp.p);
+        MPN_HIP_CHECK(hipGetLastError());
+        ev.mark(11, 36);
+        BinParams bp;
+        {
+            int32_t max_len = 1;
+            for (int32_t l : idx->lens) max_len = std::max(max_len, l);
+            int rid_bits = 0, pos_bits = 1;
+            while (((int64_t)1 << rid_bits) < (int64_t)idx->n_seq) ++rid_bits;
+            while (((int64_t)1 << pos_bits) < (int64_t)max_len) ++pos_bits;
+            bp.pos_bits = pos_bits;
+            bp.shift = std::max(0, rid_bits + pos_bits - (MSD_BITS - 1));
+        }
+        // work lists of the buckets that are not sorted in place by the chunk kernel (more than SMALL_BUCKET anchors each)
+        SortLists lists;
+        {
+            const int64_t c0 = n_a / (SMALL_BUCKET + 1) + (int64_t)n + 16, c1 = n_a / (BITONIC_SMALL + 1) + 16, c2 = n_a / (BITONIC_MID + 1) + 16;
+            if (c0 > 0x7fffffff) { set_error("sub-batch too large for the anchor sort"); return -1; }
+            if (list_mem.alloc((size_t)(c0 + c1 + c2))) return -1;
+            lists.seg[0] = list_mem.p; lists.seg[1] = list_mem.p + c0; lists.seg[2] = list_mem.p + c0 + c1;
+            lists.cap[0] = (unsigned int)c0; lists.cap[1] = (unsigned int)c1; lists.cap[2] = (unsigned int)c2;
+            lists.count = n_list.p;
+        }
+        const size_t msd_lds = (size_t)(MSD_NB + 32) * sizeof(uint32_t);
+        MPN_HIP_CHECK(hipFuncSetAttribute((const void *)anchor_msd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)msd_lds));
+        const int gr = capped(std::max(1, std::min(n, 256 * 4)));
+        hipLaunchKernelGGL(anchor_msd_kernel, dim3(gr), dim3(MSD_THREADS), msd_lds, st, (const u128 *)tmp.p, o.anchors.p, (const int64_t *)o.anchor_off.p, n, bp,
+                           lists, o.used.p + 2);
+        MPN_HIP_CHECK(hipGetLastError());
+        ev.mark(12, 47);
+        const int64_t n_win = (n_a + SORT_WIN - 1) / SORT_WIN;
+        hipLaunchKernelGGL(anchor_window_sort_kernel, dim3((unsigned)capped(std::min<int64_t>(n_win, 256 * 64))), dim3(256), 0, st, o.anchors.p,
+                           (const int64_t *)o.anchor_off.p, n, n_a, bp, o.used.p + 2);
+        MPN_HIP_CHECK(hipGetLastError());
+        ev.mark(12, 48);
+        hipLaunchKernelGGL(anchor_bitonic_list_kernel<BITONIC_SMALL>, dim3(capped(256 * 16)), dim3(256), 0, st, o.anchors.p, (const SortSeg *)lists.seg[0],
+                           (const unsigned int *)n_list.p, lists.cap[0], o.used.p + 2);
+        hipLaunchKernelGGL(anchor_bitonic_list_kernel<BITONIC_MID>, dim3(capped(256 * 4)), dim3(256), 0, st, o.anchors.p, (const SortSeg *)lists.seg[1],
+                           (const unsigned int *)n_list.p + 1, lists.cap[1], o.used.p + 2);
+        hipLaunchKernelGGL(seg_sort_list_kernel<4>, dim3(capped(256 * 4)), dim3(256), 0, st, o.anchors.p, tmp.p, (const SortSeg *)lists.seg[2],
+                           (const unsigned int *)n_list.p + 2, lists.cap[2], o.used.p + 2);
+        MPN_HIP_CHECK(hipGetLastError());
+        ev.mark(12, 49);
+    }
+    *n_a_out = n_a;
+    return 0;
+}
+
 // seeds -> sorted anchors -> chains for a batch resident on the device; pre: the batch's sketch if the caller has it (same k, w)
 int seed_chain_device(const mpn_index *idx, const mpn_map_opt *opt, int n, const uint8_t *d_seqs, const int64_t *d_off,
                       const int32_t *d_len, const int32_t *h_len, SeedChainOut &o, StreamLease &st, const ReadSketch *pre) {
@@ -370,139 +525,12 @@ int seed_chain_device(const mpn_index *idx, const mpn_map_opt *opt, int n, const
         const int32_t top = mpn_index_mid_occ(idx, 1e-30f);
         if (top > 0) mid_occ = std::min(mid_occ, top);
     }
-    DevBuf<int32_t> occ;
-    DevBuf<int64_t> pos_start, rel_off, full_off, n_blk, blk_base;
-    DevBuf<unsigned long long> span_sum;
     if (alloc_chain_tables(o, n)) return -1;
-    if (occ.alloc(n_mz) || pos_start.alloc(n_mz) || rel_off.alloc(n_mz) || full_off.alloc((size_t)n + 1) ||
-        n_blk.alloc((size_t)n + 1) || blk_base.alloc((size_t)n + 1) || span_sum.alloc(n) || o.anchor_off.alloc((size_t)n + 1))
-        return -1;
-    if (n_mz > 0) {
-        hipLaunchKernelGGL(seed_lookup_kernel, dim3(grid_1d(n_mz, 256)), dim3(256), 0, st, (const u128 *)idx->kv.p,
-                           idx->n_keys, (const int64_t *)idx->bucket_start.p, idx->bucket_shift, mz.p, n_mz, mid_occ, occ.p, pos_start.p);
-        MPN_HIP_CHECK(hipGetLastError());
-        ev.mark(11, 35);
-    }
-    hipLaunchKernelGGL(seed_prefix_kernel, dim3(std::max(1, std::min(n, 256 * 32))), dim3(64), 0, st, mz.p, mz_off.p, n, occ.p, rel_off.p,
-                       o.n_anchor.p, o.rep_len.p, span_sum.p, n_blk.p);
-    MPN_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(scan_i64x2_kernel, dim3(2), dim3(1024), 0, st, (const int64_t *)o.n_anchor.p, full_off.p, n, (const int64_t *)n_blk.p, blk_base.p, n);
-    MPN_HIP_CHECK(hipGetLastError());
-    int64_t n_full = 0;  // hits of the batch's minimizers; only those that pass the stray-hit filter become anchors
-    if (read_i64(full_off.p + n, &n_full, st)) return -1;
-    g_stats[2] += n_full;
-    // stray-hit filter: keep words over the virtual hit slots + per-block totals, then the kept hits' offsets
-    const int64_t nb_cap = n_mz / 64 + n + 1;
-    DevBuf<unsigned long long> keep;
-    DevBuf<int64_t> blk_kept, blk_off;
-    DevBuf<int32_t> blk_read, order;
-    DevBuf<unsigned int> next_read;
-    // the counters, cursors and flag arrays of the whole stage are allocated here and zeroed by ONE launch (regions must be sized
-    // in whole 4-byte words: all of them are arrays of 4- or 8-byte items)
-    DevBuf<unsigned int> n_list, seg_counters;
-    DevBuf<unsigned long long> read_kept;
-    if (next_read.alloc(4) || order.alloc(n) || keep.alloc((size_t)(n_full / 64 + nb_cap + 8)) || blk_kept.alloc((size_t)nb_cap + 1) || blk_off.alloc((size_t)nb_cap + 2) ||
-        blk_read.alloc((size_t)nb_cap + 1) || n_list.alloc(4) || seg_counters.alloc(4) || read_kept.alloc(n))
-        return -1;
-    {
-        ZeroList z{};
-        zero_list_push(z, next_read.p, 4 * sizeof(unsigned int));
-        zero_list_push(z, blk_kept.p, ((size_t)nb_cap + 1) * 8);
-        zero_list_push(z, o.used.p, o.used.n * sizeof(unsigned long long));
-        zero_list_push(z, n_list.p, 4 * sizeof(unsigned int));
-        zero_list_push(z, seg_counters.p, 4 * sizeof(unsigned int));
-        zero_list_push(z, read_kept.p, (size_t)n * 8);
-        MPN_HIP_CHECK(zero_regions(z, st));
-    }
-    if (nb_cap > 0x7fffffff) { set_error("sub-batch too large for the seed filter"); return -1; }
-    if (mid_occ > (1 << 25)) { set_error("occurrence cut-off %d too large (a block of 64 minimizers must hold fewer than 2^32 hits)", mid_occ); return -1; }
-    if (n_full > 0) {
-        FilterParams fp;
-        {
-            const int T = std::max(1, std::min(opt->min_cnt, 3));
-            const int64_t need = 2 * (int64_t)(T - 1) * std::max(opt->max_gap, 1);
-            int sh = 1;
-            while (sh < 32 && ((int64_t)1 << sh) < need) ++sh;
-            fp.shift = sh; fp.half = (uint32_t)((uint64_t)1 << (sh - 1)); fp.level = T - 1;
-            // second round for the reads with at least MPN_FLT_ROUND2 hits.  Off by default: at 20000 it emits 660 M anchors per
-            // bench step instead of 1609 M, but the filter takes 30 % longer and the sort stage only 16 % less: 127 -> 121 Gbp/min
-            // (profiles/r03/r03_filter_round2.txt)
-            static const int64_t round2 = []() { const char *e = getenv("MPN_FLT_ROUND2"); return e ? atoll(e) : INT64_MAX; }();
-            fp.second_round = round2;
-        }
-        // (set on every call and checked: the call is a table update, and a failure must not be hidden behind a later "invalid value")
-        MPN_HIP_CHECK(hipFuncSetAttribute((const void *)seed_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLT_LDS_BYTES));
-        hipLaunchKernelGGL(seed_order_kernel, dim3(1), dim3(1024), 0, st, (const int64_t *)o.n_anchor.p, n, order.p);
-        static const int flt_wgs = []() { const char *e = getenv("MPN_FLT_WGS"); return e ? std::max(1, atoi(e)) : 256; }();
-        hipLaunchKernelGGL(seed_filter_kernel, dim3(std::max(1, std::min(n, flt_wgs))), dim3(FLT_THREADS), FLT_LDS_BYTES, st, mz.p, mz_off.p, n, occ.p,
-                           pos_start.p, rel_off.p, idx->pos.p, (const int64_t *)full_off.p, (const int64_t *)blk_base.p, (const int32_t *)order.p,
-                           fp, keep.p, blk_kept.p, blk_read.p, next_read.p);
-        MPN_HIP_CHECK(hipGetLastError());
-        ev.mark(11, 50);
-    }
-    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, blk_kept.p, blk_off.p, (int)nb_cap);
-    hipLaunchKernelGGL(seed_read_off_kernel, dim3((n + 256) / 256), dim3(256), 0, st, (const int64_t *)blk_off.p, (const int64_t *)blk_base.p, n,
-                       o.anchor_off.p);
-    MPN_HIP_CHECK(hipGetLastError());
+    SeedScratch ss;
     int64_t n_a = 0;
-    if (read_i64(o.anchor_off.p + n, &n_a, st)) return -1;
-    o.n_anchors = n_a;
-    g_stats[51] += n_a;
-    DevBuf<u128> tmp;
-    if (o.anchors.alloc(n_a) || tmp.alloc(n_a) || o.n_ends.alloc(n)) return -1;
-    ev.mark(11);
-    if (n_a > 0) {
-        // kept hits in (minimizer, hit) order -> tmp; partition per read on the top key bits -> o.anchors; small buckets are
-        // sorted in LDS, the large ones (true loci) by radix passes with tmp as the bounce buffer
-        hipLaunchKernelGGL(seed_emit_kernel, dim3(grid_1d(nb_cap, 4, 256 * 64)), dim3(256), 0, st, mz.p, mz_off.p, occ.p, pos_start.p, rel_off.p,
-                           idx->pos.p, (const int64_t *)full_off.p, (const int64_t *)blk_base.p, n, (const unsigned long long *)keep.p,
-                           (const int64_t *)blk_kept.p, (const int64_t *)blk_off.p, (const int32_t *)blk_read.p, d_len, tmp.p);
-        MPN_HIP_CHECK(hipGetLastError());
-        ev.mark(11, 36);
-        BinParams bp;
-        {
-            int32_t max_len = 1;
-            for (int32_t l : idx->lens) max_len = std::max(max_len, l);
-            int rid_bits = 0, pos_bits = 1;
-            while (((int64_t)1 << rid_bits) < (int64_t)idx->n_seq) ++rid_bits;
-            while (((int64_t)1 << pos_bits) < (int64_t)max_len) ++pos_bits;
-            bp.pos_bits = pos_bits;
-            bp.shift = std::max(0, rid_bits + pos_bits - (MSD_BITS - 1));
-        }
-        // work lists of the buckets that are not sorted in place by the chunk kernel (more than SMALL_BUCKET anchors each)
-        SortLists lists;
-        DevBuf<SortSeg> list_mem;
-        {
-            const int64_t c0 = n_a / (SMALL_BUCKET + 1) + (int64_t)n + 16, c1 = n_a / (BITONIC_SMALL + 1) + 16, c2 = n_a / (BITONIC_MID + 1) + 16;
-            if (c0 > 0x7fffffff) { set_error("sub-batch too large for the anchor sort"); return -1; }
-            if (list_mem.alloc((size_t)(c0 + c1 + c2))) return -1;
-            lists.seg[0] = list_mem.p; lists.seg[1] = list_mem.p + c0; lists.seg[2] = list_mem.p + c0 + c1;
-            lists.cap[0] = (unsigned int)c0; lists.cap[1] = (unsigned int)c1; lists.cap[2] = (unsigned int)c2;
-            lists.count = n_list.p;
-        }
-        const size_t msd_lds = (size_t)(MSD_NB + 32) * sizeof(uint32_t);
-        MPN_HIP_CHECK(hipFuncSetAttribute((const void *)anchor_msd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)msd_lds));
-        const int gr = std::max(1, std::min(n, 256 * 4));
-        hipLaunchKernelGGL(anchor_msd_kernel, dim3(gr), dim3(MSD_THREADS), msd_lds, st, (const u128 *)tmp.p, o.anchors.p, (const int64_t *)o.anchor_off.p, n, bp,
-                           lists, o.used.p + 2);
-        MPN_HIP_CHECK(hipGetLastError());
-        ev.mark(12, 47);
-        const int64_t n_win = (n_a + SORT_WIN - 1) / SORT_WIN;
-        hipLaunchKernelGGL(anchor_window_sort_kernel, dim3((unsigned)std::min<int64_t>(n_win, 256 * 64)), dim3(256), 0, st, o.anchors.p,
-                           (const int64_t *)o.anchor_off.p, n, n_a, bp, o.used.p + 2);
-        MPN_HIP_CHECK(hipGetLastError());
-        ev.mark(12, 48);
-        hipLaunchKernelGGL(anchor_bitonic_list_kernel<BITONIC_SMALL>, dim3(256 * 16), dim3(256), 0, st, o.anchors.p, (const SortSeg *)lists.seg[0],
-                           (const unsigned int *)n_list.p, lists.cap[0], o.used.p + 2);
-        hipLaunchKernelGGL(anchor_bitonic_list_kernel<BITONIC_MID>, dim3(256 * 4), dim3(256), 0, st, o.anchors.p, (const SortSeg *)lists.seg[1],
-                           (const unsigned int *)n_list.p + 1, lists.cap[1], o.used.p + 2);
-        hipLaunchKernelGGL(seg_sort_list_kernel<4>, dim3(256 * 4), dim3(256), 0, st, o.anchors.p, tmp.p, (const SortSeg *)lists.seg[2],
-                           (const unsigned int *)n_list.p + 2, lists.cap[2], o.used.p + 2);
-        MPN_HIP_CHECK(hipGetLastError());
-        ev.mark(12, 49);
-    }
+    if (seed_enqueue(idx, opt, mid_occ, n, mz.p, mz_off.p, n_mz, d_len, o, SeedKnobs{}, false, ss, &n_a, st, ev)) return -1;
     ChainScratch cs;
-    if (chain_enqueue(opt, n, n_a, o, tmp.p, read_kept.p, span_sum.p, seg_counters.p, ChainKnobs{}, cs, st, ev)) return -1;
+    if (chain_enqueue(opt, n, n_a, o, ss.tmp.p, ss.read_kept.p, ss.span_sum.p, ss.seg_counters.p, ChainKnobs{}, cs, st, ev)) return -1;
     ev.mark(14);
     MPN_HIP_CHECK(stream_sync(st));
     ev.resolve();
@@ -1202,6 +1230,72 @@ int mpn_chain_batch(const mpn_map_opt *opt, int32_t n, const int64_t *anchor_off
             q[0] = (int64_t)r.fx; q[1] = (int64_t)r.fy; q[2] = (int64_t)r.lx; q[3] = (int64_t)r.ly; q[4] = r.mlen; q[5] = r.blen;
         }
     }
+    return 0;
+}
+
+// stage entry point for the tests of the seed half: the kernels from the hit lookup to the last sort launch, launched by seed_enqueue
+// as seed_chain_device launches them, on an index and on minimizers of the caller's making.  The index is a temporary mpn_index
+// from index_shell, uploads of the three arrays and build_bucket_table -- what the builder and the loader call -- without packed
+// targets; the minimizers are uploaded as a ReadSketch: nothing is sketched.
+int mpn_seed_anchors_batch(int32_t k, int32_t n_seq, const int32_t *lens, int64_t n_keys, const uint64_t *keys, const int64_t *key_off,
+                           const uint64_t *pos, const mpn_map_opt *opt, int32_t n, const int64_t *mz_off, const uint64_t *mz,
+                           const int32_t *seq_len, int64_t flt_round2, int32_t flt_wgs, int32_t grid_cap, int64_t *n_anchor, int32_t *rep_len,
+                           int64_t *span_sum, int64_t *anchor_off, uint64_t *anchors, int64_t cap, int64_t counts[4]) {
+    const char *who = "mpn_seed_anchors_batch";
+    if (!opt || n < 0) { set_error("%s: options missing or a negative count", who); return -1; }
+    // everything is checked here, before any launch
+    if (!mpn_stage::stage_seed_knobs_ok(who, opt->mid_occ, opt->min_cnt, opt->max_gap, flt_round2, flt_wgs, grid_cap, cap, set_error)) return -1;
+    if (chain_gap_check(opt, who)) return -1;
+    if (!mpn_stage::stage_seed_index_ok(who, k, n_seq, lens, n_keys, keys, key_off, pos, set_error) ||
+        !mpn_stage::stage_seed_mz_ok(who, k, n, mz_off, mz, seq_len, set_error))
+        return -1;
+    if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (n == 0) return 0;
+    if (!n_anchor || !rep_len || !span_sum || !anchor_off || !counts) { set_error("%s: an array missing", who); return -1; }
+    hipStream_t st = 0;
+    memset(g_stats, 0, sizeof(g_stats));
+    std::vector<const char *> names((size_t)n_seq, nullptr);
+    std::unique_ptr<mpn_index> idx(index_shell(n_seq, names.data(), lens, k, 10));
+    if (!idx) return -1;
+    idx->n_keys = n_keys; idx->n_mz = key_off[n_keys];
+    if (idx->keys.upload(keys, (size_t)n_keys, st) || idx->key_off.upload(key_off, (size_t)n_keys + 1, st) || idx->pos.upload(pos, (size_t)idx->n_mz, st) ||
+        build_bucket_table(idx.get(), st))
+        return -1;
+    ReadSketch sk;
+    DevBuf<int32_t> d_len;
+    sk.n_mz = mz_off[n]; sk.k = k; sk.w = 10;
+    if (sk.mz_off.upload(mz_off, (size_t)n + 1, st) || sk.mz.upload(reinterpret_cast<const u128 *>(mz), (size_t)sk.n_mz, st) || d_len.upload(seq_len, (size_t)n, st))
+        return -1;
+    sk.valid = true;
+    g_stats[1] += sk.n_mz;
+    SeedChainOut o;
+    StreamLease sl(st);
+    EvTimer ev(sl);
+    if (alloc_chain_tables(o, n)) return -1;
+    SeedKnobs kn;
+    kn.flt_round2 = flt_round2; kn.flt_wgs = flt_wgs; kn.grid_cap = grid_cap;
+    SeedScratch ss;
+    int64_t n_a = 0;
+    if (seed_enqueue(idx.get(), opt, opt->mid_occ, n, sk.mz.p, sk.mz_off.p, sk.n_mz, d_len.p, o, kn, true, ss, &n_a, sl, ev)) return -1;
+    // (pageable destinations: each copy has completed when it returns, after everything enqueued before it)
+    std::vector<unsigned long long> sums((size_t)n);
+    unsigned int lists[4] = {0, 0, 0, 0};
+    unsigned long long walked = 0;
+    if (o.n_anchor.download(n_anchor, (size_t)n, st) || o.rep_len.download(rep_len, (size_t)n, st) || ss.span_sum.download(sums.data(), (size_t)n, st) ||
+        o.anchor_off.download(anchor_off, (size_t)n + 1, st) || ss.n_list.download(lists, 4, st) || ss.walked.download(&walked, 1, st))
+        return -1;
+    MPN_HIP_CHECK(stream_sync(sl));
+    ev.resolve();
+    for (int i = 0; i < n; ++i) span_sum[i] = (int64_t)sums[(size_t)i];
+    int64_t hits = 0;
+    for (int i = 0; i < n; ++i) hits += n_anchor[i];
+    counts[0] = lists[0]; counts[1] = lists[1]; counts[2] = lists[2];
+    counts[3] = hits + (int64_t)walked;   // every hit is walked by the first round, its survivors by a read's second
+    if (anchor_off[n] != n_a) { set_error("%s: the kernels counted %lld anchors, the offsets end at %lld", who, (long long)n_a, (long long)anchor_off[n]); return -1; }
+    if (n_a > cap) return -3;
+    if (n_a > 0 && !anchors) { set_error("%s: an array missing", who); return -1; }
+    if (o.anchors.download(reinterpret_cast<u128 *>(anchors), (size_t)n_a, st)) return -1;
+    MPN_HIP_CHECK(stream_sync(st));
     return 0;
 }
 

@@ -139,6 +139,9 @@ def _bind():
         lib.mpn_stitch_batch.restype = ct.c_int
         lib.mpn_chain_batch.argtypes = [ct.POINTER(MapOpt), ct.c_int32, P, P, ct.c_int32, ct.c_int32, ct.c_int32, P, P, P, P, ct.c_int64, P, ct.c_int64]
         lib.mpn_chain_batch.restype = ct.c_int
+        lib.mpn_seed_anchors_batch.argtypes = [ct.c_int32, ct.c_int32, P, ct.c_int64, P, P, P, ct.POINTER(MapOpt), ct.c_int32, P, P, P, ct.c_int64,
+                                               ct.c_int32, ct.c_int32, P, P, P, P, P, ct.c_int64, P]
+        lib.mpn_seed_anchors_batch.restype = ct.c_int
         lib.mpn_map_last_stats.argtypes = [P]
         lib.mpn_map_last_stats.restype = None
         lib.mpn_reads_split_plan.argtypes = [ct.c_int32, P, ct.c_int64, P, P, ct.c_int32, ct.c_int64, P, P, P, P, P, P]
@@ -396,6 +399,49 @@ def chain_batch(opt, anchor_off, anchors, chain_item=0, bt_par_min=0, grid_cap=0
     b_off = np.concatenate([[0], np.cumsum(n_chained[:n])])
     return [dict(n_chain=int(n_chain[i]), n_chained=int(n_chained[i]), u=u[c_off[i]:c_off[i + 1]].copy(), b=b[b_off[i]:b_off[i + 1]].copy(),
                  recs=recs[c_off[i]:c_off[i + 1]].copy()) for i in range(n)]
+
+
+def seed_anchors_batch(k, lens, keys, key_off, pos, opt, mz_off, mz, seq_len, flt_round2=0, flt_wgs=0, grid_cap=0, cap=None):
+    """The seed half of the stage on a made index and made minimizers (mpn_seed_anchors_batch): hit lookup, stray-hit filter, emission
+    and sort.  lens: the targets' lengths; keys, key_off, pos: the index as Index.export() gives it; mz_off[n + 1] into mz uint64
+    [total, 2] in the sketch's layout; seq_len[n].  Of opt mid_occ (explicit), min_cnt and max_gap are read.  flt_round2, flt_wgs,
+    grid_cap: 0 = the mapper's values.  cap: room for that many anchors (None: grown as needed; else MpnError -3 if too small, with
+    the partial result as its .partial).  -> (list of dict(n_anchor, rep_len, span_sum, a ((n, 2) uint64)) per read,
+    dict(n_list=(3 counts), walked=hits the filter walked))."""
+    lib = _bind()
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    key_off = np.ascontiguousarray(key_off, dtype=np.int64)
+    pos = np.ascontiguousarray(pos, dtype=np.uint64)
+    mz_off = np.ascontiguousarray(mz_off, dtype=np.int64)
+    mz = np.ascontiguousarray(mz, dtype=np.uint64).reshape(-1, 2)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.int32)
+    n = len(mz_off) - 1
+    assert n >= 0 and len(seq_len) == n and len(key_off) == len(keys) + 1
+    n_anchor = np.zeros(n + 1, dtype=np.int64)
+    rep_len = np.zeros(n + 1, dtype=np.int32)
+    span_sum = np.zeros(n + 1, dtype=np.int64)
+    anchor_off = np.zeros(n + 1, dtype=np.int64)
+    counts = np.zeros(4, dtype=np.int64)
+    a_cap = (1 << 16) if cap is None else int(cap)
+    while True:
+        a = np.zeros((max(a_cap, 1), 2), dtype=np.uint64)
+        rc = lib.mpn_seed_anchors_batch(int(k), len(lens), lens.ctypes.data, len(keys), keys.ctypes.data, key_off.ctypes.data, pos.ctypes.data,
+                                        ct.byref(opt), n, mz_off.ctypes.data, mz.ctypes.data, seq_len.ctypes.data, int(flt_round2), int(flt_wgs),
+                                        int(grid_cap), n_anchor.ctypes.data, rep_len.ctypes.data, span_sum.ctypes.data, anchor_off.ctypes.data,
+                                        a.ctypes.data, a_cap, counts.ctypes.data)
+        if rc == -3 and cap is None:
+            a_cap = int(anchor_off[n]) + 1
+            continue
+        if rc == -3:
+            e = _ffi.MpnError('mpn_seed_anchors_batch rc=-3: room for %d anchors, %d needed' % (a_cap, int(anchor_off[n])))
+            e.partial = dict(n_anchor=n_anchor[:n].copy(), anchor_off=anchor_off.copy())
+            raise e
+        _ffi.check(rc, 'mpn_seed_anchors_batch')
+        break
+    reads = [dict(n_anchor=int(n_anchor[i]), rep_len=int(rep_len[i]), span_sum=int(span_sum[i]), a=a[anchor_off[i]:anchor_off[i + 1]].copy())
+             for i in range(n)]
+    return reads, dict(n_list=tuple(int(v) for v in counts[:3]), walked=int(counts[3]))
 
 
 def map_batch(idx, opt, names, seqs):
