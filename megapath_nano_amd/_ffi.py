@@ -39,5 +39,18 @@ def hint(msg):
 
 
 def check(rc, what):
+    """what: the native entry's name.  MpnError with its return code and the library's error text for rc != 0."""
     if rc != 0:
         raise MpnError(f'{what} failed (rc={rc}): {hint(last_error())}')
+
+
+def ptr(a):
+    """the address of a numpy array's data; None (a NULL pointer) for None or an empty array"""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def device_ms(fn, n):
+    """fn: a native mpn_*_last_device_ms entry that fills n doubles -> their tuple"""
+    v = [ct.c_double(0) for _ in range(n)]
+    fn(*[ct.byref(x) for x in v])
+    return tuple(x.value for x in v)

@@ -6,8 +6,9 @@ reference that are reproduced and the differences are DESIGN.md section 6; the n
     extract_variant_candidates(bam_fn, ref_fn, ..) -> writes the reference's lines
     bin/mpn-candidates                             the command line of the reference script
 
-The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) through ingest._BgzfTexts and ingest.bam_walk, as read input does: the
-file is never whole in host memory and no .bai is read.  What is taken -- flags, contig, MAPQ, the 0.55 soft-clip test in numpy
+The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) through ingest.BamTexts, as read input does: the file is never whole
+in host memory and no .bai is read.  What the stages that read a sorted BAM share is here too: contig_tid, contig_records,
+check_ascending.  What is taken -- flags, contig, MAPQ, the 0.55 soft-clip test in numpy
 float64, the first-of-POS rule for leading insertions and deletions -- is decided here from the per-record table of
 mpn_pileup_records; the counters and the decision per position stay on the device."""
 import collections
@@ -58,21 +59,14 @@ def _lib():
 
 def last_device_ms():
     """-> (records ms, counts ms, candidates ms) of the calling thread's last native calls"""
-    v = [ct.c_double(0) for _ in range(3)]
-    _lib().mpn_pileup_last_device_ms(*[ct.byref(x) for x in v])
-    return tuple(x.value for x in v)
-
-
-def _check(rc, what):
-    if rc:
-        raise _ffi.MpnError(f'{what} rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    return _ffi.device_ms(_lib().mpn_pileup_last_device_ms, 3)
 
 
 def pileup_records(text, text_len, rows):
     """mpn_pileup_records on rows of ingest.bam_walk -> a PILE_REC array"""
     rows = np.ascontiguousarray(rows, dtype=ingest.BAM_ROW)
     recs = np.zeros(len(rows), dtype=PILE_REC)
-    _check(_lib().mpn_pileup_records(text.data_ptr(), int(text_len), len(rows), ingest._ptr(rows), ingest._ptr(recs)), 'mpn_pileup_records')
+    _ffi.check(_lib().mpn_pileup_records(text.data_ptr(), int(text_len), len(rows), _ffi.ptr(rows), _ffi.ptr(recs)), 'mpn_pileup_records')
     return recs
 
 
@@ -82,7 +76,7 @@ def pileup_counts(text, text_len, takes, span, lo, hi, counts, slice_records=0):
     span = np.ascontiguousarray(span, dtype=np.int64)
     assert counts.is_contiguous() and counts.numel() == (hi - lo) * SLOTS and len(span) == len(takes)
     bad, sliced = ct.c_int64(-1), ct.c_int64(0)
-    _check(_lib().mpn_pileup_counts(text.data_ptr(), int(text_len), len(takes), ingest._ptr(takes), ingest._ptr(span), int(lo), int(hi), int(slice_records),
+    _ffi.check(_lib().mpn_pileup_counts(text.data_ptr(), int(text_len), len(takes), _ffi.ptr(takes), _ffi.ptr(span), int(lo), int(hi), int(slice_records),
                                     counts.data_ptr(), ct.byref(bad), ct.byref(sliced)), 'mpn_pileup_counts')
     return bad.value, sliced.value
 
@@ -101,12 +95,12 @@ def pileup_candidates(counts, lo, ref_bytes, bed, min_coverage, threshold):
     cap, n = 1 << 16, ct.c_int64(0)
     while True:
         rows = np.zeros(cap, dtype=PILE_CAND)
-        rc = lib.mpn_pileup_candidates(counts.data_ptr(), int(lo), n_pos, ingest._ptr(ref_bytes), n_bed, None if n_bed < 1 else bs.ctypes.data,
+        rc = lib.mpn_pileup_candidates(counts.data_ptr(), int(lo), n_pos, _ffi.ptr(ref_bytes), n_bed, None if n_bed < 1 else bs.ctypes.data,
                                        None if n_bed < 1 else be.ctypes.data, float(min_coverage), float(threshold), cap, rows.ctypes.data, ct.byref(n))
         if rc == -3 and n.value > cap:
             cap = n.value
             continue
-        _check(rc, 'mpn_pileup_candidates')
+        _ffi.check(rc, 'mpn_pileup_candidates')
         return rows[:n.value]
 
 
@@ -127,7 +121,36 @@ def bam_references(path):
     return out
 
 
-Pileup = collections.namedtuple('Pileup', 'lo hi counts n_taken n_records sliced_tiles')
+def contig_tid(bam, ctg_name):
+    """-> (the reference id the records of ctg_name carry in `bam`; -2 if its header has no such contig, which no record has; the
+    contig's length by the header, 0 then)"""
+    refs = bam_references(bam)
+    names = [n for n, _ in refs]
+    tid = names.index(ctg_name) if ctg_name in names else -2
+    return tid, (refs[tid][1] if tid >= 0 else 0)
+
+
+def contig_records(t, tid, filter_flag=FILTER_FLAG):
+    """t: an ingest.BamText -> (keep, recs): the indices into t.rows of the records that pass the flag filter and lie on the contig
+    `tid`, and their PILE_REC.  The records that pass the filter all go through mpn_pileup_records."""
+    keep = np.flatnonzero((t.rows['flag'] & filter_flag) == 0)
+    recs = pileup_records(t.text, t.text_len, t.rows[keep])
+    on = np.flatnonzero(recs['ref_id'] == tid)
+    return keep[on], recs.take(on)           # (take: a structured array indexed with [] is copied field by field)
+
+
+def check_ascending(pos, last_pos, message):
+    """pos: the positions of records in file order (int64); last_pos: the position before them, None at the start of the file.
+    ValueError(message(i)) for the first record i that lies before its predecessor -> the last position"""
+    if not len(pos):
+        return last_pos
+    down = np.flatnonzero(np.diff(pos, prepend=pos[0] if last_pos is None else last_pos) < 0)
+    if len(down):
+        raise ValueError(message(int(down[0])))
+    return int(pos[-1])
+
+
+Pileup =collections.namedtuple('Pileup', 'lo hi counts n_taken n_records sliced_tiles')
 
 
 def _record_name(text, row):
@@ -151,43 +174,20 @@ def pileup(bam, ctg_name, ctg_start=None, ctg_end=None, min_mq=0, device='cuda',
     import torch
     device = device or 'cuda'
     _lib()
-    refs = bam_references(bam)
-    names = [n for n, _ in refs]
-    tid = names.index(ctg_name) if ctg_name in names else -2       # (-2: no record has it)
-    length = max(refs[tid][1] if tid >= 0 else 0, int(ctg_len or 0), 0)
-    lo, hi = _window(ctg_start, ctg_end, length)
+    tid, length = contig_tid(bam, ctg_name)
+    lo, hi = _window(ctg_start, ctg_end, max(length, int(ctg_len or 0), 0))
     counts = torch.zeros((hi - lo, SLOTS), dtype=torch.int32, device=device)
-    walk_records = max(1, ingest.bam_walk_records())
     n_taken = n_records = sliced_tiles = 0
     last_pos = None
-    with io.BufferedReader(open(bam, 'rb', buffering=0), buffer_size=1 << 20) as stream:
-        texts = ingest._BgzfTexts(stream, device, timings)
-        carry, at_header, text_base = None, True, 0
-        while True:
-            text, text_len, final = texts.next_text(carry)
-            del carry
-            t0 = time.perf_counter()
-            start, got = 0, []
-            while True:
-                rows, nxt, st = ingest.bam_walk(text, text_len, start, at_header, final, walk_records)
-                ingest._tick(timings, 'walk_device_ms', ingest.last_bam_device_ms()[1])
-                if st != ingest.OK:
-                    raise ValueError(f'BAM text at offset {text_base + nxt} of the inflated stream: {ingest.STATUS_NAMES[st]}')
-                if at_header and nxt > start:
-                    at_header = False
-                got.append(rows)
-                start = nxt
-                if len(rows) < walk_records:
-                    break
-            rows = np.concatenate(got)
-            n_records += len(rows)
+    with ingest.BamTexts(bam, device, timings) as texts:
+        for t in texts:
+            text, text_len = t.text, t.text_len
+            n_records += len(t.rows)
             t1 = time.perf_counter()
-            ingest._tick(timings, 'walk', t1 - t0)
-            rows = rows[(rows['flag'] & FILTER_FLAG) == 0]
-            recs = pileup_records(text, text_len, rows)
+            on, recs = contig_records(t, tid)
             ingest._tick(timings, 'records_device_ms', last_device_ms()[0])
-            keep = (recs['ref_id'] == tid) & (recs['mapq'] >= min_mq) & (recs['n_cigar'] > 0)
-            rows, recs = rows[keep], recs[keep]
+            keep = np.flatnonzero((recs['mapq'] >= min_mq) & (recs['n_cigar'] > 0))
+            rows, recs = t.rows.take(on[keep]), recs.take(keep)
             bad = np.flatnonzero((recs['status'] != OK) & (recs['status'] != NO_BASE))
             if len(bad):
                 b = int(bad[0])
@@ -202,25 +202,19 @@ def pileup(bam, ctg_name, ctg_start=None, ctg_end=None, min_mq=0, device='cuda',
             ingest._tick(timings, 'records', t2 - t1)
             if len(rows):
                 pos = recs['pos'].astype(np.int64)
-                before = np.concatenate([[pos[0] - 1 if last_pos is None else last_pos], pos[:-1]])
-                down = np.flatnonzero(pos < before)
-                if len(down):
-                    raise ValueError(f'{bam}: record {_record_name(text, rows[int(down[0])])}: the records that are taken are not sorted by position')
+                lead = np.diff(pos, prepend=pos[0] - 1 if last_pos is None else last_pos) > 0        # the first taken record of its POS
+                last_pos = check_ascending(pos, last_pos, lambda i: f'{bam}: record {_record_name(text, rows[i])}: the records that are taken are not '
+                                           'sorted by position')
                 takes = np.zeros(len(rows), dtype=PILE_TAKE)
-                takes['off'], takes['pos'], takes['lead'] = rows['off'], recs['pos'], pos > before
+                takes['off'], takes['pos'], takes['lead'] = rows['off'], recs['pos'], lead
                 bad_row, sliced = pileup_counts(text, text_len, takes, recs['span'], lo, hi, counts, slice_records)
                 ingest._tick(timings, 'counts_device_ms', last_device_ms()[1])
                 if bad_row >= 0:
                     raise ValueError(f'{bam}: record {_record_name(text, rows[bad_row])}: base code 0 (=) or no base under a matched stretch '
                                      '(the reference script raises there)')
-                last_pos = int(pos[-1])
                 n_taken += len(rows)
                 sliced_tiles += sliced
             ingest._tick(timings, 'counts', time.perf_counter() - t2)
-            if final:
-                break
-            carry = text[start:text_len]
-            text_base += start
     return Pileup(lo, hi, counts, n_taken, n_records, sliced_tiles)
 
 

@@ -9,7 +9,8 @@ reproduced and the differences are DESIGN.md section 6 item 19; the native calls
     vcf_header(sample_name, ref_fn)                                  the reference's header; ##contig from the FASTA itself
     bin/mpn-call-vcf                                                 the command line of the reference script
 
-The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) exactly as clair_tensor._run does it; no pysam, .bai or .fai is used.
+The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) through ingest.BamTexts, each text beginning at the first record that an
+unfinished site still needs (keep_from); no pysam, .bai or .fai is used.
 The device gives, per record, the alleles, the genotype, the float32 product p and the integer counts; the host keeps what hangs on
 libm and printf: the quality from p (math.log in float64, as NumPy 1.x promotes `1.0 - p`), `%.4f` of the allele frequency
 (float64, capped at 1), PASS / LowQual and the line."""
@@ -22,7 +23,8 @@ import ctypes as ct
 
 import numpy as np
 
-from . import candidates, clair_tensor, fastx, ingest
+from . import _ffi, candidates, clair_tensor, fastx, ingest
+from ._ffi import check as _check, ptr as _p
 
 FLANK, CELLS, PROBS, REF_BYTES = 16, 1056, 90, 33
 MAX_LEN, MAX_EVENTS, ALLELE_BYTES, ALT1_AT, ALT2_AT = 50, 256, 256, 51, 152
@@ -68,13 +70,7 @@ def _lib():
 
 def last_device_ms():
     """-> (indels ms, decode ms, quantize ms) of the calling thread's last native calls"""
-    v = [ct.c_double(0) for _ in range(3)]
-    _lib().mpn_call_last_device_ms(*[ct.byref(x) for x in v])
-    return tuple(x.value for x in v)
-
-
-_check = candidates._check
-_p = clair_tensor._p
+    return _ffi.device_ms(_lib().mpn_call_last_device_ms, 3)
 
 
 class Events:
@@ -156,41 +152,14 @@ def indel_events(bam_fn, ctg_name, positions, contig_len, device='cuda', timings
     sites = np.asarray(positions, dtype=np.int64).reshape(-1)
     if len(sites) and (bool((sites[1:] <= sites[:-1]).any()) or int(sites[0]) < 1 or int(sites[-1]) > 0x7ffffff0):
         raise ValueError('the sites are not ascending 1-based positions')
-    refs = candidates.bam_references(bam_fn)
-    names = [n for n, _ in refs]
-    tid = names.index(ctg_name) if ctg_name in names else -2
-    walk_records = max(1, ingest.bam_walk_records())
+    tid, _ = candidates.contig_tid(bam_fn, ctg_name)
     next_site, last_pos = 0, None
     offs, evs, bss = [np.zeros(1, dtype=np.int64)], [], []
-    resident = dict() if timings is not None else None
-    with io.BufferedReader(open(bam_fn, 'rb', buffering=0), buffer_size=1 << 20) as stream:
-        texts = ingest._BgzfTexts(stream, device, resident)
-        carry, at_header = None, True
+    with ingest.BamTexts(bam_fn, device) as texts:
         while next_site < len(sites):
-            text, text_len, final = texts.next_text(carry)
-            del carry
-            start, got = 0, []
-            while True:
-                rows, nxt, st = ingest.bam_walk(text, text_len, start, at_header, final, walk_records)
-                if st != ingest.OK:
-                    raise ValueError(f'{bam_fn}: BAM text: {ingest.STATUS_NAMES[st]}')
-                if at_header and nxt > start:
-                    at_header = False
-                got.append(rows)
-                start = nxt
-                if len(rows) < walk_records:
-                    break
-            rows = np.concatenate(got)
-            keep = np.flatnonzero((rows['flag'] & candidates.FILTER_FLAG) == 0)
-            recs = candidates.pileup_records(text, text_len, rows[keep])
-            on = np.flatnonzero(recs['ref_id'] == tid)
-            keep, recs = keep[on], recs[on]
-            trecs = clair_tensor.tensor_records(text, text_len, rows[keep])
-            pos, rlen = recs['pos'].astype(np.int64), trecs['hts_len'].astype(np.int64)
-            if len(pos):
-                if bool((pos[1:] < pos[:-1]).any()) or (last_pos is not None and int(pos[0]) < last_pos):
-                    raise ValueError(f'{bam_fn}: the records of {ctg_name} are not sorted by position')
-                last_pos = int(pos[-1])
+            t = next(texts)
+            text, text_len, rows, final = t.text, t.text_len, t.rows, t.final
+            keep, pos, rlen, last_pos = clair_tensor.contig_reads(t, tid, last_pos, f'{bam_fn}: the records of {ctg_name} are not sorted by position')
             todo = sites[next_site:]
             n_fin = len(todo) if final else (int(np.searchsorted(todo, int(pos[-1]), side='left')) if len(pos) else 0)
             if n_fin:
@@ -217,7 +186,7 @@ def indel_events(bam_fn, ctg_name, positions, contig_len, device='cuda', timings
                 if b < len(keep):
                     cut = int(keep[b])
                     last_pos = int(pos[b])                # the next text starts again at this record
-            carry = text[int(rows['off'][cut]) if cut < len(rows) else start:text_len]
+            texts.keep_from(cut)
     off = np.concatenate(offs)
     if len(off) < len(sites) + 1:                      # (the file ended before the last sites)
         off = np.concatenate([off, np.full(len(sites) + 1 - len(off), off[-1], dtype=np.int64)])

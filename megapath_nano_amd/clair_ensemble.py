@@ -22,6 +22,7 @@ import ctypes as ct
 import numpy as np
 
 from . import candidates, clair_call, clair_tensor, ingest
+from ._ffi import check as _check, ptr as _p
 
 CELLS, PROBS = 1056, 90
 COLUMNS = 3 + CELLS + PROBS
@@ -47,10 +48,6 @@ def last_device_ms():
     v = ct.c_double(0)
     _lib().mpn_clair_ensemble_last_device_ms(ct.byref(v))
     return v.value
-
-
-_check = candidates._check
-_p = clair_tensor._p
 
 
 # ---- the grouping -------------------------------------------------------------------------------------------------------------------

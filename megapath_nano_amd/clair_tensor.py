@@ -7,7 +7,8 @@ differences are DESIGN.md section 6; the native calls are include/mpn_tensor.h.
     create_tensor(bam_fn, ref_fn, can, ctg_name, ..)  -> writes the reference's lines
     bin/mpn-create-tensor                             the command line of the reference script
 
-The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) exactly as candidates.pileup does it; no samtools, .bai or .fai is used.
+The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) through ingest.BamTexts, each text beginning at the first record that an
+unfinished centre still needs (keep_from); no samtools, .bai or .fai is used.
 The host decides what is taken (flags, contig, htslib's overlap with the region, MAPQ, the dcov run), bisects a range of records
 for every centre, builds the Python set of a deep centre and draws from `rng` in the reference's order; the join, the centre flags,
 the tensors and the text of the lines are made on the device."""
@@ -20,7 +21,8 @@ import ctypes as ct
 
 import numpy as np
 
-from . import candidates, ingest
+from . import _ffi, candidates, ingest
+from ._ffi import check as _check, ptr as _p
 
 FLANK = 16
 POSITIONS, ROWS, CHANNELS, CELLS = 33, 8, 4, 1056
@@ -55,16 +57,7 @@ def _lib():
 
 def last_device_ms():
     """-> (join ms, flags ms, fill ms, emit ms) of the calling thread's last native calls"""
-    v = [ct.c_double(0) for _ in range(4)]
-    _lib().mpn_tensor_last_device_ms(*[ct.byref(x) for x in v])
-    return tuple(x.value for x in v)
-
-
-_check = candidates._check
-
-
-def _p(a):
-    return a.ctypes.data if a is not None and len(a) else None
+    return _ffi.device_ms(_lib().mpn_tensor_last_device_ms, 4)
 
 
 # ---- the native calls ---------------------------------------------------------------------------------------------------------------
@@ -228,6 +221,16 @@ def reference_window(seq, ctg_start=None, ctg_end=None):
     return seq, 0
 
 
+def contig_reads(t, tid, last_pos, unsorted, filter_flag=candidates.FILTER_FLAG):
+    """What the stages that pile up columns (clair_call, local_realign) take of the text t (an ingest.BamText): every record of the
+    contig `tid` that passes the flag filter -> (keep: their indices into t.rows, pos, rlen: htslib's length on the reference, the
+    last position).  ValueError(unsorted) if they do not ascend from last_pos on."""
+    keep, recs = candidates.contig_records(t, tid, filter_flag)
+    trecs = tensor_records(t.text, t.text_len, t.rows[keep])
+    pos = recs['pos'].astype(np.int64)
+    return keep, pos, trecs['hts_len'].astype(np.int64), candidates.check_ascending(pos, last_pos, lambda i: unsorted)
+
+
 def _run(bam_fn, ref_fn, can, ctg_name, ctg_start, ctg_end, min_mq, dcov, min_coverage, left_edge, rng, device, timings, sink):
     """The whole stage.  sink(block, centres, ref_off, ref_n, d_ref, window) per text with tensors to give: block is a
     (k, 1056) int32 tensor on the device, centres (1-based), ref_off and ref_n numpy arrays of k entries."""
@@ -244,63 +247,37 @@ def _run(bam_fn, ref_fn, can, ctg_name, ctg_start, ctg_end, min_mq, dcov, min_co
     d_ref = torch.from_numpy(np.frombuffer(window, dtype=np.uint8).copy()).to(device)
     centres = read_positions(can, ctg_start, ctg_end)
     ingest._tick(timings, 'reference', time.perf_counter() - t0)
-    refs = candidates.bam_references(bam_fn)
-    names = [n for n, _ in refs]
-    tid = names.index(ctg_name) if ctg_name in names else -2
-    walk_records = max(1, ingest.bam_walk_records())
+    tid, _ = candidates.contig_tid(bam_fn, ctg_name)
     next_centre, kept_take, state, last_pos = 0, np.zeros(0, dtype=bool), (0, 0), None
     resident = dict() if timings is not None else None
-    with io.BufferedReader(open(bam_fn, 'rb', buffering=0), buffer_size=1 << 20) as stream:
-        texts = ingest._BgzfTexts(stream, device, resident)
-        carry, at_header = None, True
+    with ingest.BamTexts(bam_fn, device, resident) as texts:
         while True:
             t0 = time.perf_counter()
-            text, text_len, final = texts.next_text(carry)
-            del carry
-            start, got = 0, []
-            while True:
-                rows, nxt, st = ingest.bam_walk(text, text_len, start, at_header, final, walk_records)
-                if st != ingest.OK:
-                    raise ValueError(f'{bam_fn}: BAM text: {ingest.STATUS_NAMES[st]}')
-                if at_header and nxt > start:
-                    at_header = False
-                got.append(rows)
-                start = nxt
-                if len(rows) < walk_records:
-                    break
-            rows = np.concatenate(got)
+            t = next(texts)
+            text, text_len, rows, final = t.text, t.text_len, t.rows, t.final
             n_old = len(kept_take)
             if len(rows) < n_old:
                 raise ValueError(f'{bam_fn}: the records of a text were not found again in the next')
-            # ---- what is taken: the records of the text that pass the flag get their facts; the new ones their decision
-            keep_f = np.flatnonzero((rows['flag'] & candidates.FILTER_FLAG) == 0)
+            # ---- what is taken: the records of the contig that pass the flag get their facts; the new ones their decision
+            keep_f, recs = candidates.contig_records(t, tid)
             rows_f = rows[keep_f]
-            recs = candidates.pileup_records(text, text_len, rows_f)
             trecs = tensor_records(text, text_len, rows_f)
             t1 = time.perf_counter()
             ingest._tick(timings, 'resident', t1 - t0)
-            view = recs['ref_id'] == tid
+            walked = recs['mapq'] >= min_mq
             if region:
                 pos64 = recs['pos'].astype(np.int64)
-                view &= (pos64 < int(ctg_end)) & (pos64 + np.maximum(trecs['hts_len'], 1) > int(ctg_start) - 1)
-            walked = view & (recs['mapq'] >= min_mq)
+                walked &= (pos64 < int(ctg_end)) & (pos64 + np.maximum(trecs['hts_len'], 1) > int(ctg_start) - 1)
             new = keep_f >= n_old
             for bad in np.flatnonzero(walked & new & ((recs['status'] == candidates.PLACEHOLDER) | (recs['status'] == candidates.CIGAR_PAST) |
                                                       (recs['status'] == candidates.BAD_OP) | (trecs['status'] == candidates.CIGAR_PAST)))[:1]:
                 status = int(recs['status'][bad]) or int(trecs['status'][bad])
                 raise ValueError(f'{bam_fn}: record {candidates._record_name(text, rows_f[bad])}: {candidates.STATUS_TEXT[status]}')
             wn = np.flatnonzero(walked & new)
-            if len(wn):
-                p = recs['pos'][wn].astype(np.int64)
-                before = np.concatenate([[p[0] if last_pos is None else last_pos], p[:-1]])
-                down = np.flatnonzero(p < before)
-                if len(down):
-                    raise ValueError(f'{bam_fn}: record {candidates._record_name(text, rows_f[wn[int(down[0])]])}: the records that are taken are '
-                                     'not sorted by position')
-                last_pos = int(p[-1])
-                took, state = dcov_run(p, dcov, state)
-            else:
-                took = np.zeros(0, dtype=bool)
+            p = recs['pos'][wn].astype(np.int64)
+            last_pos = candidates.check_ascending(p, last_pos, lambda i: f'{bam_fn}: record {candidates._record_name(text, rows_f[wn[i]])}: the records '
+                                                  'that are taken are not sorted by position')
+            took, state = dcov_run(p, dcov, state)
             take_all = np.zeros(len(rows), dtype=bool)
             take_all[:n_old] = kept_take
             take_all[keep_f[wn]] = took
@@ -316,14 +293,14 @@ def _run(bam_fn, ref_fn, can, ctg_name, ctg_start, ctg_end, min_mq, dcov, min_co
             next_centre += n_fin
             if final:
                 break
-            # ---- the carry starts at the first record that an unfinished centre still needs
+            # ---- the next text starts at the first record that an unfinished centre still needs
             cut = len(rows)
             if next_centre < len(centres) and len(ti):
                 b = int(join_ranges(pos, span, centres[next_centre:next_centre + 1], left_edge)[0][0])
                 if b < len(ti):
                     cut = int(keep_f[ti[b]])
             kept_take = take_all[cut:].copy()
-            carry = text[int(rows['off'][cut]) if cut < len(rows) else start:text_len]
+            texts.keep_from(cut)
     if timings is not None:
         for key in ('read', 'h2d', 'inflate', 'flatten'):
             timings[key] = resident.get(key, 0)

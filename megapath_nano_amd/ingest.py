@@ -18,7 +18,8 @@ of this module):
       --mpn_bam_flatten--> one text --mpn_bam_walk--> record table --(skip 0x900, cut batches like aligner.iter_read_batches)-->
       mpn_bam_decode --> mapper.PackedReads with its device copy
 
-There is no host path for them: a block whose status is not OK, or a text that is no BAM, raises ValueError.
+There is no host path for them: a block whose status is not OK, or a text that is no BAM, raises ValueError.  The steps up to the
+record table are BamTexts, which the stages that read a sorted BAM (candidates, clair_tensor, clair_call, local_realign) iterate too.
 
 FASTQ files as READ input (MPN_READ_INGEST=device, iter_fastq_read_batches): the text comes from the file as it is, from zlib on the
 host for an ordinary gzip stream, or through the front half of the BAM path (_BgzfTexts) for BGZF:
@@ -32,6 +33,7 @@ fastx.iter_fastx, and its records keep filling the same batches.
 The read filter and subseq (fastq_filter.filter_stream, fastx.subseq under the same knob) take their texts from the same sources
 (_ChunkTexts, _BgzfTexts), scan them with fastq_scan and hand kept rows to a ReadBatcher.
 """
+import collections
 import ctypes as ct
 import gzip
 import io
@@ -121,13 +123,7 @@ def _lib():
 
 def last_device_ms():
     """-> (inflate ms, scan ms) of the calling thread's last native calls"""
-    a, b = ct.c_double(0), ct.c_double(0)
-    _lib().mpn_ingest_last_device_ms(ct.byref(a), ct.byref(b))
-    return a.value, b.value
-
-
-def _ptr(a):
-    return a.ctypes.data if a.size else None
+    return _ffi.device_ms(_lib().mpn_ingest_last_device_ms, 2)
 
 
 def _align16(x):
@@ -141,10 +137,8 @@ def inflate_host(n_streams, data, in_off, slot_off, slot_cap, out):
     data, out = np.ascontiguousarray(data, dtype=np.uint8), np.require(out, dtype=np.uint8, requirements=['C', 'W'])
     in_off, slot_off, slot_cap = (np.ascontiguousarray(a, dtype=np.int64) for a in (in_off, slot_off, slot_cap))
     length, members, status = np.zeros(n_streams, np.int64), np.zeros(n_streams, np.int32), np.zeros(n_streams, np.int32)
-    rc = lib.mpn_gzip_inflate(n_streams, _ptr(data), in_off.ctypes.data, _ptr(out), _ptr(slot_off), _ptr(slot_cap), _ptr(length), _ptr(members),
-                              _ptr(status))
-    if rc:
-        raise _ffi.MpnError(f'mpn_gzip_inflate rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    _ffi.check(lib.mpn_gzip_inflate(n_streams, _ffi.ptr(data), in_off.ctypes.data, _ffi.ptr(out), _ffi.ptr(slot_off), _ffi.ptr(slot_cap), _ffi.ptr(length),
+                                    _ffi.ptr(members), _ffi.ptr(status)), 'mpn_gzip_inflate')
     return length, members, status
 
 
@@ -235,10 +229,8 @@ def inflate_files(items, device='cuda', limit=None, timings=None, tail_bytes=0):
         buf = torch.empty(max(int(so[-1]) + room, 16), dtype=torch.uint8, device=device)
         length, members, status = np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, np.int32)
         if m:
-            rc = lib.mpn_gzip_inflate_device(m, d_src.data_ptr(), offs.ctypes.data, buf.data_ptr(), so.ctypes.data, caps.ctypes.data,
-                                             length.ctypes.data, members.ctypes.data, status.ctypes.data)
-            if rc:
-                raise _ffi.MpnError(f'mpn_gzip_inflate_device rc={rc}: {_ffi.hint(_ffi.last_error())}')
+            _ffi.check(lib.mpn_gzip_inflate_device(m, d_src.data_ptr(), offs.ctypes.data, buf.data_ptr(), so.ctypes.data, caps.ctypes.data,
+                                                   length.ctypes.data, members.ctypes.data, status.ctypes.data), 'mpn_gzip_inflate_device')
         return buf, so, length, members, status, last_device_ms()[0] if m else 0.0
 
     text, so, length, members, status, ms = run(d_in, in_off, cap, room=int(tail_bytes))
@@ -292,10 +284,10 @@ def scan_fasta(text, off, length, out=None, out_pos=0, count_only=False):
     n_rec, n_bases, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
 
     def call(d_seq, seq_cap, rec_cap, rs, rno, rnl, rsl, pool, pool_cap, may_be_short=False):
-        rc = lib.mpn_fasta_scan(n, text.data_ptr(), _ptr(off), _ptr(length), d_seq, seq_cap, _ptr(n_rec), _ptr(n_bases), _ptr(status), rec_cap,
+        rc = lib.mpn_fasta_scan(n, text.data_ptr(), _ffi.ptr(off), _ffi.ptr(length), d_seq, seq_cap, _ffi.ptr(n_rec), _ffi.ptr(n_bases), _ffi.ptr(status), rec_cap,
                                 rs, rno, rnl, rsl, pool, pool_cap)
-        if rc and not (rc == -3 and may_be_short):
-            raise _ffi.MpnError(f'mpn_fasta_scan rc={rc}: {_ffi.hint(_ffi.last_error())}')
+        if not (rc == -3 and may_be_short):
+            _ffi.check(rc, 'mpn_fasta_scan')
         return rc
     call(None, 0, 0, None, None, None, None, None, 0)
     ms = last_device_ms()[1]
@@ -309,7 +301,7 @@ def scan_fasta(text, off, length, out=None, out_pos=0, count_only=False):
     rs, rno, rnl, rsl = np.zeros(R, np.int32), np.zeros(R, np.int64), np.zeros(R, np.int32), np.zeros(R, np.int64)
     pool = np.zeros(64 * R + 4096, dtype=np.uint8)
     if R:
-        args = (out.data_ptr() + out_pos, B, R, _ptr(rs), _ptr(rno), _ptr(rnl), _ptr(rsl))
+        args = (out.data_ptr() + out_pos, B, R, _ffi.ptr(rs), _ffi.ptr(rno), _ffi.ptr(rnl), _ffi.ptr(rsl))
         if call(*args, pool.ctypes.data, pool.size, may_be_short=True) == -3:
             # the names are longer than guessed (the lengths are complete): once more with room for them
             ms += last_device_ms()[1]
@@ -488,9 +480,7 @@ def bam_walk_records():
 
 def last_bam_device_ms():
     """-> (flatten ms, walk ms, decode ms) of the calling thread's last native calls"""
-    v = [ct.c_double(0) for _ in range(3)]
-    _lib().mpn_bam_last_device_ms(*[ct.byref(x) for x in v])
-    return tuple(x.value for x in v)
+    return _ffi.device_ms(_lib().mpn_bam_last_device_ms, 3)
 
 
 def _tick(timings, key, value):
@@ -593,10 +583,8 @@ def bam_flatten(slots, slot_off, slot_len, carry, device):
     total = n_carry + int(slot_len.sum())
     text = torch.empty(max(_align16(total), 16), dtype=torch.uint8, device=device)
     got = ct.c_int64(0)
-    rc = lib.mpn_bam_flatten(len(slot_off), slots.data_ptr(), _ptr(slot_off), _ptr(slot_len), carry.data_ptr() if n_carry else None, n_carry,
-                             text.data_ptr(), text.numel(), ct.byref(got))
-    if rc:
-        raise _ffi.MpnError(f'mpn_bam_flatten rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    _ffi.check(lib.mpn_bam_flatten(len(slot_off), slots.data_ptr(), _ffi.ptr(slot_off), _ffi.ptr(slot_len), carry.data_ptr() if n_carry else None, n_carry,
+                                   text.data_ptr(), text.numel(), ct.byref(got)), 'mpn_bam_flatten')
     assert got.value == total
     return text, total
 
@@ -606,10 +594,8 @@ def bam_walk(text, text_len, start, at_header, final, max_records):
     lib = _lib()
     rows = np.zeros(max_records, dtype=BAM_ROW)
     n, nxt, status = ct.c_int64(0), ct.c_int64(0), ct.c_int32(0)
-    rc = lib.mpn_bam_walk(text.data_ptr(), int(text_len), int(start), int(bool(at_header)), int(bool(final)), int(max_records), _ptr(rows),
-                          ct.byref(n), ct.byref(nxt), ct.byref(status))
-    if rc:
-        raise _ffi.MpnError(f'mpn_bam_walk rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    _ffi.check(lib.mpn_bam_walk(text.data_ptr(), int(text_len), int(start), int(bool(at_header)), int(bool(final)), int(max_records), _ffi.ptr(rows),
+                                ct.byref(n), ct.byref(nxt), ct.byref(status)), 'mpn_bam_walk')
     return rows[:n.value], nxt.value, status.value
 
 
@@ -626,10 +612,8 @@ def bam_decode(text, text_len, rows, with_qual):
     qual = torch.empty(size, dtype=torch.uint8, device=text.device) if with_qual else None
     name_len = rows['l_read_name'].astype(np.int64) - 1
     pool = np.zeros(max(int(name_len.sum()), 1), dtype=np.uint8)
-    rc = lib.mpn_bam_decode(text.data_ptr(), int(text_len), len(rows), _ptr(rows), _ptr(off), seq.data_ptr(), qual.data_ptr() if with_qual else None,
-                            pool.ctypes.data, pool.size)
-    if rc:
-        raise _ffi.MpnError(f'mpn_bam_decode rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    _ffi.check(lib.mpn_bam_decode(text.data_ptr(), int(text_len), len(rows), _ffi.ptr(rows), _ffi.ptr(off), seq.data_ptr(), qual.data_ptr() if with_qual else None,
+                                  pool.ctypes.data, pool.size), 'mpn_bam_decode')
     raw, ends = pool.tobytes(), np.cumsum(name_len)
     names = [raw[e - l:e].decode() for e, l in zip(ends.tolist(), name_len.tolist())]
     return seq, qual, names
@@ -702,10 +686,8 @@ class _BgzfTexts:
         slots = torch.empty(max(int(so[-1]), 16), dtype=torch.uint8, device=device)
         length, members, status = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
         if n:
-            rc = lib.mpn_gzip_inflate_device(n, d_in.data_ptr(), in_off.ctypes.data, slots.data_ptr(), so.ctypes.data, isize.ctypes.data,
-                                             length.ctypes.data, members.ctypes.data, status.ctypes.data)
-            if rc:
-                raise _ffi.MpnError(f'mpn_gzip_inflate_device rc={rc}: {_ffi.hint(_ffi.last_error())}')
+            _ffi.check(lib.mpn_gzip_inflate_device(n, d_in.data_ptr(), in_off.ctypes.data, slots.data_ptr(), so.ctypes.data, isize.ctypes.data,
+                                                   length.ctypes.data, members.ctypes.data, status.ctypes.data), 'mpn_gzip_inflate_device')
             _tick(timings, 'inflate_device_ms', last_device_ms()[0])
             bad = np.flatnonzero((status != OK) | (length != isize) | (members != 1))
             if len(bad):
@@ -721,60 +703,108 @@ class _BgzfTexts:
         return text, text_len, final
 
 
-def iter_bam_read_batches(stream_or_path, batch_bases=200_000_000, device='cuda', walk_records=None, timings=None):
-    """The reads of one BAM file as mapper.PackedReads of at most batch_bases each (cut as aligner.iter_read_batches cuts FASTQ
-    records), resident on the device, with the semantics of `samtools fastq` (DESIGN.md section 6).  stream_or_path: a path, or
-    the binary stream fastx.open_once returned for kind 'bam' (read to its end, not closed)."""
-    import time
-    device = device or 'cuda'
-    own = isinstance(stream_or_path, (str, bytes, os.PathLike))
-    stream = io.BufferedReader(open(stream_or_path, 'rb', buffering=0), buffer_size=1 << 20) if own else stream_or_path
-    walk_records = max(1, bam_walk_records() if walk_records is None else int(walk_records))
-    try:
-        texts = _BgzfTexts(stream, device, timings)
-        carry, at_header, text_base = None, True, 0       # text_base: the offset of text[0] in the whole inflated stream
-        pieces, acc, count = [], 0, 0
+# text[:text_len]: a device tensor; rows: every record walked in it (a BAM_ROW array); final: the last text of the file; base: the
+# offset of text[0] in the whole inflated stream
+BamText = collections.namedtuple('BamText', 'text text_len rows final base')
+
+
+class BamTexts:
+    """The texts of one BAM file with their records walked, one BamText per step: what every reader of a BAM iterates over, and the
+    only caller of bam_walk.  source: a path (opened at the first text, closed on leaving the `with`) or an open binary stream (read
+    to its end, left open).  A text begins where the one before ended, at the first byte that no complete record holds -- or, after
+    keep_from(i), at record i of the text before, for a reader that needs those records again next to the ones that follow.  The
+    text before is released once the next is built: one text and its carry are resident.  Booked in `timings`: what _BgzfTexts
+    books, and walk_device_ms, walk_launches and walk (seconds).  ValueError for a text that is no BAM, with its offset in the
+    whole inflated stream."""
+
+    def __init__(self, source, device='cuda', timings=None, walk_records=None):
+        self.path = source if isinstance(source, (str, bytes, os.PathLike)) else None
+        self.stream = None if self.path is not None else source
+        self.device, self.timings = device or 'cuda', timings
+        self.walk_records = max(1, bam_walk_records() if walk_records is None else int(walk_records))
+        self._steps, self._n_rows, self._keep = None, 0, None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._steps = None
+        if self.path is not None and self.stream is not None:
+            self.stream.close()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._steps is None:
+            self._steps = self._run()
+        return next(self._steps)
+
+    def keep_from(self, i):
+        """the next text begins at record i of the current one (i = len(rows): behind its last complete record, as without a call)"""
+        if not 0 <= i <= self._n_rows:
+            raise ValueError(f'keep_from({i}): the text has {self._n_rows} records')
+        self._keep = int(i)
+
+    def _run(self):
+        import time
+        if self.path is not None:
+            self.stream = io.BufferedReader(open(self.path, 'rb', buffering=0), buffer_size=1 << 20)
+        texts, timings = _BgzfTexts(self.stream, self.device, self.timings), self.timings
+        where = '' if self.path is None else f'{os.fsdecode(self.path)}: '
+        carry, at_header, base = None, True, 0
         while True:
             text, text_len, final = texts.next_text(carry)
-            t4 = time.perf_counter()
             del carry
+            t0 = time.perf_counter()
             start, got = 0, []
             while True:
-                rows, nxt, st = bam_walk(text, text_len, start, at_header, final, walk_records)
+                rows, nxt, st = bam_walk(text, text_len, start, at_header, final, self.walk_records)
                 _tick(timings, 'walk_device_ms', last_bam_device_ms()[1])
                 _tick(timings, 'walk_launches', 1)
                 if st != OK:
-                    raise ValueError(f'BAM text at offset {text_base + nxt} of the inflated stream: {STATUS_NAMES[st]}')
+                    raise ValueError(f'{where}BAM text at offset {base + nxt} of the inflated stream: {STATUS_NAMES[st]}')
                 if at_header and nxt > start:
                     at_header = False
                 got.append(rows)
                 start = nxt
-                if len(rows) < walk_records:
+                if len(rows) < self.walk_records:
                     break
             rows = np.concatenate(got)
-            _tick(timings, 'records', len(rows))
-            rows = rows[(rows['flag'] & BAM_SKIP) == 0]
-            _tick(timings, 'walk', time.perf_counter() - t4)
+            _tick(timings, 'walk', time.perf_counter() - t0)
+            self._n_rows, self._keep = len(rows), None
+            yield BamText(text, text_len, rows, final, base)
+            if final:
+                return
+            if self._keep is not None and self._keep < len(rows):
+                start = int(rows['off'][self._keep])
+            carry = text[start:text_len]
+            base += start
+
+
+def iter_bam_read_batches(stream_or_path, batch_bases=200_000_000, device='cuda', walk_records=None, timings=None):
+    """The reads of one BAM file as mapper.PackedReads of at most batch_bases each (cut as aligner.iter_read_batches cuts FASTQ
+    records), resident on the device, with the semantics of `samtools fastq` (DESIGN.md section 6).  stream_or_path: a path, or
+    the binary stream fastx.open_once returned for kind 'bam' (read to its end, not closed)."""
+    device = device or 'cuda'
+    pieces, acc, count = [], 0, 0
+    with BamTexts(stream_or_path, device, timings, walk_records) as texts:
+        for t in texts:
+            _tick(timings, 'records', len(t.rows))
+            rows = t.rows[(t.rows['flag'] & BAM_SKIP) == 0]
             lo = 0
             for i, l in enumerate(rows['l_seq'].tolist()):
                 if count and acc + l > batch_bases:
                     if i > lo:
-                        pieces.append((text, text_len, rows[lo:i]))
+                        pieces.append((t.text, t.text_len, rows[lo:i]))
                     yield _bam_batch(pieces, device, timings)
                     pieces, acc, count, lo = [], 0, 0, i
                 acc += l
                 count += 1
             if lo < len(rows):
-                pieces.append((text, text_len, rows[lo:]))
-            if final:
-                break
-            carry = text[start:text_len]
-            text_base += start
+                pieces.append((t.text, t.text_len, rows[lo:]))
         if count:
             yield _bam_batch(pieces, device, timings)
-    finally:
-        if own:
-            stream.close()
 
 
 def read_bam(stream_or_path, device='cuda'):
@@ -801,9 +831,7 @@ def fastq_tile():
 
 def last_fastq_device_ms():
     """-> (scan ms, gather ms) of the calling thread's last native calls"""
-    a, b = ct.c_double(0), ct.c_double(0)
-    _lib().mpn_fastq_last_device_ms(ct.byref(a), ct.byref(b))
-    return a.value, b.value
+    return _ffi.device_ms(_lib().mpn_fastq_last_device_ms, 2)
 
 
 def fastq_scan(text, text_len, final, rec_cap=None):
@@ -819,13 +847,12 @@ def fastq_scan(text, text_len, final, rec_cap=None):
     ms = 0.0
     while True:
         rows = np.empty(cap, dtype=FASTQ_ROW)
-        rc = lib.mpn_fastq_scan(text.data_ptr(), text_len, int(bool(final)), cap, _ptr(rows), ct.byref(n), ct.byref(consumed), ct.byref(status))
+        rc = lib.mpn_fastq_scan(text.data_ptr(), text_len, int(bool(final)), cap, _ffi.ptr(rows), ct.byref(n), ct.byref(consumed), ct.byref(status))
         ms += last_fastq_device_ms()[0]
         if rc == -3 and n.value > cap:
             cap = n.value
             continue
-        if rc:
-            raise _ffi.MpnError(f'mpn_fastq_scan rc={rc}: {_ffi.hint(_ffi.last_error())}')
+        _ffi.check(rc, 'mpn_fastq_scan')
         return rows[:n.value], consumed.value, status.value, ms
 
 
@@ -842,10 +869,8 @@ def fastq_gather(text, text_len, rows, with_qual=True):
     qual = torch.empty(size, dtype=torch.uint8, device=text.device) if with_qual else None
     name_len = rows['name_len'].astype(np.int64)
     pool = np.zeros(max(int(name_len.sum()), 1), dtype=np.uint8)
-    rc = lib.mpn_fastq_gather(text.data_ptr(), int(text_len), len(rows), _ptr(rows), _ptr(off), seq.data_ptr(), qual.data_ptr() if with_qual else None,
-                              pool.ctypes.data, pool.size)
-    if rc:
-        raise _ffi.MpnError(f'mpn_fastq_gather rc={rc}: {_ffi.hint(_ffi.last_error())}')
+    _ffi.check(lib.mpn_fastq_gather(text.data_ptr(), int(text_len), len(rows), _ffi.ptr(rows), _ffi.ptr(off), seq.data_ptr(), qual.data_ptr() if with_qual else None,
+                                    pool.ctypes.data, pool.size), 'mpn_fastq_gather')
     raw, ends = pool.tobytes(), np.cumsum(name_len)
     names = [raw[e - l:e].decode() for e, l in zip(ends.tolist(), name_len.tolist())]
     return seq, qual, names

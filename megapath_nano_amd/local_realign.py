@@ -8,7 +8,8 @@ include/mpn_local_realign.h.
     extract_vcf_position(vcf_fn, alt, output_fn)                  ExtractVcfPosition: DP and AF of the VCF from those lines
     bin/mpn-local-realign                                         the command line of realignment.sh
 
-The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) as clair_call.indel_events does it; no samtools, .bai or .fai is used.
+The BAM goes to HBM group by group (MPN_INGEST_BATCH_BYTES) through ingest.BamTexts, each text beginning at the first record that an
+unfinished site still needs (keep_from); no samtools, .bai or .fai is used.
 Per group the host bisects every site's range of records and keeps those that overlap its region (numpy; samtools' -d 8000 rule runs
 in the native layer for the sites that have 8000 candidates); the device finds the surviving columns, builds every read's fragment,
 aligns it (SSW) against the site's reference window and counts the alleles.  Fragments, SSW results and CIGARs never leave HBM; the host
@@ -27,7 +28,8 @@ import sys
 
 import numpy as np
 
-from . import candidates, clair_tensor, ingest
+from . import _ffi, candidates, clair_tensor, ingest
+from ._ffi import check as _check, ptr as _p
 
 FILTER_FLAG = 1796          # mpileup's default --ff: UNMAP, SECONDARY, QCFAIL, DUP (supplementary records are piled up)
 WINDOW, REGION, FLANK, MAXCNT, MASK_WORDS, MAX_KEYS = 200, 233, 300, 8000, 13, 4
@@ -67,13 +69,7 @@ def _lib():
 
 def last_device_ms():
     """-> (columns ms, fragments ms, SSW ms, tally ms) of the calling thread's last native calls"""
-    v = [ct.c_double(0) for _ in range(4)]
-    _lib().mpn_lr_last_device_ms(*[ct.byref(x) for x in v])
-    return tuple(x.value for x in v)
-
-
-_check = candidates._check
-_p = clair_tensor._p
+    return _ffi.device_ms(_lib().mpn_lr_last_device_ms, 4)
 
 
 # ---- the native calls ---------------------------------------------------------------------------------------------------------------
@@ -161,7 +157,7 @@ def fragment_bytes(text, text_len, reads, sites, pairs, mask, length):
     _check(_lib().mpn_lr_fragments(text.data_ptr(), int(text_len), len(reads), _p(reads), len(sites), _p(sites), len(pairs), _p(pairs), mask.data_ptr(),
                                    _p(length), None, _p(off), letters.data_ptr(), codes.data_ptr(), cap, ct.byref(bad), ct.byref(why)), 'mpn_lr_fragments')
     if bad.value >= 0:
-        raise candidates._ffi.MpnError('mpn_lr_fragments: the fill pass refuses a pair that the count pass took')
+        raise _ffi.MpnError('mpn_lr_fragments: the fill pass refuses a pair that the count pass took')
     return off, letters, codes
 
 
@@ -277,42 +273,15 @@ def alt_info(bam_fn, ref_fn, ctg_name, positions, device='cuda', timings=None):
                                                if p <= FLANK else 'behind the end of the contig'), file=sys.stderr)
     sites = sites[(sites > FLANK) & (sites <= len(seq))]
     contig = torch.from_numpy(np.frombuffer(bytes(seq), dtype=np.uint8).copy()).to(device)
-    refs = candidates.bam_references(bam_fn)
-    names = [n for n, _ in refs]
-    tid = names.index(ctg_name) if ctg_name in names else -2
-    walk_records = max(1, ingest.bam_walk_records())
+    tid, _ = candidates.contig_tid(bam_fn, ctg_name)
     next_site, last_pos, result = 0, None, {}
-    with io.BufferedReader(open(bam_fn, 'rb', buffering=0), buffer_size=1 << 20) as stream:
-        texts = ingest._BgzfTexts(stream, device, timings)
-        carry, at_header = None, True
+    with ingest.BamTexts(bam_fn, device, timings) as texts:
         while next_site < len(sites):
-            text, text_len, final = texts.next_text(carry)
-            del carry
-            start, got = 0, []
-            while True:
-                rows, nxt, st = ingest.bam_walk(text, text_len, start, at_header, final, walk_records)
-                if st != ingest.OK:
-                    raise ValueError(f'{bam_fn}: BAM text: {ingest.STATUS_NAMES[st]}')
-                if at_header and nxt > start:
-                    at_header = False
-                got.append(rows)
-                start = nxt
-                if len(rows) < walk_records:
-                    break
-            rows = np.concatenate(got)
-            all_rows = rows
-            keep = np.flatnonzero((rows['flag'] & FILTER_FLAG) == 0)
-            recs = candidates.pileup_records(text, text_len, rows[keep])
-            on = np.flatnonzero(recs['ref_id'] == tid)
-            keep, recs = keep[on], recs[on]
-            rows = all_rows[keep]
-            trecs = clair_tensor.tensor_records(text, text_len, rows)
-            pos = recs['pos'].astype(np.int64)
-            end = pos + np.maximum(trecs['hts_len'].astype(np.int64), 1)
-            if len(pos):
-                if bool((pos[1:] < pos[:-1]).any()) or (last_pos is not None and int(pos[0]) < last_pos):
-                    raise ValueError(f'{bam_fn}: the records of {ctg_name} are not sorted by position')
-                last_pos = int(pos[-1])
+            t = next(texts)
+            text, text_len, final = t.text, t.text_len, t.final
+            keep, pos, rlen, last_pos = clair_tensor.contig_reads(t, tid, last_pos, f'{bam_fn}: the records of {ctg_name} are not sorted by position',
+                                                                  FILTER_FLAG)
+            rows, end = t.rows[keep], pos + np.maximum(rlen, 1)
             todo = sites[next_site:]
             # a site is complete when a record starts behind its region (0-based: at site + 234 or later)
             n_fin = len(todo) if final else (int(np.searchsorted(todo, int(pos[-1]) - REGION - 1, side='right')) if len(pos) else 0)
@@ -323,14 +292,14 @@ def alt_info(bam_fn, ref_fn, ctg_name, positions, device='cuda', timings=None):
                 next_site += n_fin
             if final:
                 break
-            cut = len(all_rows)
+            cut = len(t.rows)
             if next_site < len(sites) and len(pos):
                 reach = np.maximum.accumulate(end)
                 b = int(np.searchsorted(reach, int(sites[next_site]) - REGION - 1, side='right'))
                 if b < len(keep):
                     cut = int(keep[b])
                     last_pos = int(pos[b])                # the next text starts again at this record
-            carry = text[int(all_rows['off'][cut]) if cut < len(all_rows) else start:text_len]
+            texts.keep_from(cut)
     out = {}
     for p in sites.tolist():
         got = result.get(p, (0, {}))                       # (the file ended before the site: no read reaches it)
