@@ -54,6 +54,33 @@ typedef struct {
 int mpn_realign_batch(int32_t n_windows, const mpn_realign_window *windows, int32_t *out_position, char **out_cigar);
 void mpn_realign_free_cigars(char **cigars, int64_t n);
 
+/* ---- Part 3: stage entry of the placement stage (for the parity tests) ------------------ */
+/* One accepted placement of a read on a haplotype (hap and read count inside their window): the read fits at `start` with `mm`
+ * (<= 2) mismatches, and the reference's loop would first have evaluated it at haplotype position `t` through the read's k-mer at
+ * offset `p` (start == max(0, t - p)). */
+typedef struct {
+    int32_t window, hap, read, start, mm, t, p;
+} mpn_realign_hit;
+
+/* Runs the two steps mpn_realign_batch begins with -- the placement kernel over every (haplotype, read) pair, then the
+ * per-haplotype bookkeeping of FastAlignReadsToHaplotypes (realigner.cpp:147-230) -- on the same windows, and returns what they
+ * leave before any Smith-Waterman step (tests/test_realign_place_gpu.py; positions, cigars, ref_start and the content of
+ * reference beyond its comparison with the haplotypes are not read).
+ *   list_cap   capacity of the first launch's hit list, grid_cap the largest grid; 0: the realigner's own value
+ *   hit_cap    room in out_hits; at least the sum over the pairs of max(0, haplotype length - read length + 1) is asked for
+ *   out_hits   the hits in the reference's order of evaluation (haplotype, t, read, p); *out_n_hits of them
+ *   out_kmer   per haplotype, one byte per position 0 .. length - 32: 1 where the 32-mer there is a k-mer of any read of the
+ *              window longer than 32 bases (the haplotypes of all windows in order, back to back)
+ *   out_dropped, out_hap_score   per haplotype: 1 where the coverage test ended it (:224-228), and its score
+ *   out_position, out_score      per (haplotype, read) in window, haplotype, read order: -1 / 0 where the read is not placed
+ *   out_launches  kernel launches it took: 2 when the first list overflowed (a second overflow is an error, -1)
+ * Malformed windows, haplotypes under 32 bases, negative knobs and a hit_cap too small are refused before anything is uploaded
+ * (-2, mpn_last_error()); the outputs are written only on success. */
+int mpn_realign_place_batch(int32_t n_windows, const mpn_realign_window *windows, int64_t list_cap, int32_t grid_cap,
+                            int64_t hit_cap, mpn_realign_hit *out_hits, int64_t *out_n_hits, uint8_t *out_kmer,
+                            uint8_t *out_dropped, int32_t *out_hap_score, int32_t *out_position, int32_t *out_score,
+                            int32_t *out_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -333,23 +333,41 @@ struct HapAln {
     bool operator<(const HapAln &o) const { return score < o.score; }   // realigner.h HaplotypeReadsAlignment::operator<
 };
 
-static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_pos, std::vector<std::string> &out_cig) {
-    // ---- flatten ----
+// The windows laid out for the kernel: every read and haplotype in one text, a pair per (haplotype, read) of a window.
+struct Flat {
     std::vector<uint8_t> text;
     std::vector<int64_t> read_off, hap_off, hk_off;
     std::vector<int32_t> read_len, hap_len, pair_hap, pair_read;
-    std::vector<int> win_read0(n_win + 1, 0), win_hap0(n_win + 1, 0);
+    std::vector<int> win_read0, win_hap0;
     int64_t hk_words = 0;
+};
+
+// Placement stage: flattens the windows, runs realign_fast_kernel over every (haplotype, read) pair and leaves the hits in the
+// reference's order of evaluation with the haplotypes' k-mer bitmaps.  list_cap / grid_cap: the first launch's list capacity and the
+// largest grid (0: the realigner's own); max_hits >= 0: refuse, before anything is uploaded, a batch that could give more hits.
+static int place_reads(int n_win, const mpn_realign_window *W, int64_t list_cap, int grid_cap, int64_t max_hits, Flat &F,
+                       std::vector<FastHit> &hits, std::vector<uint32_t> &has_kmer, int *launches) {
+    // ---- flatten ----
+    std::vector<uint8_t> &text = F.text;
+    std::vector<int64_t> &read_off = F.read_off, &hap_off = F.hap_off, &hk_off = F.hk_off;
+    std::vector<int32_t> &read_len = F.read_len, &hap_len = F.hap_len, &pair_hap = F.pair_hap, &pair_read = F.pair_read;
+    std::vector<int> &win_read0 = F.win_read0, &win_hap0 = F.win_hap0;
+    int64_t &hk_words = F.hk_words;
+    win_read0.assign((size_t)n_win + 1, 0); win_hap0.assign((size_t)n_win + 1, 0);
     for (int w = 0; w < n_win; ++w) {
         const mpn_realign_window &x = W[w];
-        if (x.n_reads < 0 || x.n_haps < 0 || !x.reference) { set_error("realign: window %d is malformed", w); return -2; }
+        if (x.n_reads < 0 || x.n_haps < 0 || !x.reference || (x.n_reads > 0 && !x.seqs) || (x.n_haps > 0 && !x.haplotypes)) {
+            set_error("realign: window %d is malformed", w); return -2;
+        }
         win_read0[w + 1] = win_read0[w] + x.n_reads; win_hap0[w + 1] = win_hap0[w] + x.n_haps;
         for (int r = 0; r < x.n_reads; ++r) {
+            if (!x.seqs[r]) { set_error("realign: window %d is malformed", w); return -2; }
             const size_t L = strlen(x.seqs[r]);
             read_off.push_back((int64_t)text.size()); read_len.push_back((int32_t)L);
             text.insert(text.end(), x.seqs[r], x.seqs[r] + L);
         }
         for (int h = 0; h < x.n_haps; ++h) {
+            if (!x.haplotypes[h]) { set_error("realign: window %d is malformed", w); return -2; }
             const size_t L = strlen(x.haplotypes[h]);
             if (L < (size_t)RA_KMER) { set_error("realign: window %d haplotype %d has %zu bases (< 32: undefined in the reference)", w, h, L); return -2; }
             hap_off.push_back((int64_t)text.size()); hap_len.push_back((int32_t)L);
@@ -358,10 +376,16 @@ static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_
             for (int r = 0; r < x.n_reads; ++r) { pair_hap.push_back(win_hap0[w] + h); pair_read.push_back(win_read0[w] + r); }
         }
     }
-    const int n_reads = win_read0[n_win], n_haps = win_hap0[n_win], n_pairs = (int)pair_hap.size();
+    const int n_pairs = (int)pair_hap.size();
     // ---- GPU: placements of every read on every haplotype ----
-    std::vector<FastHit> hits;
-    std::vector<uint32_t> has_kmer((size_t)hk_words, 0);
+    hits.clear();
+    has_kmer.assign((size_t)hk_words, 0);
+    *launches = 0;
+    // every (pair, start) is reported at most once
+    int64_t cap_max = 0;
+    for (int p = 0; p < n_pairs; ++p) cap_max += std::max(0, hap_len[pair_hap[p]] - read_len[pair_read[p]] + 1);
+    if (cap_max > 0xfffffff0LL) { set_error("realign: batch too large (split it)"); return -2; }
+    if (max_hits >= 0 && cap_max > max_hits) { set_error("realign: room for %lld hits needed", (long long)cap_max); return -2; }
     if (n_pairs > 0) {
         hipStream_t st = 0;
         DevBuf<uint8_t> d_text;
@@ -371,19 +395,17 @@ static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_
         DevBuf<unsigned int> d_n;
         DevBuf<FastHit> d_hits;
         text.push_back(0);
-        // every (pair, start) is reported at most once, and a read fits a haplotype with <= 2 mismatches at a handful of starts:
-        // the list is sized for 16 per pair and the kernel is run again in the (pathological) case that it overflows
-        int64_t cap_max = 0;
-        for (int p = 0; p < n_pairs; ++p) cap_max += std::max(0, hap_len[pair_hap[p]] - read_len[pair_read[p]] + 1);
-        int64_t cap = std::min<int64_t>(std::max<int64_t>(16 * (int64_t)n_pairs, 1 << 16), std::max<int64_t>(cap_max, 1));
-        if (cap_max > 0xfffffff0LL) { set_error("realign: batch too large (split it)"); return -2; }
+        // a read fits a haplotype with <= 2 mismatches at a handful of starts: the list is sized for 16 per pair and the kernel is
+        // run again in the (pathological) case that it overflows
+        int64_t cap = std::min<int64_t>(list_cap > 0 ? list_cap : std::max<int64_t>(16 * (int64_t)n_pairs, 1 << 16), std::max<int64_t>(cap_max, 1));
         if (d_text.upload(text.data(), text.size(), st) || d_roff.upload(read_off.data(), read_off.size(), st) ||
             d_rlen.upload(read_len.data(), read_len.size(), st) || d_hoff.upload(hap_off.data(), hap_off.size(), st) ||
             d_hlen.upload(hap_len.data(), hap_len.size(), st) || d_ph.upload(pair_hap.data(), pair_hap.size(), st) ||
             d_pr.upload(pair_read.data(), pair_read.size(), st) || d_hk_off.upload(hk_off.data(), hk_off.size(), st) ||
             d_hk.alloc((size_t)hk_words) || d_hk.zero(st) || d_n.alloc(1))
             return -1;
-        const int grid = std::max(1, std::min((n_pairs + 3) / 4, 256 * 32));
+        int grid = std::max(1, std::min((n_pairs + 3) / 4, 256 * 32));
+        if (grid_cap > 0) grid = std::min(grid, grid_cap);
         unsigned int nh = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
             if (d_n.zero(st) || d_hits.alloc((size_t)cap)) return -1;
@@ -391,6 +413,7 @@ static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_
                                (const int32_t *)d_rlen.p, (const int64_t *)d_hoff.p, (const int32_t *)d_hlen.p, (const int32_t *)d_ph.p,
                                (const int32_t *)d_pr.p, n_pairs, (const int64_t *)d_hk_off.p, d_hk.p, d_hits.p, d_n.p, (unsigned int)cap);
             MPN_HIP_CHECK(hipGetLastError());
+            ++*launches;
             if (d_n.download(&nh, 1, st)) return -1;
             MPN_HIP_CHECK(hipStreamSynchronize(st));
             if ((int64_t)nh <= cap) break;
@@ -410,17 +433,21 @@ static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_
         if (ra != rb) return ra < rb;
         return a.p < b.p;
     });
-    // ---- per haplotype: coverage test, best placement per read, haplotype score (realigner.cpp:147-230) ----
-    std::vector<HapAln> haps((size_t)n_haps);
-    std::vector<std::vector<int8_t>> read_codes((size_t)n_reads), hap_codes((size_t)n_haps), ref_codes((size_t)n_win);
-    auto translate = [](const char *s, size_t n, std::vector<int8_t> &out) {
-        out.resize(n);
-        for (size_t i = 0; i < n; ++i) out[i] = g_tr.tr[(unsigned char)s[i] & 127];
-    };
+    return 0;
+}
+
+// Per haplotype: coverage test, best placement per read, haplotype score, reset of a dropped or zero-score haplotype
+// (FastAlignReadsToHaplotypes, realigner.cpp:147-230) from the placement stage's hits and bitmaps.  dropped (optional): one flag per
+// haplotype, set where the coverage test ended the haplotype.
+static void score_haplotypes(int n_win, const mpn_realign_window *W, const Flat &F, const std::vector<FastHit> &hits,
+                             const std::vector<uint32_t> &has_kmer, std::vector<HapAln> &haps, std::vector<uint8_t> *dropped_out) {
+    const std::vector<int32_t> &read_len = F.read_len, &hap_len = F.hap_len, &pair_hap = F.pair_hap, &pair_read = F.pair_read;
+    const std::vector<int> &win_read0 = F.win_read0, &win_hap0 = F.win_hap0;
+    haps.assign((size_t)win_hap0[n_win], HapAln());
+    if (dropped_out) dropped_out->assign(haps.size(), 0);
     size_t hp = 0;
     for (int w = 0; w < n_win; ++w) {
         const mpn_realign_window &x = W[w];
-        translate(x.reference, strlen(x.reference), ref_codes[(size_t)w]);
         for (int h = 0; h < x.n_haps; ++h) {
             const int gh = win_hap0[w] + h, HL = hap_len[gh];
             HapAln &A = haps[(size_t)gh];
@@ -431,7 +458,7 @@ static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_
             while (hp < hits.size() && pair_hap[hits[hp].pair] == gh) ++hp;
             bool dropped = false;
             {
-                const uint32_t *hk = has_kmer.data() + hk_off[gh];
+                const uint32_t *hk = has_kmer.data() + F.hk_off[gh];
                 size_t k = h0;
                 int max_end = -1;
                 for (int i = 0; i + RA_KMER <= HL && !is_ref; ++i) {
@@ -451,8 +478,31 @@ static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_
                 }
             }
             if (dropped || A.score == 0) { A.score = 0; A.reads.assign((size_t)x.n_reads, ReadAln()); }
-            translate(x.haplotypes[h], (size_t)HL, hap_codes[(size_t)gh]);
+            if (dropped_out) (*dropped_out)[(size_t)gh] = dropped;
         }
+    }
+}
+
+static int realign_windows(int n_win, const mpn_realign_window *W, int32_t *out_pos, std::vector<std::string> &out_cig) {
+    Flat F;
+    std::vector<FastHit> hits;
+    std::vector<uint32_t> has_kmer;
+    int launches = 0;
+    if (const int rc = place_reads(n_win, W, 0, 0, -1, F, hits, has_kmer, &launches)) return rc;
+    std::vector<HapAln> haps;
+    score_haplotypes(n_win, W, F, hits, has_kmer, haps, nullptr);
+    const std::vector<int32_t> &read_len = F.read_len, &hap_len = F.hap_len;
+    const std::vector<int> &win_read0 = F.win_read0, &win_hap0 = F.win_hap0;
+    const int n_reads = win_read0[n_win], n_haps = win_hap0[n_win];
+    std::vector<std::vector<int8_t>> read_codes((size_t)n_reads), hap_codes((size_t)n_haps), ref_codes((size_t)n_win);
+    auto translate = [](const char *s, size_t n, std::vector<int8_t> &out) {
+        out.resize(n);
+        for (size_t i = 0; i < n; ++i) out[i] = g_tr.tr[(unsigned char)s[i] & 127];
+    };
+    for (int w = 0; w < n_win; ++w) {
+        const mpn_realign_window &x = W[w];
+        translate(x.reference, strlen(x.reference), ref_codes[(size_t)w]);
+        for (int h = 0; h < x.n_haps; ++h) translate(x.haplotypes[h], (size_t)hap_len[win_hap0[w] + h], hap_codes[(size_t)(win_hap0[w] + h)]);
         for (int r = 0; r < x.n_reads; ++r) translate(x.seqs[r], (size_t)read_len[win_read0[w] + r], read_codes[(size_t)(win_read0[w] + r)]);
     }
     // ---- GPU: haplotype -> reference (realigner.cpp:325-349) ----
@@ -552,6 +602,46 @@ int mpn_realign_batch(int32_t n_windows, const mpn_realign_window *windows, int3
 void mpn_realign_free_cigars(char **cigars, int64_t n) {
     if (!cigars) return;
     for (int64_t i = 0; i < n; ++i) { free(cigars[i]); cigars[i] = nullptr; }
+}
+
+int mpn_realign_place_batch(int32_t n_windows, const mpn_realign_window *windows, int64_t list_cap, int32_t grid_cap, int64_t hit_cap,
+                            mpn_realign_hit *out_hits, int64_t *out_n_hits, uint8_t *out_kmer, uint8_t *out_dropped, int32_t *out_hap_score,
+                            int32_t *out_position, int32_t *out_score, int32_t *out_launches) {
+    if (n_windows < 0 || (n_windows > 0 && !windows) || !out_n_hits || !out_launches) { set_error("mpn_realign_place_batch: null argument"); return -2; }
+    if (list_cap < 0 || grid_cap < 0 || hit_cap < 0) { set_error("mpn_realign_place_batch: list_cap, grid_cap or hit_cap negative"); return -2; }
+    {   // the arrays the results go to: needed as soon as there is a haplotype, a pair or room for a hit
+        int64_t n_haps = 0, n_pairs = 0;
+        for (int w = 0; w < n_windows; ++w)
+            if (windows[w].n_haps > 0) { n_haps += windows[w].n_haps; n_pairs += (int64_t)windows[w].n_haps * std::max(0, windows[w].n_reads); }
+        if ((n_haps > 0 && (!out_kmer || !out_dropped || !out_hap_score)) || (n_pairs > 0 && (!out_position || !out_score)) || (hit_cap > 0 && !out_hits)) {
+            set_error("mpn_realign_place_batch: null argument"); return -2;
+        }
+    }
+    Flat F;
+    std::vector<FastHit> hits;
+    std::vector<uint32_t> has_kmer;
+    int launches = 0;
+    if (const int rc = place_reads(n_windows, windows, list_cap, grid_cap, hit_cap, F, hits, has_kmer, &launches)) return rc;
+    std::vector<HapAln> haps;
+    std::vector<uint8_t> dropped;
+    score_haplotypes(n_windows, windows, F, hits, has_kmer, haps, &dropped);
+    for (size_t k = 0; k < hits.size(); ++k) {
+        const FastHit &f = hits[k];
+        const int gh = F.pair_hap[f.pair], gr = F.pair_read[f.pair];
+        const int w = (int)(std::upper_bound(F.win_hap0.begin(), F.win_hap0.end(), gh) - F.win_hap0.begin()) - 1;
+        out_hits[k] = mpn_realign_hit{w, gh - F.win_hap0[w], gr - F.win_read0[w], f.start, f.mm, f.t, f.p};
+    }
+    *out_n_hits = (int64_t)hits.size();
+    *out_launches = launches;
+    int64_t kp = 0, pp = 0;
+    for (size_t gh = 0; gh < haps.size(); ++gh) {
+        const uint32_t *hk = has_kmer.data() + F.hk_off[gh];
+        for (int i = 0; i + RA_KMER <= F.hap_len[gh]; ++i) out_kmer[kp++] = (uint8_t)(hk[i >> 5] >> (i & 31) & 1);
+        out_dropped[gh] = dropped[gh];
+        out_hap_score[gh] = haps[gh].score;
+        for (const ReadAln &ra : haps[gh].reads) { out_position[pp] = ra.position; out_score[pp] = ra.score; ++pp; }
+    }
+    return 0;
 }
 
 struct_str_arr *realign_reads(char *seqs[], int *positions, char *cigars[], char *reference, char *haplotypes, int ref_start,

@@ -3,6 +3,7 @@
 
     realign_reads(...)   one window through the reference's own C entry points (realign_reads / free_memory)
     realign_batch([...]) many windows in one call (mpn_realign_batch): one launch per stage over all of them
+    place_batch([...])   the placement stage of realign_batch on its own (mpn_realign_place_batch), for the parity tests
 
 Both return, per read, (position, cigar_string) exactly as the reference's `realigner_p.contents` would hold them
 (a match run is written 'X'; reads the realigner leaves alone come back with their input position and CIGAR).
@@ -51,13 +52,9 @@ def realign_reads(seqs, positions, cigars, reference, haplotypes, ref_start, ref
     return out
 
 
-def realign_batch(windows):
-    """windows: dicts with the keyword arguments of realign_reads -> one list of (position, cigar) per window."""
-    lib = _ffi.lib()
-    nw = len(windows)
-    if nw == 0:
-        return []
-    arr = (Window * nw)()
+def _window_array(windows):
+    """-> (mpn_realign_window array, the ctypes arrays it points into, reads in all)"""
+    arr = (Window * max(len(windows), 1))()
     keep = []
     total = 0
     for k, w in enumerate(windows):
@@ -66,9 +63,78 @@ def realign_batch(windows):
         cigs = (ct.c_char_p * max(n, 1))(*[_b(c) for c in w['cigars']])
         pos = (ct.c_int32 * max(n, 1))(*w['positions'])
         haps = (ct.c_char_p * max(nh, 1))(*[_b(h) for h in w['haplotypes']])
-        keep.append((seqs, cigs, pos, haps))
-        arr[k] = Window(n, seqs, pos, cigs, _b(w['reference']), nh, haps, w['ref_start'], w['ref_prefix'], w['ref_suffix'])
+        ref = None if w['reference'] is None else _b(w['reference'])
+        keep.append((seqs, cigs, pos, haps, ref))
+        arr[k] = Window(n, seqs, pos, cigs, ref, nh, haps, w['ref_start'], w['ref_prefix'], w['ref_suffix'])
         total += n
+    return arr, keep, total
+
+
+class Hit(ct.Structure):             # include/mpn_realign.h mpn_realign_hit
+    _fields_ = [(k, ct.c_int32) for k in ('window', 'hap', 'read', 'start', 'mm', 't', 'p')]
+
+
+def place_call(windows, list_cap=0, grid_cap=0, hit_cap=None):
+    """mpn_realign_place_batch as it is: -> (return code, dict of the output arrays).  The arrays are filled with marks first
+    (bytes of 0x55), so that a caller sees whether a refused call wrote to them."""
+    lib = _ffi.lib()
+    arr, keep, _ = _window_array(windows)   # keep: alive until the call has returned
+    n_haps = sum(len(w['haplotypes']) for w in windows)
+    n_pairs = sum(len(w['haplotypes']) * len(w['seqs']) for w in windows)
+    n_kmer = sum(max(0, len(h) - 31) for w in windows for h in w['haplotypes'])
+    if hit_cap is None:
+        hit_cap = sum(max(0, len(h) - len(s) + 1) for w in windows for h in w['haplotypes'] for s in w['seqs'])
+    out = dict(hits=(Hit * max(hit_cap, 1))(), n_hits=ct.c_int64(), kmer=(ct.c_uint8 * max(n_kmer, 1))(),
+               dropped=(ct.c_uint8 * max(n_haps, 1))(), hap_score=(ct.c_int32 * max(n_haps, 1))(),
+               position=(ct.c_int32 * max(n_pairs, 1))(), score=(ct.c_int32 * max(n_pairs, 1))(), launches=ct.c_int32())
+    for v in out.values():
+        ct.memset(ct.byref(v), 0x55, ct.sizeof(v))
+    P = ct.c_void_p
+    lib.mpn_realign_place_batch.restype = ct.c_int
+    lib.mpn_realign_place_batch.argtypes = [ct.c_int32, ct.POINTER(Window), ct.c_int64, ct.c_int32, ct.c_int64, P, P, P, P, P, P, P, P]
+    rc = lib.mpn_realign_place_batch(len(windows), arr, list_cap, grid_cap, hit_cap, ct.byref(out['hits']), ct.byref(out['n_hits']),
+                                     ct.byref(out['kmer']), ct.byref(out['dropped']), ct.byref(out['hap_score']),
+                                     ct.byref(out['position']), ct.byref(out['score']), ct.byref(out['launches']))
+    return rc, out
+
+
+def place_batch(windows, list_cap=0, grid_cap=0):
+    """The placement stage on its own (mpn_realign_place_batch): the kernel's hits and k-mer bitmaps and the per-haplotype
+    bookkeeping, as realign_batch has them before any Smith-Waterman step.  windows as for realign_batch; list_cap / grid_cap: the
+    first launch's hit-list capacity and the largest grid, 0 for the realigner's own.  -> (one dict per window, kernel launches):
+        hits        [(hap, read, start, mm, t, p)] in the reference's order of evaluation (haplotype, t, read, p)
+        kmer        per haplotype: bytes, 1 at the positions 0 .. HL - 32 that hold a 32-mer of any read
+        dropped, score          per haplotype
+        position, read_score    per haplotype, per read (-1 / 0: not placed)"""
+    rc, o = place_call(windows, list_cap, grid_cap)
+    _ffi.check(rc, 'mpn_realign_place_batch')
+    res = [dict(hits=[], kmer=[], dropped=[], score=[], position=[], read_score=[]) for _ in windows]
+    for k in range(o['n_hits'].value):
+        h = o['hits'][k]
+        res[h.window]['hits'].append((h.hap, h.read, h.start, h.mm, h.t, h.p))
+    kmer = bytes(o['kmer'])
+    gh = kp = pp = 0
+    for w, r in zip(windows, res):
+        n = len(w['seqs'])
+        for hap in w['haplotypes']:
+            r['kmer'].append(kmer[kp:kp + len(hap) - 31])
+            r['dropped'].append(bool(o['dropped'][gh]))
+            r['score'].append(int(o['hap_score'][gh]))
+            r['position'].append([int(x) for x in o['position'][pp:pp + n]])
+            r['read_score'].append([int(x) for x in o['score'][pp:pp + n]])
+            kp += len(hap) - 31
+            pp += n
+            gh += 1
+    return res, int(o['launches'].value)
+
+
+def realign_batch(windows):
+    """windows: dicts with the keyword arguments of realign_reads -> one list of (position, cigar) per window."""
+    lib = _ffi.lib()
+    nw = len(windows)
+    if nw == 0:
+        return []
+    arr, keep, total = _window_array(windows)
     out_pos = (ct.c_int32 * max(total, 1))()
     out_cig = (ct.c_char_p * max(total, 1))()
     lib.mpn_realign_batch.restype = ct.c_int

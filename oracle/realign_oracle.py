@@ -341,11 +341,10 @@ def positions_map(hap_len, cigar):
     return pm
 
 
-def realign_reads(seqs, positions, cigars, reference, haplotypes, ref_start, ref_prefix, ref_suffix):
-    """-> [(position, cigar_string), ...] per read (realigner.cpp:782-850, AlignReads :88-117)."""
+def fast_align_reads_to_haplotypes(seqs, reference, haplotypes, ref_prefix, ref_suffix):
+    """BuildIndex + FastAlignReadsToHaplotypes -> per haplotype dict(index, score, reads=[dict(position, cigar, score)], ...)
+    as AlignReads holds them before any Smith-Waterman step."""
     n = len(seqs)
-    thr = MATCH * READ_SIZE * SIMILARITY - MISMATCH * READ_SIZE * (1 - SIMILARITY)
-    thr = 1 if thr < 0 else int(thr)
     # BuildIndex (:429-451)
     index = {}
     for rid, read in enumerate(seqs):
@@ -383,12 +382,22 @@ def realign_reads(seqs, positions, cigars, reference, haplotypes, ref_start, ref
                         hap_score += sc - old
                         ra['position'] = start
                         ra['cigar'] = '%d=' % size
-            if coverage[i] == 0 and i >= ref_prefix and i < len(hap) - ref_suffix and not is_ref:
+            # (the right side is size_t: a ref_suffix above the haplotype's length wraps, and the test holds for every i)
+            if coverage[i] == 0 and i >= ref_prefix and i < (len(hap) - ref_suffix) % (1 << 64) and not is_ref:
                 hap_score = 0
                 break
         if hap_score == 0:
             al = [dict(position=NOT_ALIGNED, cigar='', score=0) for _ in range(n)]
         haps.append(dict(index=hi, score=hap_score, reads=al, cigar='', ops=[], ref_pos=0, is_ref=False, pmap=[]))
+    return haps
+
+
+def realign_reads(seqs, positions, cigars, reference, haplotypes, ref_start, ref_prefix, ref_suffix):
+    """-> [(position, cigar_string), ...] per read (realigner.cpp:782-850, AlignReads :88-117)."""
+    n = len(seqs)
+    thr = MATCH * READ_SIZE * SIMILARITY - MISMATCH * READ_SIZE * (1 - SIMILARITY)
+    thr = 1 if thr < 0 else int(thr)
+    haps = fast_align_reads_to_haplotypes(seqs, reference, haplotypes, ref_prefix, ref_suffix)
     # AlignHaplotypesToReference (:325-349)
     ref_codes = translate(reference)
     for h in haps:

@@ -2,7 +2,7 @@
 compiled in place by oracle/Makefile (oracle/_ref/librealigner.so), called through its C entry points `realign_reads` /
 `free_memory` exactly as /root/reference/bin/realignment/realign_illumina_reads.py:596-629 does, on the seeded windows of
 tests/realign_cases.py.  Only inputs and outputs are stored.  Also writes realign_random_golden.json: the outputs on the random windows of
-tests/test_realign_oracle.py.
+tests/test_realign_oracle.py, and realign_place_golden.json: the outputs on the constructed windows of tests/realign_place_cases.py.
 
     make -C oracle && python tests/golden/make_realign_golden.py
 """
@@ -31,3 +31,11 @@ with open(os.path.join(HERE, 'realign_random_golden.json'), 'w') as f:
     json.dump(dict(source='reference realigner via oracle/_ref/librealigner.so', windows='realign_cases.random_window_kwargs()',
                    expected=rand), f, separators=(',', ':'))
 print('wrote', len(rand), 'random windows')
+# outputs only on the constructed windows of the placement stage's tests (tests/realign_place_cases.py), by family/name
+import realign_place_cases as pc  # noqa: E402
+place = {f + '/' + n: [[p, cg] for p, cg in ref_realign(**w)] for f, n, w in pc.make_cases()}
+place['overflow/all_a'] = [[p, cg] for p, cg in ref_realign(**pc.all_a_window())]
+with open(os.path.join(HERE, 'realign_place_golden.json'), 'w') as f:
+    json.dump(dict(source='reference realigner via oracle/_ref/librealigner.so', windows='realign_place_cases.make_cases(), all_a_window()',
+                   expected=place), f, separators=(',', ':'))
+print('wrote', len(place), 'constructed windows')

@@ -23,7 +23,7 @@ def declared_symbols():
 def test_headers_declare_something():
     syms = declared_symbols()
     assert {'ssw_init', 'ssw_align', 'init_destroy', 'align_destroy', 'mpn_ssw_align_batch', 'mpn_last_error', 'realign_reads',
-            'free_memory', 'mpn_realign_batch', 'mpn_realign_free_cigars'} <= syms
+            'free_memory', 'mpn_realign_batch', 'mpn_realign_free_cigars', 'mpn_realign_place_batch'} <= syms
 
 
 def test_library_exports_all_declared_symbols(libmpn):
