@@ -15,6 +15,7 @@ written by megapath_nano_amd.bam.
 import hashlib
 import os
 import random
+import sys
 
 import numpy as np
 import pandas
@@ -592,6 +593,54 @@ def align_table(batches, *, assembly_metadata, global_options, target_assembly_l
     return align_list.assign(alignment_score_tiebreaker=random_block(random, align_list.shape[0]))
 
 
+class _DeviceBam:
+    """Align()'s use of bam.DeviceBamBuilder under MPN_BAM_WRITER=device: the header, then every batch's SAM text; finish() -> True if
+    <prefix>.bam and .bam.bai were written.  A DeviceRefused, at any point, goes to the log and ends the device path: the caller
+    then runs the host writer on the .sam."""
+
+    def __init__(self, exclude_flags, log_file):
+        self.exclude, self.log_file, self.builder, self.refused = exclude_flags, log_file, None, False
+
+    def _refuse(self, e):
+        msg = f'MPN_BAM_WRITER=device: {e}; the host writer takes over'
+        print(msg, file=self.log_file if hasattr(self.log_file, 'write') else sys.stderr)
+        self.refused = True
+        if self.builder:
+            self.builder.close()
+            self.builder = None
+
+    def header(self, text):
+        from . import bam
+        lines = text.splitlines(keepends=True)
+        names, lens = bam.parse_header(lines)
+        try:
+            self.builder = bam.DeviceBamBuilder(names, lens, bam.sorted_header_text(lines), self.exclude)
+        except bam.DeviceRefused as e:
+            self._refuse(e)
+
+    def batch(self, sam_text):
+        from . import bam
+        if self.builder and sam_text:
+            try:
+                self.builder.add_text(sam_text.encode())
+            except bam.DeviceRefused as e:
+                self._refuse(e)
+
+    def finish(self, bam_path):
+        from . import bam
+        if not self.builder:
+            return False
+        try:
+            self.builder.finish(bam_path)
+            return True
+        except bam.DeviceRefused as e:
+            self._refuse(e)
+            return False
+        finally:
+            if self.builder:
+                self.builder.close()
+
+
 def Align(*, assembly_metadata, global_options, temp_dir_name, log_file, query_filename_list=None,
           query_assembly_list=None, target_filename_list=None, target_assembly_list=None, aligner_options=None,
           paf_path_and_prefix=None, mapping_only=False, module_option='', AMR_output_folder='', align_concat_fa=False,
@@ -614,19 +663,36 @@ def Align(*, assembly_metadata, global_options, temp_dir_name, log_file, query_f
         how = os.environ.get('MPN_BGZF', 'zlib')
         if how not in ('zlib', 'device'):
             raise ValueError(f'MPN_BGZF={how}: expected zlib or device')
-        # PAF and SAM go to disk batch by batch: nothing but the integer columns of a batch is kept in memory
-        with open(f'{paf_path_and_prefix}.paf', 'w') as paf_f, open(f'{paf_path_and_prefix}.sam', 'w') as sam_f:
-            batches, header = map_files(target_paths, query_paths, options, want_paf=True, want_sam=True, want_cols=True,
-                                        read_batch_bases=batch_bases, cache_key=cache_key, on_header=sam_f.write,
-                                        on_batch=lambda b: (paf_f.write(b.paf), sam_f.write(b.sam)))
-        print('Finished species alignment step.')                                                        # aligner.py:244
+        # MPN_BAM_WRITER=device: every batch's SAM text goes to the GPU as it is written, the records stay there until they are sorted
+        # and deflated (bam.DeviceBamBuilder), and the SAM is not read back; MPN_BGZF is then not looked at -- the deflate is the
+        # device's.  Unset or `host`: bam.sam_to_sorted_bam on the finished .sam
+        writer = os.environ.get('MPN_BAM_WRITER', 'host')
+        if writer not in ('host', 'device'):
+            raise ValueError(f'MPN_BAM_WRITER={writer}: expected host or device')
         from . import abundance, bam
         # samtools view -F<flags> -b | samtools sort; samtools index (aligner.py:245-252): 1796 = unmapped | secondary | QC fail |
         # duplicate; the amplicon filter keeps everything that is mapped
         exclude = 4 if module_option == 'amplicon_filter_module' else 1796
-        bam.sam_to_sorted_bam(f'{paf_path_and_prefix}.sam', f'{paf_path_and_prefix}.bam', exclude_flags=exclude,
-                              sort_keys=abundance.device_sort_order,   # the coordinate sort runs on the GPU (mpn_sort_order)
-                              compress_blocks=bam.device_bgzf_blocks if how == 'device' else None)
+        dev = _DeviceBam(exclude, log_file) if writer == 'device' else None
+        # PAF and SAM go to disk batch by batch: nothing but the integer columns of a batch is kept in memory
+        with open(f'{paf_path_and_prefix}.paf', 'w') as paf_f, open(f'{paf_path_and_prefix}.sam', 'w') as sam_f:
+            def on_header(text):
+                sam_f.write(text)
+                if dev:
+                    dev.header(text)
+
+            def on_batch(b):
+                paf_f.write(b.paf)
+                sam_f.write(b.sam)
+                if dev:
+                    dev.batch(b.sam)
+            batches, header = map_files(target_paths, query_paths, options, want_paf=True, want_sam=True, want_cols=True,
+                                        read_batch_bases=batch_bases, cache_key=cache_key, on_header=on_header, on_batch=on_batch)
+        print('Finished species alignment step.')                                                        # aligner.py:244
+        if not (dev and dev.finish(f'{paf_path_and_prefix}.bam')):
+            bam.sam_to_sorted_bam(f'{paf_path_and_prefix}.sam', f'{paf_path_and_prefix}.bam', exclude_flags=exclude,
+                                  sort_keys=abundance.device_sort_order,   # the coordinate sort runs on the GPU (mpn_sort_order)
+                                  compress_blocks=bam.device_bgzf_blocks if how == 'device' or dev else None)
         if module_option in ('taxon_and_AMR_module', 'AMR_module_only'):                                # aligner.py:250-256
             _run_amr(global_options, f'{paf_path_and_prefix}.bam', AMR_output_folder, log_file)
         if module_option in ('AMR_module_only', 'amplicon_filter_module'):                               # aligner.py:257-259

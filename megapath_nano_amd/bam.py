@@ -8,6 +8,9 @@ bam_write1, bgzf.c, hts.c hts_idx_push / hts_idx_finish): smallest integer type 
 BGZF blocks unless it is larger than one, the index's pseudo-bin 37450, bins with less than 64 KiB of compressed span
 folded into their parents, chunks that start in the block the previous one ends in merged.  The reference's own htslib
 test data pin this module (tests/golden/htslib).
+
+The last part of the file is the opt-in device writer (sam_to_sorted_bam_device, DeviceBamBuilder over include/mpn_bam.h's
+mpn_bam_out_*): the same two files, byte for byte, with the records resident on the GPU from the SAM text to the deflated blocks.
 """
 import struct
 import zlib
@@ -519,3 +522,201 @@ class NativeEncoder:
         if self.h:
             self.lib.mpn_bam_encoder_destroy(self.h)
             self.h = None
+
+
+# ---- the device writer (include/mpn_bam.h: mpn_bam_out_*, csrc/bam_out_kernels.hip) ---------------------------------------------------
+POOL_BYTES_DEFAULT = 16 << 30
+STAGES = ('text upload', 'scan', 'encode', 'sort', 'gather', 'deflate', 'download', 'file writes', 'cut + BAI')
+_out_bound = False
+
+
+class DeviceRefused(Exception):
+    """The device writer does not take this input: a line it would have to guess about (line: its 1-based number in the text,
+    status: an MPN_SAM_* code of include/mpn_bam.h), or a record pool that would pass its limit.  Nothing has been written; the
+    host writer (sam_to_sorted_bam) takes everything."""
+
+    def __init__(self, line, status, text):
+        super().__init__(f'SAM line {line}: {text}')
+        self.line, self.status, self.text = line, status, text
+
+
+def _out_lib():
+    import ctypes as ct
+    from . import _ffi
+    global _out_bound
+    lib = _ffi.lib()
+    if not _out_bound:
+        P, PP = ct.c_void_p, ct.POINTER(ct.c_char_p)
+        lib.mpn_sam_status_text.argtypes = [ct.c_int32]
+        lib.mpn_sam_status_text.restype = ct.c_char_p
+        lib.mpn_sam_encode_batch.argtypes = [PP, ct.c_int32, ct.c_char_p, P, P, ct.c_int64, ct.c_int32, P, ct.c_int64] + [P] * 6
+        lib.mpn_sam_encode_batch.restype = ct.c_int64
+        lib.mpn_bai_build.argtypes = [ct.c_int32, ct.c_int64, P, P, P, P, P, ct.c_uint64, ct.c_uint64, P, ct.c_int64, P]
+        lib.mpn_bai_build.restype = ct.c_int64
+        lib.mpn_bam_out_create.argtypes = [PP, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64]
+        lib.mpn_bam_out_create.restype = P
+        lib.mpn_bam_out_destroy.argtypes = [P]
+        lib.mpn_bam_out_destroy.restype = None
+        lib.mpn_bam_out_add_text.argtypes = [P, ct.c_char_p, ct.c_int64]
+        lib.mpn_bam_out_add_text.restype = ct.c_int32
+        lib.mpn_bam_out_refusal.argtypes = [P, P, P]
+        lib.mpn_bam_out_refusal.restype = ct.c_int32
+        lib.mpn_bam_out_finish.argtypes = [P, ct.c_char_p, ct.c_int64, ct.c_char_p, ct.c_char_p]
+        lib.mpn_bam_out_finish.restype = ct.c_int64
+        lib.mpn_bam_out_stage_ms.argtypes = [P, P]
+        lib.mpn_bam_out_stage_ms.restype = None
+        _out_bound = True
+    return lib
+
+
+def _name_array(ref_names):
+    import ctypes as ct
+    return (ct.c_char_p * max(1, len(ref_names)))(*[n_.encode() for n_ in ref_names])
+
+
+def status_text(status):
+    return _out_lib().mpn_sam_status_text(int(status)).decode()
+
+
+def device_encode_lines(ref_names, lines, exclude_flags=0, pad=0):
+    """The stage entry mpn_sam_encode_batch: lines (bytes each) through the writer's scan and encode kernels ->
+    [(status, tid, pos0, end0, flag, record bytes)]; a line whose status is not 0 has no bytes.  pad: bytes in front of the first
+    line, so that the lines start at chosen places mod 16."""
+    import numpy as np
+    from . import _ffi
+    lib, n = _out_lib(), len(lines)
+    text = b'\n' * pad + b''.join(lines)
+    lens = np.fromiter((len(l) for l in lines), dtype=np.int32, count=n)
+    offs = np.full(max(n, 1), pad, dtype=np.int64)[:n]
+    if n > 1:
+        offs[1:] += np.cumsum(lens[:-1], dtype=np.int64)
+    rec_off = np.zeros(n + 1, dtype=np.int64)
+    tid, pos0, end0, flag, status = (np.zeros(n, dtype=np.int32) for _ in range(5))
+    cap = 0
+    while True:
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        r = lib.mpn_sam_encode_batch(_name_array(ref_names), len(ref_names), text, _ffi.ptr(offs), _ffi.ptr(lens), n, exclude_flags,
+                                     out.ctypes.data, cap, rec_off.ctypes.data, *(_ffi.ptr(a) for a in (tid, pos0, end0, flag, status)))
+        if r == -3:
+            cap = int(rec_off[n])
+            continue
+        if r < 0:
+            raise _ffi.MpnError(f'mpn_sam_encode_batch failed (rc={r}): {_ffi.hint(_ffi.last_error())}')
+        break
+    buf, ro = out.tobytes(), rec_off.tolist()
+    return [(int(status[i]), int(tid[i]), int(pos0[i]), int(end0[i]), int(flag[i]), buf[ro[i]:ro[i + 1]]) for i in range(n)]
+
+
+def native_bai(n_ref, tid, pos0, end0, voff_after, mapped, voff_first, voff_end):
+    """mpn_bai_build: BaiBuilder in C++ over records in file order with their real virtual offsets -> the bytes of the .bai"""
+    import ctypes as ct
+    import numpy as np
+    from . import _ffi
+    lib = _out_lib()
+    arrs = [np.ascontiguousarray(a, dtype=t) for a, t in ((tid, np.int32), (pos0, np.int32), (end0, np.int32), (voff_after, np.uint64), (mapped, np.uint8))]
+    need = ct.c_int64(0)
+    args = [n_ref, len(arrs[0])] + [_ffi.ptr(a) for a in arrs] + [voff_first, voff_end]
+    lib.mpn_bai_build(*args, None, 0, ct.byref(need))
+    out = np.empty(need.value, dtype=np.uint8)
+    r = lib.mpn_bai_build(*args, out.ctypes.data, need.value, ct.byref(need))
+    if r < 0:
+        raise _ffi.MpnError(f'mpn_bai_build failed (rc={r}): {_ffi.last_error()}')
+    return out.tobytes()
+
+
+class DeviceBamBuilder:
+    """SAM text in, batch by batch (add_text), sorted BAM + BAI out (finish), with the records resident on the GPU in between: what
+    sam_to_sorted_bam(sort_keys=abundance.device_sort_order, compress_blocks=device_bgzf_blocks) writes, byte for byte, without
+    reading the SAM back.  header_text: the header the file gets (finish puts nothing in front of it).  add_text and finish raise
+    DeviceRefused for input the device does not take, before any file is opened."""
+
+    def __init__(self, ref_names, ref_lens, header_text, exclude_flags=0, chunk_bytes=None, pool_bytes=None):
+        import os
+        from . import _ffi, ingest
+        self.h = None
+        if len(set(ref_names)) != len(ref_names):
+            raise DeviceRefused(0, 0, 'two references of the same name')      # (the host's dictionary keeps the last, the name set the first)
+        self.lib = _out_lib()
+        self.ref_names, self.ref_lens, self.header_text = list(ref_names), list(ref_lens), header_text
+        chunk = ingest.batch_bytes() if chunk_bytes is None else int(chunk_bytes)
+        pool = int(os.environ.get('MPN_BAM_POOL_BYTES', POOL_BYTES_DEFAULT)) if pool_bytes is None else int(pool_bytes)
+        self.h = self.lib.mpn_bam_out_create(_name_array(ref_names), len(ref_names), exclude_flags, min(max(chunk, 1), 0x7fffffff), pool)
+        if not self.h:
+            raise _ffi.MpnError('mpn_bam_out_create: ' + _ffi.hint(_ffi.last_error()))
+
+    def _refused(self):
+        import ctypes as ct
+        line, status = ct.c_int64(0), ct.c_int32(0)
+        self.lib.mpn_bam_out_refusal(self.h, ct.byref(line), ct.byref(status))
+        return DeviceRefused(line.value, status.value, status_text(status.value))
+
+    def add_text(self, data):
+        from . import _ffi
+        r = self.lib.mpn_bam_out_add_text(self.h, data, len(data))
+        if r == 1:
+            raise self._refused()
+        if r != 0:
+            raise _ffi.MpnError(f'mpn_bam_out_add_text failed (rc={r}): {_ffi.hint(_ffi.last_error())}')
+
+    def finish(self, bam_path, index=True):
+        """-> the number of records written"""
+        from . import _ffi
+        text = self.header_text.encode()
+        hdr = bytearray(b'BAM\1' + struct.pack('<i', len(text)) + text + struct.pack('<i', len(self.ref_names)))
+        for nm, ln in zip(self.ref_names, self.ref_lens):
+            hdr += struct.pack('<i', len(nm) + 1) + nm.encode() + b'\0' + struct.pack('<i', ln)
+        r = self.lib.mpn_bam_out_finish(self.h, bytes(hdr), len(hdr), bam_path.encode(), (bam_path + '.bai').encode() if index else None)
+        if r == -4:
+            raise self._refused()
+        if r < 0:
+            raise _ffi.MpnError(f'mpn_bam_out_finish failed (rc={r}): {_ffi.hint(_ffi.last_error())}')
+        return r
+
+    def stage_ms(self):
+        """{stage: milliseconds so far} (STAGES)"""
+        import ctypes as ct
+        v = (ct.c_double * len(STAGES))()
+        self.lib.mpn_bam_out_stage_ms(self.h, v)
+        return dict(zip(STAGES, v))
+
+    def close(self):
+        if self.h:
+            self.lib.mpn_bam_out_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def sorted_header_text(header_lines):
+    """The header sam_to_sorted_bam writes: @HD VN:1.6 SO:coordinate, then the lines that are no @HD"""
+    return '@HD\tVN:1.6\tSO:coordinate\n' + ''.join(l for l in header_lines if not l.startswith('@HD'))
+
+
+def sam_to_sorted_bam_device(sam_path, bam_path, exclude_flags=0, index=True, chunk_bytes=None, pool_bytes=None):
+    """sam_to_sorted_bam with the records on the GPU from parse to deflate (DeviceBamBuilder): the same two files as
+    sam_to_sorted_bam(..., sort_keys=abundance.device_sort_order, compress_blocks=device_bgzf_blocks), byte for byte.  Raises
+    DeviceRefused (the line, the reason) before a byte of either file is written.  -> the number of records."""
+    from . import ingest
+    header = []
+    with open(sam_path, 'rb') as f:
+        body = 0
+        for raw in f:                              # the header: the lines in front of the first record
+            if raw[:1] == b'@':
+                header.append(raw.decode())
+            elif raw.strip():
+                break
+            body += len(raw)
+        names, lens = parse_header(header)
+        b = DeviceBamBuilder(names, lens, sorted_header_text(header), exclude_flags, chunk_bytes, pool_bytes)
+        try:
+            f.seek(0)                              # (the device skips header lines itself, and counts them)
+            step = max(1 << 16, min(ingest.batch_bytes() if chunk_bytes is None else int(chunk_bytes), 1 << 28))
+            while True:
+                data = f.read(step)
+                if not data:
+                    break
+                b.add_text(data)
+            return b.finish(bam_path, index=index)
+        finally:
+            b.close()

@@ -24,6 +24,7 @@
 // L2 for 64 KiB of payload.  LDS 46 KiB per workgroup (below the 64 KiB every runtime grants; 3 workgroups share a CU).
 #include "mpn_common.h"
 #include "crc32_poly.h"
+#include "bgzf_resident.h"
 #include "../../include/mpn_bam.h"
 
 #include <cstring>
@@ -474,40 +475,48 @@ extern "C" int64_t mpn_bgzf_compress(int64_t n_blocks, const uint8_t *payload, c
     const int64_t pay_bytes = pay_off[n_blocks] - pay_off[0];
     if (pay_bytes > 0 && !payload) { set_error("mpn_bgzf_compress: bad arguments"); return -2; }
     hipStream_t st = 0;
-    DevBuf<uint8_t> d_pay, d_slots, d_out;
-    DevBuf<int64_t> d_po, d_oo;
-    DevBuf<uint32_t> d_tok;
-    DevBuf<int32_t> d_sizes;
-    DevBuf<int> d_flag;
-    const int64_t chunk = std::min<int64_t>(n_blocks, BZ_CHUNK);
-    DevTimer tm_deflate, tm_pack;
+    DevBuf<uint8_t> d_pay;
+    DevBuf<int64_t> d_po;
+    BgzfWork w;
+    DevTimer tm_pack;
     tl_bgzf_ms[0] = tl_bgzf_ms[1] = 0;
-    if (d_pay.upload(payload + pay_off[0], (size_t)pay_bytes, st) || d_po.upload(pay_off, (size_t)n_blocks + 1, st) ||
-        d_slots.alloc((size_t)(pay_bytes + BZ_SLOT_EXTRA * n_blocks)) || d_oo.alloc((size_t)n_blocks + 1) || d_sizes.alloc((size_t)n_blocks) ||
-        d_flag.alloc(1) || (mode != MPN_BGZF_STORED && d_tok.alloc((size_t)chunk * BZ_TOK_STRIDE)) || tm_deflate.start(st))
-        return -1;
-    for (int64_t b0 = 0; b0 < n_blocks; b0 += chunk) {   // launches on one stream run one after another: they share the token rows
-        const int g = (int)std::min<int64_t>(chunk, n_blocks - b0);
-        hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(g), dim3(BZ_THREADS), 0, st, (const uint8_t *)d_pay.p, (const int64_t *)d_po.p, b0, d_slots.p, d_tok.p,
-                           d_sizes.p, (int)mode);
-    }
-    hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)d_sizes.p, n_blocks, d_oo.p, d_flag.p);
-    MPN_HIP_CHECK(hipGetLastError());
-    if (tm_deflate.stop(st)) return -1;
-    int flag = 0;
-    if (d_oo.download(out_off, (size_t)n_blocks + 1, st) || d_flag.download(&flag, 1, st)) return -1;
-    MPN_HIP_CHECK(hipStreamSynchronize(st));
-    if (tm_deflate.elapsed_ms(&tl_bgzf_ms[0])) return -1;
-    if (flag) { set_error("mpn_bgzf_compress: a block's emitted bits disagree with its computed size"); return -1; }
-    const int64_t total = out_off[n_blocks];
+    if (d_pay.upload(payload + pay_off[0], (size_t)pay_bytes, st) || d_po.upload(pay_off, (size_t)n_blocks + 1, st)) return -1;
+    const int64_t total = bgzf_deflate_resident(d_pay.p, pay_bytes, d_po.p, n_blocks, mode, st, w, out_off);
+    if (total < 0) return -1;
     if (total > out_cap) { set_error("mpn_bgzf_compress: out_cap %lld is below the %lld bytes needed", (long long)out_cap, (long long)total); return -3; }
-    if (d_out.alloc((size_t)total) || tm_pack.start(st)) return -1;
-    hipLaunchKernelGGL(bgzf_pack_kernel, dim3((unsigned)n_blocks), dim3(BZ_THREADS), 0, st, (const uint8_t *)d_slots.p, (const int64_t *)d_po.p,
-                       (const int64_t *)d_oo.p, d_out.p);
-    MPN_HIP_CHECK(hipGetLastError());
-    if (tm_pack.stop(st)) return -1;
-    if (d_out.download(out, (size_t)total, st)) return -1;
+    if (bgzf_pack_resident(d_po.p, n_blocks, total, st, w, tm_pack)) return -1;
+    if (w.out.download(out, (size_t)total, st)) return -1;
     MPN_HIP_CHECK(hipStreamSynchronize(st));
     if (tm_pack.elapsed_ms(&tl_bgzf_ms[1])) return -1;
     return total;
+}
+
+int64_t mpn::bgzf_deflate_resident(const uint8_t *d_pay, int64_t pay_bytes, const int64_t *d_po, int64_t n_blocks, int32_t mode, hipStream_t st,
+                                   BgzfWork &w, int64_t *out_off) {
+    const int64_t chunk = std::min<int64_t>(n_blocks, BZ_CHUNK);
+    DevTimer tm_deflate;
+    if (w.slots.alloc((size_t)(pay_bytes + BZ_SLOT_EXTRA * n_blocks)) || w.oo.alloc((size_t)n_blocks + 1) || w.sizes.alloc((size_t)n_blocks) ||
+        w.flag.alloc(1) || (mode != MPN_BGZF_STORED && w.tok.alloc((size_t)chunk * BZ_TOK_STRIDE)) || tm_deflate.start(st))
+        return -1;
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += chunk) {   // launches on one stream run one after another: they share the token rows
+        const int g = (int)std::min<int64_t>(chunk, n_blocks - b0);
+        hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(g), dim3(BZ_THREADS), 0, st, d_pay, d_po, b0, w.slots.p, w.tok.p, w.sizes.p, (int)mode);
+    }
+    hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)w.sizes.p, n_blocks, w.oo.p, w.flag.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    if (tm_deflate.stop(st)) return -1;
+    int flag = 0;
+    if (w.oo.download(out_off, (size_t)n_blocks + 1, st) || w.flag.download(&flag, 1, st)) return -1;
+    MPN_HIP_CHECK(hipStreamSynchronize(st));
+    if (tm_deflate.elapsed_ms(&tl_bgzf_ms[0])) return -1;
+    if (flag) { set_error("mpn_bgzf_compress: a block's emitted bits disagree with its computed size"); return -1; }
+    return out_off[n_blocks];
+}
+
+int mpn::bgzf_pack_resident(const int64_t *d_po, int64_t n_blocks, int64_t total, hipStream_t st, BgzfWork &w, DevTimer &tm) {
+    if (w.out.alloc((size_t)total) || tm.start(st)) return -1;
+    hipLaunchKernelGGL(bgzf_pack_kernel, dim3((unsigned)n_blocks), dim3(BZ_THREADS), 0, st, (const uint8_t *)w.slots.p, d_po, (const int64_t *)w.oo.p, w.out.p);
+    MPN_HIP_CHECK(hipGetLastError());
+    if (tm.stop(st)) return -1;
+    return 0;
 }

@@ -6,38 +6,11 @@
 //                          gather16.h at any alignment; ns_hash, then ns_find along the probe chain.  A slot is one 16-byte load; the
 //                          pooled name is loaded (aligned words) only behind a slot whose hash and length are the id's.
 // Every vector that is loaded from the text holds at least one byte of an id the host has checked against text_len.
-#include "gather16.h"
-#include "name_set_core.h"
-
-struct mpn_name_set {
-    mpn::NsSlot *d_table = nullptr;
-    uint4 *d_pool = nullptr;
-    int64_t slots = 0, n = 0, distinct = 0;
-};
+#include "name_set_dev.h"
 
 namespace mpn {
 
 thread_local double tl_lookup_ms = 0;    // device time of the last mpn_fastq_name_lookup on this thread
-
-struct NsTextWords {      // the words of the id at byte o of the aligned vectors base
-    const uint4 *__restrict__ base;
-    int64_t o;
-    int32_t len;
-    __device__ __forceinline__ NsWord operator()(uint32_t k) const {
-        const int64_t b = o + 16 * (int64_t)k;
-        const uint4 *p = base + (b >> 4);
-        const uint32_t sh = (uint32_t)(b & 15), left = (uint32_t)len - 16 * k;
-        const uint4 v = left >= 16 ? load16_at(p, sh) : load16_head(p, sh, left);
-        return NsWord{v.x, v.y, v.z, v.w};
-    }
-};
-struct NsDevPool {
-    const uint4 *__restrict__ pool;
-    __device__ __forceinline__ NsWord operator()(uint32_t k) const {
-        const uint4 v = pool[k];
-        return NsWord{v.x, v.y, v.z, v.w};
-    }
-};
 
 // text_al: the text's pointer rounded down to 16 bytes, shift: what was taken off it
 __global__ __launch_bounds__(256) void name_lookup_kernel(const uint4 *__restrict__ text_al, int64_t shift, const mpn_fastq_head *__restrict__ heads,
