@@ -1,9 +1,11 @@
 // mpn_map_batch: chains -> hits -> base-level extension -> MAPQ -> PAF  (include/mpn_map.h).
 //
 // Device work: seed/chain kernels (map_kernels.h) and the extension kernels (ext_kernels.h).
-// Host work (this file, multi-threaded over reads): the per-read hit bookkeeping of minimap2's hit.c/align.c --
-// ranking chains, primary/secondary marking, long-join, planning the DP windows of every hit, stitching the
-// CIGARs the GPU returns, MAPQ (float logf, evaluated on the host so that it is libm-exact) and PAF text.
+// This file holds what touches the device or orders the stages: the workers' slots, the extension rounds (planning, DP groups,
+// stitching, finishing), the hit stage's dispatch, the pipeline over sub-batches and the mpn_map_* entries.  The host-only
+// logic lives in units of its own that a host compiler builds: the per-read hit bookkeeping of minimap2's hit.c and MAPQ
+// (float logf, evaluated on the host so that it is libm-exact) in hit_host.cpp, the hits accumulator and its wire format in
+// hits_block.cpp, the thread pool of the host phases in host_pool.cpp, and PAF / SAM text in aln_text.cpp.
 // All DP windows of a batch are planned up front and run as independent GPU jobs (one wavefront each); a hit
 // whose alignment z-drops is split and its remainder goes through another round.
 #include "map_types.h"
@@ -14,6 +16,9 @@
 #include "plan_kernels.h"
 #include "hit_kernels.h"
 #include "mapper_internal.h"
+#include "hit_host.h"
+#include "host_pool.h"
+#include "aln_text.h"
 #include "../../include/mpn_map.h"
 #include "../../include/mpn_ssw.h"
 
@@ -45,665 +50,6 @@ int download_chains(int n, SeedChainOut &o, HostChains &h, PoolBuf &pin_u, PoolB
 int download_chain_records(SeedChainOut &o, HostChains &h, PoolBuf &pin_u, StreamLease &st);
 
 const char *get_error();
-
-static bool g_cpu_on = false;                 // MPN_DEBUG_CPU=1: thread CPU time of every parallel region, by tag
-static std::atomic<long long> g_cpu_ns[32];
-static const int PARENT_UNSET = -1, PARENT_TMP_PRI = -2;
-static const uint64_t SEED_LONG_JOIN = 1ULL << 40, SEED_IGNORE = 1ULL << 41, SEED_TANDEM = 1ULL << 42;
-
-struct Reg {
-    int32_t id = 0, cnt = 0, rid = 0, score = 0, qs = 0, qe = 0, rs = 0, re = 0, parent = PARENT_UNSET, subsc = 0, as = 0;
-    int32_t mlen = 0, blen = 0, n_sub = 0, score0 = 0;
-    uint32_t mapq = 0, split = 0, rev = 0, inv = 0, sam_pri = 0, split_inv = 0, hash = 0;
-    int32_t has_p = 0, dp_score = 0, dp_max = 0, dp_max2 = 0, n_ambi = 0;
-    std::vector<uint32_t> cigar;   // with MPN_TAG_EQX: its M ops already split into = (7) and X (8)
-    std::string cs, md;            // cs:Z / MD:Z strings of the alignment (tag_kernels.h), when the call asked for them
-    int32_t aligned = 0;  // base-level extension already done (or not needed)
-    int32_t fin_qs = 0, fin_rs = 0, fin_ql = 0, fin_tl = 0;   // an inversion hit before its extension: the window to extend
-    int32_t fin_idx = -1;  // >= 0: stitched this round (its index among the round's hits): CIGAR fix-up and statistics are due
-    // The hit's first and last chained anchor (the anchors themselves stay in HBM: chain_backtrack_kernel's ChainRec) and, until
-    // the squeeze, where its chain lies in the chain stage's pool (relative to the read's b_pos) and its segment of the squeeze
-    uint64_t fx = 0, fy = 0, lx = 0, ly = 0;
-    int64_t src = 0;
-    int32_t seg = -1;
-};
-
-static inline uint64_t hash64(uint64_t key) {
-    key = ~key + (key << 21);
-    key = key ^ key >> 24;
-    key = (key + (key << 3)) + (key << 8);
-    key = key ^ key >> 14;
-    key = (key + (key << 2)) + (key << 4);
-    key = key ^ key >> 28;
-    key = key + (key << 31);
-    return key;
-}
-static inline uint32_t wang32(uint32_t key) {
-    key += ~(key << 15); key ^= (key >> 10); key += (key << 3);
-    key ^= (key >> 6); key += ~(key << 11); key ^= (key >> 16);
-    return key;
-}
-static inline uint32_t x31_hash(const char *s) {
-    uint32_t h = (uint32_t)(unsigned char)*s;
-    if (h) for (++s; *s; ++s) h = (h << 5) - h + (uint32_t)(unsigned char)*s;
-    return h;
-}
-
-// mm_reg_set_coor from the hit's first and last anchor (the approximate lengths of mm_cal_fuzzy_len come with the chain
-// record, or are combined from two hits' when they are joined)
-static void reg_set_coor(Reg &r, int32_t qlen) {
-    const int32_t q_span = (int32_t)(r.fy >> 32 & 0xff);
-    r.rev = r.fx >> 63;
-    r.rid = r.fx << 1 >> 33;
-    r.rs = (int32_t)r.fx + 1 > q_span ? (int32_t)r.fx + 1 - q_span : 0;
-    r.re = (int32_t)r.lx + 1;
-    if (!r.rev) { r.qs = (int32_t)r.fy + 1 - q_span; r.qe = (int32_t)r.ly + 1; }
-    else { r.qs = qlen - ((int32_t)r.ly + 1); r.qe = qlen - ((int32_t)r.fy + 1 - q_span); }
-}
-
-// Per-thread scratch of the per-read hit bookkeeping: a few hundred thousand reads per step each need a handful of small
-// arrays; allocating them per read costs more than the work on them.
-struct HitScratch {
-    std::vector<uint64_t> cov;
-    std::vector<int> w, idx;
-    std::vector<std::pair<uint64_t, int>> aux;
-    std::vector<int32_t> order;
-    std::vector<int64_t> src;
-};
-static thread_local HitScratch tl_hs;
-
-// Chain c of a read in the order of the first anchors (the order minimap2's chaining leaves them in, HostChains::chain_order):
-// its (score, count) word, its record and the start of its anchors relative to the read's slice of the chain pool
-struct ChainIn { uint64_t u; const ChainRec *rec; int64_t src; };
-
-static void gen_regs(uint32_t hash, int qlen, int n_u, const ChainIn *c, std::vector<Reg> &regs) {
-    struct Z { uint64_t x, y; int i; };
-    static thread_local std::vector<Z> z;
-    z.resize((size_t)n_u);
-    int k = 0;
-    for (int i = 0; i < n_u; ++i) {
-        const uint32_t h = (uint32_t)hash64((hash64(c[i].rec->fx) + hash64(c[i].rec->fy)) ^ hash);
-        z[i].x = c[i].u ^ h;
-        z[i].y = (uint64_t)k << 32 | (uint32_t)(int32_t)c[i].u;
-        z[i].i = i;
-        k += (int32_t)c[i].u;
-    }
-    std::sort(z.begin(), z.end(), [](const Z &p, const Z &q) { return p.x != q.x ? p.x < q.x : p.y < q.y; });
-    regs.assign(n_u, Reg());
-    for (int i = 0; i < n_u; ++i) {
-        Reg &ri = regs[i];
-        const Z &zi = z[n_u - 1 - i];
-        const ChainRec &rc = *c[zi.i].rec;
-        ri.id = i;
-        ri.parent = PARENT_UNSET;
-        ri.score = ri.score0 = (int32_t)(zi.x >> 32);
-        ri.hash = (uint32_t)zi.x;
-        ri.cnt = (int32_t)zi.y;
-        ri.as = (int32_t)(zi.y >> 32);
-        ri.fx = rc.fx; ri.fy = rc.fy; ri.lx = rc.lx; ri.ly = rc.ly; ri.src = c[zi.i].src;
-        ri.mlen = rc.mlen; ri.blen = rc.blen;
-        reg_set_coor(ri, qlen);
-    }
-}
-
-static void set_parent(float mask_level, std::vector<Reg> &r, int sub_diff) {
-    const int n = (int)r.size();
-    if (n <= 0) return;
-    for (int i = 0; i < n; ++i) r[i].id = i;
-    std::vector<uint64_t> &cov = tl_hs.cov;
-    std::vector<int> &w = tl_hs.w;
-    if ((int)cov.size() < n) { cov.resize((size_t)n); w.resize((size_t)n); }
-    w[0] = 0; r[0].parent = 0;
-    int k = 1;
-    for (int i = 1; i < n; ++i) {
-        Reg &ri = r[i];
-        const int si = ri.qs, ei = ri.qe;
-        int n_cov = 0, uncov_len = 0, j;
-        for (j = 0; j < k; ++j) {
-            const Reg &rp = r[w[j]];
-            int sj = rp.qs, ej = rp.qe;
-            if (ej <= si || sj >= ei) continue;
-            if (sj < si) sj = si;
-            if (ej > ei) ej = ei;
-            cov[n_cov++] = (uint64_t)sj << 32 | (uint32_t)ej;
-        }
-        if (n_cov > 0) {
-            int x = si;
-            std::sort(cov.begin(), cov.begin() + n_cov);
-            for (j = 0; j < n_cov; ++j) {
-                if ((int)(cov[j] >> 32) > x) uncov_len += (int)(cov[j] >> 32) - x;
-                x = (int32_t)cov[j] > x ? (int32_t)cov[j] : x;
-            }
-            if (ei > x) uncov_len += ei - x;
-            for (j = 0; j < k; ++j) {
-                Reg &rp = r[w[j]];
-                const int sj = rp.qs, ej = rp.qe;
-                if (ej <= si || sj >= ei) continue;
-                const int min = ej - sj < ei - si ? ej - sj : ei - si, max = ej - sj > ei - si ? ej - sj : ei - si;
-                const int ol = si < sj ? (ei < sj ? 0 : ei < ej ? ei - sj : ej - sj) : (ej < si ? 0 : ej < ei ? ej - si : ei - si);
-                if ((float)ol / min - (float)uncov_len / max > mask_level) {
-                    int cnt_sub = 0;
-                    ri.parent = rp.parent;
-                    rp.subsc = rp.subsc > ri.score ? rp.subsc : ri.score;
-                    if (ri.cnt >= rp.cnt) cnt_sub = 1;
-                    if (rp.has_p && ri.has_p && (rp.rid != ri.rid || rp.rs != ri.rs || rp.re != ri.re || ol != min)) {
-                        rp.dp_max2 = rp.dp_max2 > ri.dp_max ? rp.dp_max2 : ri.dp_max;
-                        if (rp.dp_max - ri.dp_max <= sub_diff) cnt_sub = 1;
-                    }
-                    if (cnt_sub) ++rp.n_sub;
-                    break;
-                }
-            }
-        } else j = k;
-        if (j == k) { w[k++] = i; ri.parent = i; ri.n_sub = 0; }
-    }
-}
-
-static void set_sam_pri(std::vector<Reg> &r) {
-    int n_pri = 0;
-    for (auto &x : r)
-        if (x.id == x.parent) { ++n_pri; x.sam_pri = (n_pri == 1); }
-        else x.sam_pri = 0;
-}
-
-static void sync_regs(std::vector<Reg> &regs) {
-    const int n_regs = (int)regs.size();
-    if (n_regs <= 0) return;
-    int max_id = -1;
-    for (auto &r : regs) max_id = max_id > r.id ? max_id : r.id;
-    std::vector<int> tmp(max_id + 1 > 0 ? max_id + 1 : 1, -1);
-    for (int i = 0; i < n_regs; ++i) if (regs[i].id >= 0) tmp[regs[i].id] = i;
-    for (int i = 0; i < n_regs; ++i) {
-        Reg &r = regs[i];
-        r.id = i;
-        if (r.parent == PARENT_TMP_PRI) r.parent = i;
-        else if (r.parent >= 0 && r.parent <= max_id && tmp[r.parent] >= 0) r.parent = tmp[r.parent];
-        else r.parent = PARENT_UNSET;
-    }
-    set_sam_pri(regs);
-}
-
-static void select_sub(float pri_ratio, int min_diff, int best_n, std::vector<Reg> &r) {
-    if (pri_ratio > 0.0f && !r.empty()) {
-        const int n = (int)r.size();
-        int k = 0, n_2nd = 0;
-        for (int i = 0; i < n; ++i) {
-            const int p = r[i].parent;
-            if (p == i || r[i].inv) { if (k != i) r[k] = r[i]; ++k; }
-            else if ((r[i].score >= r[p].score * pri_ratio || r[i].score + min_diff >= r[p].score) && n_2nd < best_n) {
-                if (!(r[i].qs == r[p].qs && r[i].qe == r[p].qe && r[i].rid == r[p].rid && r[i].rs == r[p].rs && r[i].re == r[p].re)) {
-                    if (k != i) r[k] = r[i];
-                    ++k; ++n_2nd;
-                }
-            }
-        }
-        // NB: r[p] above may already have been overwritten when p > k; minimap2 has the same in-place semantics
-        if (k != n) { r.resize(k); sync_regs(r); }
-    }
-}
-
-static void filter_regs(const mpn_map_opt *opt, int qlen, std::vector<Reg> &regs) {
-    int k = 0;
-    for (int i = 0; i < (int)regs.size(); ++i) {
-        Reg &r = regs[i];
-        int flt = 0;
-        if (!r.inv && r.cnt < opt->min_cnt) flt = 1;
-        if (r.has_p) {
-            if (r.mlen < opt->min_chain_score) flt = 1;
-            else if (r.dp_max < opt->min_dp_max) flt = 1;
-            else if (r.qs > qlen * opt->max_clip_ratio && qlen - r.qe > qlen * opt->max_clip_ratio) flt = 1;
-        }
-        if (!flt) { if (k < i) regs[k] = regs[i]; ++k; }
-    }
-    regs.resize(k);
-}
-
-// mm_squeeze_a: the hits that survived selection get consecutive places in the read's anchor list, in the order of their first
-// anchors.  The anchors themselves are moved on the device (anchor_squeeze_kernel) along the segments written here: every hit
-// is still ONE chain at this point.  Returns the anchors the list holds.
-// (the read's segments are appended to `segs`, the staging list of the calling pool thread; Reg::seg indexes it)
-static int squeeze_a(std::vector<Reg> &regs, int read, int64_t pool_base, std::vector<SqueezeSeg> &segs) {
-    const int n_regs = (int)regs.size();
-    std::vector<std::pair<uint64_t, int>> &aux = tl_hs.aux;
-    aux.resize((size_t)n_regs);
-    for (int i = 0; i < n_regs; ++i) aux[i] = {(uint64_t)regs[i].as, i};
-    if (n_regs > 1) std::sort(aux.begin(), aux.end());
-    int as = 0;
-    for (int i = 0; i < n_regs; ++i) {
-        Reg &r = regs[aux[i].second];
-        r.as = as;
-        r.seg = (int32_t)segs.size();
-        segs.push_back(SqueezeSeg{pool_base + r.src, as, r.cnt, read, 0});
-        as += r.cnt;
-    }
-    return as;
-}
-
-// (called on a squeezed list: squeeze_a above has run)
-static void join_long(const mpn_map_opt *opt, int qlen, std::vector<Reg> &regs, std::vector<SqueezeSeg> &segs) {
-    const int n_regs = (int)regs.size();
-    if (n_regs < 2) return;
-    std::vector<std::pair<uint64_t, int>> &aux = tl_hs.aux;
-    aux.clear();
-    for (int i = 0; i < n_regs; ++i)
-        if (regs[i].parent == i || regs[i].parent < 0) aux.push_back({(uint64_t)regs[i].as, i});
-    std::sort(aux.begin(), aux.end());
-    int n_drop = 0;
-    for (int i = (int)aux.size() - 1; i >= 1; --i) {
-        Reg &r0 = regs[aux[i - 1].second], &r1 = regs[aux[i].second];
-        if (r0.as + r0.cnt != r1.as) continue;
-        if (r0.rid != r1.rid || r0.rev != r1.rev) continue;
-        const u128 a0e_{r0.lx, r0.ly}, a1s_{r1.fx, r1.fy};
-        const u128 *a0e = &a0e_, *a1s = &a1s_;
-        if (a1s->x <= a0e->x || (int32_t)a1s->y <= (int32_t)a0e->y) continue;
-        int max_gap, min_gap;
-        max_gap = min_gap = (int32_t)a1s->y - (int32_t)a0e->y;
-        max_gap = max_gap > (int64_t)(a1s->x - a0e->x) ? max_gap : (int)(a1s->x - a0e->x);
-        min_gap = min_gap < (int64_t)(a1s->x - a0e->x) ? min_gap : (int)(a1s->x - a0e->x);
-        if (max_gap > opt->max_join_long || min_gap > opt->max_join_short) continue;
-        const int sc_thres = (int)((float)opt->min_join_flank_sc / opt->max_join_long * max_gap + .499);
-        if (r0.score < sc_thres || r1.score < sc_thres) continue;
-        const int min_flank_len = (int)(max_gap * opt->min_join_flank_ratio);
-        if (r0.re - r0.rs < min_flank_len || r0.qe - r0.qs < min_flank_len) continue;
-        if (r1.re - r1.rs < min_flank_len || r1.qe - r1.qs < min_flank_len) continue;
-        segs[(size_t)r1.seg].flag = 1;   // (a[r1.as].y |= SEED_LONG_JOIN, applied by the squeeze kernel)
-        r0.cnt += r1.cnt; r0.score += r1.score;
-        {   // mm_cal_fuzzy_len over the joined anchors: both parts' sums and the step across the joint
-            const int span = (int)(a1s->y >> 32 & 0xff);
-            const int tl = (int32_t)a1s->x - (int32_t)a0e->x, ql = (int32_t)a1s->y - (int32_t)a0e->y;
-            r0.blen += r1.blen - span + (tl > ql ? tl : ql);
-            r0.mlen += r1.mlen - span + (tl > span && ql > span ? span : tl < ql ? tl : ql);
-        }
-        r0.lx = r1.lx; r0.ly = r1.ly;
-        reg_set_coor(r0, qlen);
-        r1.cnt = 0;
-        r1.parent = r0.id;
-        ++n_drop;
-    }
-    if (n_drop > 0) {
-        for (auto &r : regs)
-            if (r.parent >= 0 && r.id != r.parent)
-                if (regs[r.parent].parent >= 0 && regs[r.parent].parent != r.parent) r.parent = regs[r.parent].parent;
-        filter_regs(opt, qlen, regs);
-        sync_regs(regs);
-    }
-}
-
-static void hit_sort(std::vector<Reg> &r) {
-    const int n = (int)r.size();
-    if (n <= 1) return;
-    std::vector<std::pair<uint64_t, int>> &aux = tl_hs.aux;
-    aux.clear();
-    for (int i = 0; i < n; ++i)
-        if (r[i].inv || r[i].cnt > 0) aux.push_back({(uint64_t)(uint32_t)(r[i].has_p ? r[i].dp_max : r[i].score) << 32 | r[i].hash, i});
-    std::sort(aux.begin(), aux.end());
-    const int m = (int)aux.size();
-    if (m == n) {
-        // every hit stays: permute in place along the cycles (a read of a split, strain-rich target set brings a hundred hits
-        // to the merge; a second array of them costs an allocation and a construction + destruction per hit)
-        std::vector<int> &from = tl_hs.idx;   // the hit that belongs at place k
-        from.resize((size_t)n);
-        for (int k = 0; k < n; ++k) from[(size_t)k] = aux[(size_t)(n - 1 - k)].second;
-        for (int s0 = 0; s0 < n; ++s0) {
-            if (from[(size_t)s0] == s0 || from[(size_t)s0] < 0) continue;
-            Reg tmp = std::move(r[(size_t)s0]);
-            int k = s0;
-            for (;;) {
-                const int f = from[(size_t)k];
-                from[(size_t)k] = -1;
-                if (f == s0) { r[(size_t)k] = std::move(tmp); break; }
-                r[(size_t)k] = std::move(r[(size_t)f]);
-                k = f;
-            }
-        }
-        return;
-    }
-    std::vector<Reg> t(aux.size());
-    for (int i = m - 1; i >= 0; --i) t[(size_t)(m - 1 - i)] = std::move(r[(size_t)aux[i].second]);
-    r.swap(t);
-}
-
-static void set_mapq(std::vector<Reg> &regs, int min_chain_sc, int match_sc, int rep_len) {
-    static const float q_coef = 40.0f;
-    if (regs.empty()) return;
-    int64_t sum_sc = 0;
-    for (auto &r : regs) if (r.parent == r.id) sum_sc += r.score;
-    const float uniq_ratio = (float)sum_sc / (sum_sc + rep_len);
-    for (auto &r : regs) {
-        if (r.inv) r.mapq = 0;
-        else if (r.parent == r.id) {
-            int mapq;
-            float pen_s1 = (r.score > 100 ? 1.0f : 0.01f * r.score) * uniq_ratio;
-            float pen_cm = r.cnt > 10 ? 1.0f : 0.1f * r.cnt;
-            pen_cm = pen_s1 < pen_cm ? pen_s1 : pen_cm;
-            const int subsc = r.subsc > min_chain_sc ? r.subsc : min_chain_sc;
-            if (r.has_p && r.dp_max2 > 0 && r.dp_max > 0) {
-                const float identity = (float)r.mlen / r.blen;
-                const float x = (float)r.dp_max2 * subsc / r.dp_max / r.score0;
-                mapq = (int)(identity * pen_cm * q_coef * (1.0f - x * x) * logf((float)r.dp_max / match_sc));
-                const int mapq_alt = (int)(6.02f * identity * identity * (r.dp_max - r.dp_max2) / match_sc + .499f);
-                mapq = mapq < mapq_alt ? mapq : mapq_alt;
-            } else {
-                const float x = (float)subsc / r.score0;
-                if (r.has_p) {
-                    const float identity = (float)r.mlen / r.blen;
-                    mapq = (int)(identity * pen_cm * q_coef * (1.0f - x) * logf((float)r.dp_max / match_sc));
-                } else mapq = (int)(pen_cm * q_coef * (1.0f - x) * logf(r.score));
-            }
-            mapq -= (int)(4.343f * logf(r.n_sub + 1) + .499f);
-            mapq = mapq > 0 ? mapq : 0;
-            r.mapq = mapq < 60 ? mapq : 60;
-            if (r.has_p && r.dp_max > r.dp_max2 && r.mapq == 0) r.mapq = 1;
-        } else r.mapq = 0;
-    }
-}
-
-static void split_reg(Reg &r, Reg &r2, int n, int qlen, const SplitRec *sp) {
-    if (n <= 0 || n >= r.cnt || !sp) return;
-    r2 = r;
-    r2.id = -1;
-    r2.sam_pri = 0;
-    r2.has_p = 0; r2.cigar.clear(); r2.cs.clear(); r2.md.clear(); r2.dp_score = r2.dp_max = r2.dp_max2 = r2.n_ambi = 0;
-    r2.split_inv = 0;
-    r2.aligned = 0;
-    r2.cnt = r.cnt - n;
-    r2.score = (int32_t)(r.score * ((float)r2.cnt / r.cnt) + .499);
-    r2.as = r.as + n;
-    if (r.parent == r.id) r2.parent = PARENT_TMP_PRI;
-    r2.fx = sp->fx; r2.fy = sp->fy;   // (its last anchor is the hit's)
-    r2.mlen = sp->mlen_r; r2.blen = sp->blen_r;
-    reg_set_coor(r2, qlen);
-    r.cnt -= r2.cnt;
-    r.score -= r2.score;
-    r.lx = sp->lx_left; r.ly = sp->ly_left;
-    r.mlen = sp->mlen_l; r.blen = sp->blen_l;
-    reg_set_coor(r, qlen);
-    r.split |= 1; r2.split |= 2;
-}
-
-// MPN_DEBUG_CPU: thread CPU time of the sections of a host phase (g_cpu_ns[16 + k])
-struct CpuSect {
-    timespec t;
-    bool on;
-    explicit CpuSect(bool o) : on(o) { if (on) clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t); }
-    void lap(int k);
-};
-
-// What the stitching kernel found for one hit (stitch_kernels.h) applied to the hit: coordinates, DP score, and -- when a
-// gap fill z-dropped -- the split of the hit at the last anchor before the drop (mm_align1's `dropped` branch; the kernel
-// has located the anchor).  returns true if a split remainder was produced in r2
-static bool apply_stitch(int qlen, Reg &r, Reg &r2, const SplitRec *splits, const StitchOut &so, int fin_idx) {
-    bool has_r2 = false;
-    r2.cnt = 0;
-    if (so.has_p) r.has_p = 1;
-    r.dp_score += so.dp_score;
-    if (so.split_n > 0) {
-        const int old_cnt = r.cnt;
-        split_reg(r, r2, so.split_n, qlen, so.split_rec >= 0 ? splits + so.split_rec : nullptr);
-        has_r2 = r2.cnt > 0 && r.cnt != old_cnt;
-        if (so.split_inv) r2.split_inv = 1;
-    }
-    r.rs = so.rs1; r.re = so.re1;
-    if (r.rev) { r.qs = qlen - so.qe1; r.qe = qlen - so.qs1; }
-    else { r.qs = so.qs1; r.qe = so.qe1; }
-    // the CIGAR fix-up and the alignment statistics (mm_update_extra) are done for the whole round by aln_finish_wave_kernel
-    r.fin_idx = r.has_p ? fin_idx : -1;
-    r.aligned = 1;
-    return has_r2;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Host thread pool shared by the pipeline workers.  A worker's host phases (hits from chains, DP-window planning, CIGAR
-// stitching, MAPQ/text) are short bursts between GPU waits; with a private share of the cores a worker would crawl
-// through its burst while the threads of the workers that wait on the GPU sleep.  Every burst is a job in one queue and
-// every idle pool thread helps the oldest open job; the posting thread works on its own job too, so a job always
-// advances.  fn(i, slot): slot < max_par identifies the helping thread (per-thread accumulators of the caller).
-void CpuSect::lap(int k) {
-    if (!on) return;
-    timespec b;
-    clock_gettime(CLOCK_THREAD_CPUTIME_ID, &b);
-    g_cpu_ns[16 + k] += (b.tv_sec - t.tv_sec) * 1000000000LL + (b.tv_nsec - t.tv_nsec);
-    t = b;
-}
-class HostPool {
-    struct Job {
-        const std::function<void(int, int)> *fn;
-        int n, max_par, tag = 0, chunk = 1;   // items are handed out `chunk` at a time: one atomic per item is a hot cache line
-        std::atomic<int> next{0};
-        int slots = 1, active = 0;  // guarded by mu (slot 0 is the posting thread)
-    };
-    std::mutex mu;
-    std::condition_variable cv_work, cv_done;
-    std::deque<Job *> jobs;
-    std::vector<std::thread> threads;
-    bool stop = false;
-
-    static void drain(Job &j, int slot) {
-        for (;;) {
-            const int i0 = j.next.fetch_add(j.chunk);
-            if (i0 >= j.n) break;
-            const int i1 = std::min(j.n, i0 + j.chunk);
-            for (int i = i0; i < i1; ++i) (*j.fn)(i, slot);
-        }
-    }
-    static void run(Job &j, int slot) {
-        if (!g_cpu_on) { drain(j, slot); return; }
-        timespec a, b;
-        clock_gettime(CLOCK_THREAD_CPUTIME_ID, &a);
-        drain(j, slot);
-        clock_gettime(CLOCK_THREAD_CPUTIME_ID, &b);
-        g_cpu_ns[j.tag & 31] += (b.tv_sec - a.tv_sec) * 1000000000LL + (b.tv_nsec - a.tv_nsec);
-    }
-    Job *pick(int *slot) {  // mu held
-        for (Job *j : jobs)
-            if (j->slots < j->max_par && j->next.load(std::memory_order_relaxed) < j->n) { *slot = j->slots++; ++j->active; return j; }
-        return nullptr;
-    }
-    void worker() {
-        pthread_setname_np(pthread_self(), "mpn-pool");
-        std::unique_lock<std::mutex> lk(mu);
-        for (;;) {
-            int slot = 0;
-            Job *j = nullptr;
-            cv_work.wait(lk, [&]() { return stop || (j = pick(&slot)) != nullptr; });
-            if (stop) return;
-            lk.unlock();
-            run(*j, slot);
-            lk.lock();
-            if (--j->active == 0) cv_done.notify_all();
-        }
-    }
-
-public:
-    void ensure(int n_threads) {
-        std::lock_guard<std::mutex> g(mu);
-        while ((int)threads.size() < n_threads - 1) threads.emplace_back([this]() { worker(); });
-    }
-    // grain: items that are worth one helping thread.  The bursts of a sub-batch are a few thousand light items: waking all
-    // pool threads for each of them (a futex round trip and a fight for the queue lock per thread and burst) cost more CPU
-    // than the items themselves.
-    void parallel_for(int n, int max_par, const std::function<void(int, int)> &fn, int tag = 0, int grain = 512) {
-        max_par = std::min(max_par, 1 + n / std::max(1, grain));
-        if (max_par <= 1 || n < 2) { for (int i = 0; i < n; ++i) fn(i, 0); return; }
-        Job j;
-        j.fn = &fn; j.n = n; j.max_par = max_par; j.tag = tag;
-        j.chunk = std::max(1, std::min(32, n / (max_par * 8)));
-        { std::lock_guard<std::mutex> g(mu); jobs.push_back(&j); }
-        for (int k = 1; k < max_par; ++k) cv_work.notify_one();
-        run(j, 0);
-        std::unique_lock<std::mutex> lk(mu);
-        for (auto it = jobs.begin(); it != jobs.end(); ++it) if (*it == &j) { jobs.erase(it); break; }
-        cv_done.wait(lk, [&]() { return j.active == 0; });
-    }
-    ~HostPool() {
-        { std::lock_guard<std::mutex> g(mu); stop = true; }
-        cv_work.notify_all();
-        for (auto &t : threads) t.join();
-    }
-};
-static HostPool g_pool;
-
-static void parallel_for(int n, int n_threads, const std::function<void(int, int)> &fn, int tag = 0, int grain = 512) { g_pool.parallel_for(n, n_threads, fn, tag, grain); }
-
-struct ReadState {
-    std::vector<Reg> regs;
-    int n_a = 0;           // anchors of the read's squeezed list (which lives in HBM)
-    std::vector<int> pending; // reg indices aligned this round
-};
-
-static double event_identity(const Reg &r) {
-    int32_t n_gapo = 0, n_gap = 0;
-    for (uint32_t c : r.cigar) { const int32_t op = c & 0xf, len = c >> 4; if (op == 1 || op == 2) { ++n_gapo; n_gap += len; } }
-    return (double)r.mlen / (r.blen + r.n_ambi - n_gap + n_gapo);
-}
-
-// names and lengths of the targets the hits refer to: one index, or all parts of a split index in order
-struct Targets {
-    const std::vector<std::string> *names;
-    const std::vector<int32_t> *lens;
-};
-
-// cs:Z and MD:Z of a hit that has a CIGAR, in this order (both when both were asked for: DESIGN.md section 6)
-static void write_diff_tags(const mpn_map_opt *o, const Reg &r, std::string &out) {
-    if (r.cigar.empty()) return;
-    if (o->out_tags & (MPN_TAG_CS | MPN_TAG_CS_LONG)) { out += "\tcs:Z:"; out += r.cs; }
-    if (o->out_tags & MPN_TAG_MD) { out += "\tMD:Z:"; out += r.md; }
-}
-
-static void write_paf(const Targets mi_, const mpn_map_opt *o, const char *name, int32_t qlen, const std::vector<Reg> &regs,
-                      int32_t rep_len, std::string &out) {
-    const Targets *mi = &mi_;
-    char buf[1024];
-    for (const Reg &r : regs) {
-        const int type = r.id == r.parent ? (r.inv ? 'I' : 'P') : (r.inv ? 'i' : 'S');
-        out += name;
-        snprintf(buf, sizeof(buf), "\t%d\t%d\t%d\t%c\t", qlen, r.qs, r.qe, "+-"[r.rev]);
-        out += buf;
-        out += (*mi->names)[r.rid];
-        snprintf(buf, sizeof(buf), "\t%d\t%d\t%d\t%d\t%d\t%d", (*mi->lens)[r.rid], r.rs, r.re, r.mlen, r.blen, r.mapq);
-        out += buf;
-        if (r.has_p) {
-            snprintf(buf, sizeof(buf), "\tNM:i:%d\tms:i:%d\tAS:i:%d\tnn:i:%d", r.blen - r.mlen + r.n_ambi, r.dp_max, r.dp_score, r.n_ambi);
-            out += buf;
-        }
-        snprintf(buf, sizeof(buf), "\ttp:A:%c\tcm:i:%d\ts1:i:%d", type, r.cnt, r.score);
-        out += buf;
-        if (r.parent == r.id) { snprintf(buf, sizeof(buf), "\ts2:i:%d", r.subsc); out += buf; }
-        if (r.has_p) {
-            const double div = 1.0 - event_identity(r);
-            if (div == 0.0) out += "\tde:f:0";
-            else { snprintf(buf, sizeof(buf), "\tde:f:%.4f", div); out += buf; }
-        }
-        if (r.split) { snprintf(buf, sizeof(buf), "\tzd:i:%d", r.split); out += buf; }
-        snprintf(buf, sizeof(buf), "\trl:i:%d", rep_len);
-        out += buf;
-        if (r.has_p && o->with_cigar) {
-            out += "\tcg:Z:";
-            for (uint32_t c : r.cigar) { snprintf(buf, sizeof(buf), "%d%c", c >> 4, "MIDNSHP=X"[c & 0xf]); out += buf; }
-            write_diff_tags(o, r, out);
-        }
-        out += '\n';
-    }
-}
-
-// SAM records of one read (minimap2 2.17 -a: mm_write_sam3 / write_sam_cigar / sam_write_sq for single-segment reads
-// without read group; qualities are not carried).  A read without hits gets a flag-4 record.
-static char sam_comp(char c) {
-    static const char from[] = "ACGTUNRYKMSWBDHVacgtunrykmswbdhv", to[] = "TGCAANYRMKSWVHDBtgcaanyrmkswvhdb";
-    const char *p = c ? strchr(from, c) : nullptr;
-    return p ? to[p - from] : c;
-}
-
-static void sam_seq(std::string &out, const char *seq, int st, int en, bool rev) {
-    if (!rev) out.append(seq + st, (size_t)(en - st));
-    else for (int i = en - 1; i >= st; --i) out += sam_comp(seq[i]);
-}
-
-// QUAL column of a record whose SEQ is seq[st, en) on strand rev: the qualities in the same orientation, or '*' without them
-static void sam_qual(std::string &out, const char *qual, int st, int en, bool rev) {
-    out += '\t';
-    if (!qual) { out += '*'; return; }
-    if (!rev) out.append(qual + st, (size_t)(en - st));
-    else for (int i = en - 1; i >= st; --i) out += qual[i];
-}
-
-static void write_sam(const Targets mi_, const mpn_map_opt *o, const char *name, int32_t qlen, const char *seq, const char *qual, const std::vector<Reg> &regs,
-                      int32_t rep_len, std::string &out) {
-    const Targets *mi = &mi_;
-    char buf[1024];
-    if (regs.empty()) {
-        out += name;
-        out += "\t4\t*\t0\t0\t*\t*\t0\t0\t";
-        sam_seq(out, seq, 0, qlen, false);
-        sam_qual(out, qual, 0, qlen, false);
-        snprintf(buf, sizeof(buf), "\trl:i:%d\n", rep_len);
-        out += buf;
-        return;
-    }
-    for (size_t i = 0; i < regs.size(); ++i) {
-        const Reg &r = regs[i];
-        const int type = r.id == r.parent ? (r.inv ? 'I' : 'P') : (r.inv ? 'i' : 'S');
-        int flag = r.rev ? 0x10 : 0;
-        if (r.parent != r.id) flag |= 0x100;
-        else if (!r.sam_pri) flag |= 0x800;
-        out += name;
-        snprintf(buf, sizeof(buf), "\t%d\t", flag);
-        out += buf;
-        out += (*mi->names)[r.rid];
-        snprintf(buf, sizeof(buf), "\t%d\t%d\t", r.rs + 1, r.mapq);
-        out += buf;
-        if (!r.has_p) out += '*';
-        else {
-            const int clip0 = r.rev ? qlen - r.qe : r.qs, clip1 = r.rev ? r.qs : qlen - r.qe;
-            const char clip_char = (flag & 0x800) ? 'H' : 'S';
-            if (clip0) { snprintf(buf, sizeof(buf), "%d%c", clip0, clip_char); out += buf; }
-            for (uint32_t c : r.cigar) { snprintf(buf, sizeof(buf), "%d%c", c >> 4, "MIDNSHP=X"[c & 0xf]); out += buf; }
-            if (clip1) { snprintf(buf, sizeof(buf), "%d%c", clip1, clip_char); out += buf; }
-        }
-        out += "\t*\t0\t0\t";
-        if ((flag & 0x900) == 0) { sam_seq(out, seq, 0, qlen, r.rev); sam_qual(out, qual, 0, qlen, r.rev); }
-        else if (flag & 0x100) out += "*\t*";
-        else { sam_seq(out, seq, r.qs, r.qe, r.rev); sam_qual(out, qual, r.qs, r.qe, r.rev); }
-        if (r.has_p) {
-            snprintf(buf, sizeof(buf), "\tNM:i:%d\tms:i:%d\tAS:i:%d\tnn:i:%d", r.blen - r.mlen + r.n_ambi, r.dp_max, r.dp_score, r.n_ambi);
-            out += buf;
-        }
-        snprintf(buf, sizeof(buf), "\ttp:A:%c\tcm:i:%d\ts1:i:%d", type, r.cnt, r.score);
-        out += buf;
-        if (r.parent == r.id) { snprintf(buf, sizeof(buf), "\ts2:i:%d", r.subsc); out += buf; }
-        if (r.has_p) {
-            const double div = 1.0 - event_identity(r);
-            if (div == 0.0) out += "\tde:f:0";
-            else { snprintf(buf, sizeof(buf), "\tde:f:%.4f", div); out += buf; }
-        }
-        if (r.split) { snprintf(buf, sizeof(buf), "\tzd:i:%d", r.split); out += buf; }
-        if (r.parent == r.id && r.has_p && regs.size() > 1) {  // SA: the other non-secondary hits that have a CIGAR
-            bool any = false;
-            for (size_t j = 0; j < regs.size(); ++j) {
-                const Reg &q = regs[j];
-                if (j == i || q.parent != q.id || !q.has_p) continue;
-                if (!any) { out += "\tSA:Z:"; any = true; }
-                int l_M, l_I = 0, l_D = 0;
-                if (q.qe - q.qs < q.re - q.rs) { l_M = q.qe - q.qs; l_D = (q.re - q.rs) - l_M; }
-                else { l_M = q.re - q.rs; l_I = (q.qe - q.qs) - l_M; }
-                const int c5 = q.rev ? qlen - q.qe : q.qs, c3 = q.rev ? q.qs : qlen - q.qe;
-                out += (*mi->names)[q.rid];
-                snprintf(buf, sizeof(buf), ",%d,%c,", q.rs + 1, "+-"[q.rev]);
-                out += buf;
-                if (c5) { snprintf(buf, sizeof(buf), "%dS", c5); out += buf; }
-                if (l_M) { snprintf(buf, sizeof(buf), "%dM", l_M); out += buf; }
-                if (l_I) { snprintf(buf, sizeof(buf), "%dI", l_I); out += buf; }
-                if (l_D) { snprintf(buf, sizeof(buf), "%dD", l_D); out += buf; }
-                if (c3) { snprintf(buf, sizeof(buf), "%dS", c3); out += buf; }
-                snprintf(buf, sizeof(buf), ",%d,%d;", q.mapq, q.blen - q.mlen + q.n_ambi);
-                out += buf;
-            }
-        }
-        if (r.has_p && o->with_cigar) write_diff_tags(o, r, out);
-        snprintf(buf, sizeof(buf), "\trl:i:%d\n", rep_len);
-        out += buf;
-    }
-}
 
 // per-worker resources: a device arena, grow-only scratch pools and pinned staging buffers, and the events that join the
 // extension stage's side streams (the streams themselves are leased per GPU segment: StreamLease)
@@ -740,12 +86,6 @@ static Slot g_slots[16];
 static thread_local Slot *tl_slot = &g_slots[0];
 
 static int g_force_kernel = 0;  // test hook: 0 auto, 1 workgroup kernel with one wave, 3 with 256+ threads, 4 strip (else band), 5 band, 6 tiled
-
-static void parallel_chunks(int64_t n, int n_threads, const std::function<void(int64_t, int64_t, int)> &fn, int tag = 0) {
-    if (n_threads <= 1 || n < 8192) { fn(0, n, 0); return; }
-    // chunk t of n_threads equal ranges; the chunk index is what the callers use for their per-thread accumulators
-    g_pool.parallel_for(n_threads, n_threads, [&](int t, int) { fn(n * t / n_threads, n * (t + 1) / n_threads, t); }, tag, 1);
-}
 
 // the second pass of a gap fill whose CIGAR failed the z-drop test: exact maximum, band (or anti-diagonal) layout
 __global__ void ext_redo_patch_kernel(ExtJob *jobs, const int32_t *ids, const int32_t *layout, const int32_t *qstride,
@@ -1951,50 +1291,6 @@ static int map_range(const mpn_index *idx, const mpn_map_opt *opt, const char *c
     return 0;
 }
 
-// Hits of a batch accumulated over the parts of a split index (minimap2 -I / --split-prefix): per read the hits of every
-// part with target ids shifted to the concatenated target table, and the largest repetitive-seed span.
-struct mpn_hits {
-    int32_t n_reads = 0, n_parts = 0, k = 15;
-    int32_t want_text = 1;   // 0: mpn_hits_finish will be asked for columns only: the CIGARs need not leave the GPU (mpn_hits_set_text)
-    std::vector<std::vector<Reg>> regs;
-    std::vector<int32_t> rep_len;
-    std::vector<std::string> names;
-    std::vector<int32_t> lens;
-    int32_t tags = 0;        // MPN_TAG_* outputs the accumulated hits carry (made while each part was resident)
-};
-
-// Threads of the host pool: what the caller asks for, else the cores this process may actually use -- the container's CPU
-// quota (cgroup v2 cpu.max / v1 cfs quota) counts, not just the visible cores: with 256 visible cores and a quota of 16
-// a pool sized by the visible cores is throttled -- capped at 32.
-static int default_host_threads(const mpn_map_opt *opt) {
-    if (const char *e = getenv("MPN_HOST_THREADS")) return std::max(1, atoi(e));
-    if (opt->host_threads > 0) return opt->host_threads;
-    static const int detected = []() {
-        long long cores = std::max(1, (int)std::thread::hardware_concurrency());
-        long long quota = -1, period = 100000;
-        if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-            char q[64] = {0};
-            if (fscanf(f, "%63s %lld", q, &period) >= 1 && strcmp(q, "max") != 0) quota = atoll(q);
-            fclose(f);
-        } else if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {
-            if (fscanf(g, "%lld", &quota) != 1) quota = -1;
-            fclose(g);
-            if (FILE *h = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(h, "%lld", &period) != 1) period = 100000; fclose(h); }
-        }
-        if (quota > 0 && period > 0) cores = std::min(cores, std::max(1LL, (quota + period - 1) / period));
-        // one process per GPU: the ranks of a node share its cores (bench.py / the launcher export the rank count)
-        int ranks = 1;
-        if (const char *e = getenv("MPN_RANKS_ON_NODE")) ranks = std::max(1, atoi(e));
-        else if (const char *e2 = getenv("LOCAL_WORLD_SIZE")) ranks = std::max(1, atoi(e2));
-        // twice this rank's share of the cores, at most 32: the pool's threads mostly serve short bursts between GPU waits, and a
-        // burst waiting for a free pool thread costs more than the quota's throttling (measured on a 16-CPU quota, one rank:
-        // 16 threads 84.7, 24: 86.4, 32: 88.2, 48: 84.1 Gbp/min); never fewer than 4 (a rank's host phases need ~4 cores)
-        const int n = (int)std::max(4LL, std::min(32LL, 2 * cores / ranks));
-        return n;
-    }();
-    return detected;
-}
-
 // The mapping itself: every read's final hits against every one of n_parts RESIDENT indexes -> rs[part], rep_len[part] (no text).
 // One index is the plain case.  Several are the parts of a target set that exceeds one index (minimap2 -I): the work items of
 // the pipeline are (sub-batch, part) pairs, so the reads go up once, and the pipeline neither drains nor refills between parts.
@@ -2027,7 +1323,7 @@ static int map_batch_core(const mpn_index *const *parts, int n_parts, const mpn_
     wt.stop_into(g_stats[16]);
     int n_threads = default_host_threads(opt);
     *n_threads_out = n_threads;
-    g_pool.ensure(n_threads);
+    pool_ensure(n_threads);
     // sub-batches of ~32 Mbp run through a small pool of workers (12 by default), each with its own device arena and a
     // submission stream leased per GPU segment (StreamLease), so that the host phases of one sub-batch overlap the GPU phases of the others and the
     // latency-bound kernels (chain DP, long extensions) of one overlap the throughput-bound ones of another
@@ -2346,28 +1642,6 @@ extern "C" int64_t mpn_map_batch_ex(const mpn_index *idx, const mpn_map_opt *opt
 }
 
 // ---- split index (minimap2 -I parts + --split-prefix merge) ---------------------------------------------------------
-extern "C" mpn_hits *mpn_hits_create(int32_t n_reads) {
-    if (n_reads < 0) { set_error("mpn_hits_create: negative read count"); return nullptr; }
-    mpn_hits *h = new mpn_hits();
-    h->n_reads = n_reads;
-    h->regs.resize((size_t)n_reads);
-    h->rep_len.assign((size_t)n_reads, 0);
-    return h;
-}
-extern "C" void mpn_hits_destroy(mpn_hits *h) { delete h; }
-extern "C" void mpn_hits_set_text(mpn_hits *h, int32_t want_text) { if (h) h->want_text = want_text ? 1 : 0; }
-extern "C" int32_t mpn_hits_n_seq(const mpn_hits *h) { return (int32_t)h->lens.size(); }
-extern "C" int32_t mpn_hits_n_parts(const mpn_hits *h) { return h->n_parts; }
-extern "C" int32_t mpn_hits_seq_len(const mpn_hits *h, int32_t i) { return i >= 0 && (size_t)i < h->lens.size() ? h->lens[(size_t)i] : -1; }
-extern "C" int32_t mpn_hits_seq_name(const mpn_hits *h, int32_t i, char *buf, int32_t cap) {
-    if (i < 0 || (size_t)i >= h->names.size() || !buf || cap <= 0) return -1;
-    const std::string &nm = h->names[(size_t)i];
-    const int32_t l = (int32_t)std::min<size_t>(nm.size(), (size_t)cap - 1);
-    memcpy(buf, nm.data(), (size_t)l);
-    buf[l] = 0;
-    return (int32_t)nm.size();
-}
-
 // several RESIDENT parts in one call (288 GB of HBM hold what a CPU host streams through -I): the pipeline's work items are
 // (sub-batch, part) pairs; the hits land in the accumulator part by part, in the order given, as repeated
 // mpn_map_batch_part calls would leave them
@@ -2420,18 +1694,6 @@ extern "C" int mpn_map_batch_part(const mpn_index *part, const mpn_map_opt *opt,
     return mpn_map_batch_parts(&part, 1, opt, n, names, seqs, seq_off, seq_len, r_seqs, r_off, r_len, acc);
 }
 
-// minimap2's merge of the per-part hits of a read (mm_split_merge): the sub-optimal bookkeeping is reset, the hits are
-// ranked, grouped and trimmed again over all parts, and MAPQ is recomputed
-static void merge_regs(const mpn_map_opt *opt, int k, std::vector<Reg> &regs, int32_t rep_len) {
-    if (regs.empty()) return;
-    for (Reg &r : regs) { r.subsc = 0; r.n_sub = 0; if (r.has_p) r.dp_max2 = 0; }
-    hit_sort(regs);
-    set_parent(opt->mask_level, regs, opt->a * 2 + opt->b);
-    select_sub(opt->pri_ratio, k * 2, opt->best_n, regs);
-    set_sam_pri(regs);
-    set_mapq(regs, opt->min_chain_score, opt->a, rep_len);
-}
-
 extern "C" int64_t mpn_hits_finish(mpn_hits *acc, const mpn_map_opt *opt, int32_t n, const char *const *names, const char *seqs,
                                    const char *quals, const int64_t *seq_off, const int32_t *seq_len, char *paf, int64_t paf_cap,
                                    mpn_aln_cols *cols) {
@@ -2440,7 +1702,7 @@ extern "C" int64_t mpn_hits_finish(mpn_hits *acc, const mpn_map_opt *opt, int32_
     if (cols) cols->n_rows = 0;
     if (n <= 0) { if (paf && paf_cap > 0) paf[0] = 0; g_kept = Kept(); if (opt->out_sam == 2) g_kept.has_sam = true; return 0; }
     const int n_threads = default_host_threads(opt);
-    g_pool.ensure(n_threads);
+    pool_ensure(n_threads);
     if (!acc->n_parts) { set_error("mpn_hits_finish: no part was mapped"); return -1; }
     if (!acc->want_text && (paf || opt->out_sam != 0)) { set_error("mpn_hits_finish: text asked of an accumulator that was told there would be none (mpn_hits_set_text)"); return -1; }
     if ((paf || opt->out_sam != 0) && opt->with_cigar) {   // the strings were made while the parts were resident: they cannot be made now
@@ -2456,155 +1718,6 @@ extern "C" int64_t mpn_hits_finish(mpn_hits *acc, const mpn_map_opt *opt, int32_
     std::vector<std::vector<Reg>*> regs((size_t)n);
     for (int i = 0; i < n; ++i) regs[(size_t)i] = &acc->regs[(size_t)i];
     return emit_batch(Targets{&acc->names, &acc->lens}, opt, n, names, seqs, quals, seq_off, seq_len, regs, acc->rep_len, n_threads, paf, paf_cap, cols);
-}
-
-// ---- hits of a range of reads as a byte block (index parts sharded over ranks: DESIGN section 7) ----------------------------
-// Little-endian block: HitsBlockHead, then per read rep_len, n_hits (int32) and per hit the HIT_FIELDS int32 fields below, followed,
-// when want_text, by n_cigar and the CIGAR words.  Only what merge_regs and emit_batch read travels: the hit's coordinates, scores
-// and flags; everything merge_regs recomputes (id, parent, subsc, n_sub, dp_max2, mapq, sam_pri) and the transient bookkeeping of
-// the mapping pass (fin_*, fx/fy/lx/ly, src, seg, as, aligned) stay behind.
-struct HitsBlockHead {
-    char magic[4];
-    uint32_t version;
-    int32_t k, want_text, n_reads, n_seq, n_parts, pad;
-    int64_t payload;      // bytes after the header
-    uint64_t check;       // hits_check() of the payload
-};
-static const char HITS_MAGIC[4] = {'M', 'P', 'H', 'B'};
-static const uint32_t HITS_VERSION = 1;
-static const int HIT_FIELDS = 18;
-
-static uint64_t hits_check(const uint8_t *p, int64_t n) {
-    uint64_t h = 0x9e3779b97f4a7c15ULL ^ (uint64_t)n;
-    int64_t i = 0;
-    for (; i + 8 <= n; i += 8) { uint64_t w; memcpy(&w, p + i, 8); h = (h ^ w) * 0x100000001b3ULL; h ^= h >> 29; }
-    for (; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ULL;
-    return h;
-}
-
-static inline void hit_fields(const Reg &r, int32_t *f) {
-    const int32_t v[HIT_FIELDS] = {r.cnt, r.rid, r.score, r.score0, r.qs, r.qe, r.rs, r.re, r.mlen, r.blen, (int32_t)r.rev, (int32_t)r.inv,
-                                   (int32_t)r.split, (int32_t)r.hash, r.has_p, r.dp_score, r.dp_max, r.n_ambi};
-    memcpy(f, v, sizeof(v));
-}
-
-static inline void hit_from_fields(const int32_t *f, Reg &r) {
-    r = Reg();
-    r.cnt = f[0]; r.rid = f[1]; r.score = f[2]; r.score0 = f[3]; r.qs = f[4]; r.qe = f[5]; r.rs = f[6]; r.re = f[7]; r.mlen = f[8]; r.blen = f[9];
-    r.rev = (uint32_t)f[10]; r.inv = (uint32_t)f[11]; r.split = (uint32_t)f[12]; r.hash = (uint32_t)f[13]; r.has_p = f[14]; r.dp_score = f[15];
-    r.dp_max = f[16]; r.n_ambi = f[17];
-    r.aligned = 1;
-}
-
-extern "C" int64_t mpn_hits_export(const mpn_hits *h, int32_t lo, int32_t hi, void *buf, int64_t cap) {
-    if (!h || lo < 0 || hi < lo || hi > h->n_reads) { set_error("mpn_hits_export: no accumulator or reads [%d, %d) outside its batch", lo, hi); return -1; }
-    if (h->tags) { set_error("mpn_hits_export: the hits carry cs/MD strings or =/X CIGARs (out_tags 0x%x), which the block format does not hold", h->tags); return -1; }
-    int64_t payload = 0;
-    for (int32_t i = lo; i < hi; ++i) {
-        payload += 8;
-        for (const Reg &r : h->regs[(size_t)i]) payload += 4 * HIT_FIELDS + (h->want_text ? 4 + 4 * (int64_t)r.cigar.size() : 0);
-    }
-    const int64_t need = (int64_t)sizeof(HitsBlockHead) + payload;
-    if (!buf) return need;
-    if (cap < need) return -3;
-    uint8_t *const base = (uint8_t *)buf, *p = base + sizeof(HitsBlockHead);
-    auto put = [&](const void *src, size_t bytes) { memcpy(p, src, bytes); p += bytes; };
-    int32_t f[HIT_FIELDS];
-    for (int32_t i = lo; i < hi; ++i) {
-        const std::vector<Reg> &regs = h->regs[(size_t)i];
-        const int32_t rh[2] = {h->rep_len[(size_t)i], (int32_t)regs.size()};
-        put(rh, 8);
-        for (const Reg &r : regs) {
-            hit_fields(r, f);
-            put(f, sizeof(f));
-            if (h->want_text) {
-                const int32_t nc = (int32_t)r.cigar.size();
-                put(&nc, 4);
-                if (nc) put(r.cigar.data(), (size_t)nc * 4);
-            }
-        }
-    }
-    HitsBlockHead hd;
-    memset(&hd, 0, sizeof(hd));
-    memcpy(hd.magic, HITS_MAGIC, 4);
-    hd.version = HITS_VERSION;
-    hd.k = h->k; hd.want_text = h->want_text; hd.n_reads = hi - lo; hd.n_seq = (int32_t)h->lens.size(); hd.n_parts = h->n_parts;
-    hd.payload = payload;
-    hd.check = hits_check(base + sizeof(HitsBlockHead), payload);
-    memcpy(base, &hd, sizeof(hd));
-    return need;
-}
-
-// Every check runs before the accumulator is touched: a refused block leaves it as it was.
-extern "C" int mpn_hits_import(mpn_hits *h, const void *buf, int64_t len, int32_t n_parts, int32_t n_seq, const char *const *names,
-                               const int32_t *lens) {
-    if (!h || (!buf && len > 0) || len < 0) { set_error("mpn_hits_import: null accumulator or buffer"); return -1; }
-    if (n_parts < 0 || n_seq < 0 || (n_seq > 0 && (!names || !lens))) { set_error("mpn_hits_import: bad target list (n_parts %d, n_seq %d)", n_parts, n_seq); return -1; }
-    HitsBlockHead hd;
-    if (len < (int64_t)sizeof(hd)) { set_error("mpn_hits_import: block of %lld bytes is shorter than its header", (long long)len); return -1; }
-    memcpy(&hd, buf, sizeof(hd));
-    if (memcmp(hd.magic, HITS_MAGIC, 4) != 0 || hd.version != HITS_VERSION) { set_error("mpn_hits_import: not a hits block (bad magic or version)"); return -1; }
-    if (hd.payload != len - (int64_t)sizeof(hd)) { set_error("mpn_hits_import: block says %lld payload bytes, %lld given", (long long)hd.payload, (long long)(len - (int64_t)sizeof(hd))); return -1; }
-    const uint8_t *const p0 = (const uint8_t *)buf + sizeof(hd);
-    if (hits_check(p0, hd.payload) != hd.check) { set_error("mpn_hits_import: corrupted block (checksum)"); return -1; }
-    if (hd.want_text != h->want_text) { set_error("mpn_hits_import: block %s CIGARs, the accumulator %s them", hd.want_text ? "carries" : "lacks", h->want_text ? "wants" : "does not want"); return -1; }
-    if (h->n_parts > 0 && hd.k != h->k) { set_error("mpn_hits_import: block of k = %d into an accumulator of k = %d", hd.k, h->k); return -1; }
-    if (hd.n_reads != h->n_reads) { set_error("mpn_hits_import: block of %d reads into an accumulator of %d", hd.n_reads, h->n_reads); return -1; }
-    if (hd.n_seq != n_seq || hd.n_parts != n_parts) { set_error("mpn_hits_import: block of %d targets in %d parts, %d in %d given", hd.n_seq, hd.n_parts, n_seq, n_parts); return -1; }
-    for (int32_t i = 0; i < n_seq; ++i)
-        if (!names[i] || lens[i] < 0) { set_error("mpn_hits_import: target %d has no name or a negative length", i); return -1; }
-    // pass 1: walk the payload with every length checked against what is left, and the fields the text writers index with
-    const uint8_t *p = p0, *const end = p0 + hd.payload;
-    int32_t f[HIT_FIELDS];
-    auto take = [&](void *dst, int64_t bytes) { if (bytes < 0 || end - p < bytes) return false; memcpy(dst, p, (size_t)bytes); p += bytes; return true; };
-    for (int32_t i = 0; i < hd.n_reads; ++i) {
-        int32_t rh[2];
-        if (!take(rh, 8) || rh[1] < 0) { set_error("mpn_hits_import: truncated block (read %d)", i); return -1; }
-        for (int32_t j = 0; j < rh[1]; ++j) {
-            if (!take(f, sizeof(f))) { set_error("mpn_hits_import: truncated block (read %d, hit %d)", i, j); return -1; }
-            if (f[1] < 0 || f[1] >= n_seq || (uint32_t)f[10] > 1 || f[4] < 0 || f[5] < f[4] || f[6] < 0 || f[7] < f[6]) {
-                set_error("mpn_hits_import: corrupted hit (read %d, hit %d)", i, j); return -1;
-            }
-            if (hd.want_text) {
-                int32_t nc;
-                if (!take(&nc, 4) || nc < 0 || end - p < 4 * (int64_t)nc) { set_error("mpn_hits_import: truncated CIGAR (read %d, hit %d)", i, j); return -1; }
-                for (int32_t c = 0; c < nc; ++c) {
-                    uint32_t op;
-                    memcpy(&op, p + 4 * (size_t)c, 4);
-                    if ((op & 0xf) > 5) { set_error("mpn_hits_import: corrupted CIGAR (read %d, hit %d)", i, j); return -1; }
-                }
-                p += 4 * (size_t)nc;
-            }
-        }
-    }
-    if (p != end) { set_error("mpn_hits_import: %lld bytes past the last read", (long long)(end - p)); return -1; }
-    // pass 2: append, as mpn_map_batch_parts appends the hits of the exporter's parts
-    const int32_t rid0 = (int32_t)h->lens.size();
-    p = p0;
-    for (int32_t i = 0; i < hd.n_reads; ++i) {
-        int32_t rh[2];
-        take(rh, 8);
-        std::vector<Reg> &regs = h->regs[(size_t)i];
-        regs.reserve(regs.size() + (size_t)rh[1]);
-        for (int32_t j = 0; j < rh[1]; ++j) {
-            take(f, sizeof(f));
-            regs.emplace_back();
-            Reg &r = regs.back();
-            hit_from_fields(f, r);
-            r.rid += rid0;
-            if (hd.want_text) {
-                int32_t nc;
-                take(&nc, 4);
-                r.cigar.resize((size_t)nc);
-                if (nc) take(r.cigar.data(), 4 * (int64_t)nc);
-            }
-        }
-        h->rep_len[(size_t)i] = std::max(h->rep_len[(size_t)i], rh[0]);
-    }
-    for (int32_t i = 0; i < n_seq; ++i) { h->names.emplace_back(names[i]); h->lens.push_back(lens[i]); }
-    h->k = hd.k;
-    h->n_parts += n_parts;
-    return 0;
 }
 
 extern "C" int64_t mpn_map_fetch_cols(mpn_aln_cols *cols) {
@@ -2635,30 +1748,11 @@ static int64_t fetch_kept(std::string &txt, bool &has, const char *what, char *b
 extern "C" int64_t mpn_map_fetch_text(char *buf, int64_t cap) { return fetch_kept(g_kept.text, g_kept.has_text, "mpn_map_fetch_text", buf, cap); }
 extern "C" int64_t mpn_map_fetch_sam(char *buf, int64_t cap) { return fetch_kept(g_kept.sam, g_kept.has_sam, "mpn_map_fetch_sam", buf, cap); }
 
-static int64_t sam_header_of(const std::vector<std::string> &names, const std::vector<int32_t> &lens, const char *cmdline, char *buf, int64_t cap);
-
 extern "C" int64_t mpn_sam_header(const mpn_index *idx, const char *cmdline, char *buf, int64_t cap) {
     return sam_header_of(idx->names, idx->lens, cmdline, buf, cap);
 }
 extern "C" int64_t mpn_hits_sam_header(const mpn_hits *h, const char *cmdline, char *buf, int64_t cap) {
     return sam_header_of(h->names, h->lens, cmdline, buf, cap);
-}
-
-static int64_t sam_header_of(const std::vector<std::string> &names, const std::vector<int32_t> &lens, const char *cmdline, char *buf, int64_t cap) {
-    std::string h;
-    char line[64];
-    for (size_t i = 0; i < names.size(); ++i) {
-        h += "@SQ\tSN:"; h += names[i];
-        snprintf(line, sizeof(line), "\tLN:%d\n", lens[i]);
-        h += line;
-    }
-    h += "@PG\tID:mpn-aligner\tPN:mpn-aligner\tVN:r02";
-    if (cmdline && cmdline[0]) { h += "\tCL:"; h += cmdline; }
-    h += '\n';
-    if ((int64_t)h.size() + 1 > cap) return -3;
-    memcpy(buf, h.data(), h.size());
-    buf[h.size()] = 0;
-    return (int64_t)h.size();
 }
 
 extern "C" int64_t mpn_map_batch(const mpn_index *idx, const mpn_map_opt *opt, int32_t n, const char *const *names, const char *seqs,

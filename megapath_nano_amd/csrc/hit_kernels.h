@@ -6,7 +6,7 @@
 // The read's chains live in LDS as a struct of arrays.  The two sorts are rank sorts over the 64 lanes (a read has tens of
 // chains); the grouping / selection / joining passes are the sequential algorithms of hit.c on lane 0 (their state is a few
 // LDS words per step: ~100 us for a read with a hundred chains, thousands of reads in flight).  Reads with more than
-// HIT_MAX_CHAINS chains are listed for the host, which runs the same functions (csrc/align.hip) on the downloaded records.
+// HIT_MAX_CHAINS chains are listed for the host, which runs the same functions (csrc/hit_host.cpp) on the downloaded records.
 #pragma once
 #include "map_types.h"
 #include "mpn_common.h"
@@ -28,22 +28,6 @@ struct HitRec { uint64_t fx, fy, lx, ly; int32_t score, score0, cnt, as, parent,
 // per read: where its hits are, how many, the anchors of its squeezed list; flags bit 0: ids were re-synchronised (mm_sync_regs
 // ran, so mm_set_sam_pri has); n_regs = -1: too many chains, left to the host
 struct HitRead { int64_t reg_pos; int32_t n_regs, n_a, flags, pad; };
-
-__device__ __forceinline__ uint64_t hs_hash64(uint64_t key) {
-    key = ~key + (key << 21);
-    key = key ^ key >> 24;
-    key = (key + (key << 3)) + (key << 8);
-    key = key ^ key >> 14;
-    key = (key + (key << 2)) + (key << 4);
-    key = key ^ key >> 28;
-    key = key + (key << 31);
-    return key;
-}
-__device__ __forceinline__ uint32_t hs_wang32(uint32_t key) {
-    key += ~(key << 15); key ^= (key >> 10); key += (key << 3);
-    key ^= (key >> 6); key += ~(key << 11); key ^= (key >> 16);
-    return key;
-}
 
 // N: chains a read may have in this instantiation; it takes the reads with lo_excl < chains <= min(N, prm.max_chains), and the
 // instantiation with lo_excl == 0 also writes the records of the reads without chains; the one with N == HIT_MAX_CHAINS those
@@ -78,8 +62,8 @@ __global__ __launch_bounds__(64) void hit_select_kernel(HitSelParams prm, int lo
         const uint64_t *u = Uc + u_pos[read];
         const ChainRec *rc = Rc + u_pos[read];
         uint32_t hash = name_hash[read];
-        hash ^= hs_wang32((uint32_t)qlen) + prm.seed_mix;
-        hash = hs_wang32(hash);
+        hash ^= wang32((uint32_t)qlen) + prm.seed_mix;
+        hash = wang32(hash);
         // ---- chains in the order of their first anchors (ties: pool order), their places `as` in that order ----
         for (int c = lane; c < nc; c += 64) { k0[c] = rc[c].fx; TMP[c] = (int32_t)u[c]; }
         __syncthreads();
@@ -107,7 +91,7 @@ __global__ __launch_bounds__(64) void hit_select_kernel(HitSelParams prm, int lo
         for (int t = lane; t < nc; t += 64) {
             const int c = ord[t];
             const ChainRec r = rc[c];
-            const uint32_t h = (uint32_t)hs_hash64((hs_hash64(r.fx) + hs_hash64(r.fy)) ^ hash);
+            const uint32_t h = (uint32_t)hash64((hash64(r.fx) + hash64(r.fy)) ^ hash);
             k0[t] = u[c] ^ (uint64_t)h;
             k1[t] = (uint64_t)AS[t] << 32 | (uint32_t)TMP[c];
         }
@@ -123,6 +107,7 @@ __global__ __launch_bounds__(64) void hit_select_kernel(HitSelParams prm, int lo
             SC[i] = SC0[i] = (int32_t)(x >> 32); HSH[i] = (uint32_t)x; CNT[i] = (int32_t)y; PAR[i] = -1; SUB[i] = 0; NSUB[i] = 0;
             ML[i] = r.mlen; BL[i] = r.blen; SRC[i] = W[c]; SEG[i] = -1;
             TMP[i] = (int32_t)(y >> 32);   // as (moved to AS below: AS is still read by other lanes)
+            // (coor_qs / coor_qe of map_records.h, written out: through the shared functions this fill costs the large instantiation 4 VGPRs)
             const int32_t q_span = (int32_t)(r.fy >> 32 & 0xff);
             const bool rev = r.fx >> 63;
             QS[i] = !rev ? (int32_t)r.fy + 1 - q_span : qlen - ((int32_t)r.ly + 1);
@@ -133,15 +118,11 @@ __global__ __launch_bounds__(64) void hit_select_kernel(HitSelParams prm, int lo
         __syncthreads();
         if (lane == 0) {
             int n = nc, flags = 0;
-            auto rid_of = [&](int i) { return (int32_t)(FX[i] << 1 >> 33); };
-            auto rev_of = [&](int i) { return (int32_t)(FX[i] >> 63); };
-            auto rs_of = [&](int i) { const int32_t sp = (int32_t)(FY[i] >> 32 & 0xff); return (int32_t)FX[i] + 1 > sp ? (int32_t)FX[i] + 1 - sp : 0; };
-            auto re_of = [&](int i) { return (int32_t)LX[i] + 1; };
-            auto set_q = [&](int i) {
-                const int32_t sp = (int32_t)(FY[i] >> 32 & 0xff);
-                if (!rev_of(i)) { QS[i] = (int32_t)FY[i] + 1 - sp; QE[i] = (int32_t)LY[i] + 1; }
-                else { QS[i] = qlen - ((int32_t)LY[i] + 1); QE[i] = qlen - ((int32_t)FY[i] + 1 - sp); }
-            };
+            auto rid_of = [&](int i) { return coor_rid(FX[i]); };
+            auto rev_of = [&](int i) { return coor_rev(FX[i]); };
+            auto rs_of = [&](int i) { return coor_rs(FX[i], FY[i]); };
+            auto re_of = [&](int i) { return coor_re(LX[i]); };
+            auto set_q = [&](int i) { QS[i] = coor_qs(FX[i], FY[i], LY[i], qlen); QE[i] = coor_qe(FX[i], FY[i], LY[i], qlen); };
             auto move = [&](int dst, int src) {
                 FX[dst] = FX[src]; FY[dst] = FY[src]; LX[dst] = LX[src]; LY[dst] = LY[src];
                 SC[dst] = SC[src]; SC0[dst] = SC0[src]; CNT[dst] = CNT[src]; AS[dst] = AS[src]; PAR[dst] = PAR[src]; SUB[dst] = SUB[src];

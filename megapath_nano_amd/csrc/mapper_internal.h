@@ -1,4 +1,4 @@
-// Internal types shared by mapper.hip (seed + chain stages) and align.hip (base-level extension, hit bookkeeping).
+// Internal types shared by mapper.hip (seed + chain stages) and align.hip (base-level extension, hit stage).
 #pragma once
 #include "mpn_common.h"
 #include "map_types.h"

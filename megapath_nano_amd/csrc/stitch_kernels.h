@@ -18,14 +18,7 @@ struct StitchReg {
     int32_t read, rid, rev, pad;
 };
 
-struct StitchOut {
-    int64_t cig_off;                  // start of the stitched CIGAR in the round's pool
-    int32_t n_ops, dp_score, rs1, re1, qs1, qe1;
-    int32_t has_p, dropped, drop_fill, drop_max_t, drop_max_q;   // drop_fill: index of the z-dropped gap fill among the hit's fills
-    int32_t split_n;                  // > 0: a z-drop cuts the hit after its first split_n anchors (mm_align1's mm_split_reg call)
-    int32_t split_inv, split_rec;     // the cut is at an inversion: the remainder is marked (mm_align1: r2->split_inv = 1); index of the hit's SplitRec
-};
-
+// (StitchOut, what the kernel leaves for one hit: map_records.h, where the host unit that applies it finds it)
 
 
 // One hit to align in this round, as the host hands it to the planning kernel (plan_kernels.h), and what that kernel leaves

@@ -4,6 +4,9 @@ chain stage leaves them (x = strand << 63 | rid << 32 | last target base of the 
 chain's strand) and a score.  mlen / blen of a chain follow from its anchors by the mm_cal_fuzzy_len rule.
 
 families() -> {name: [Batch]}; a batch is one call of the stage: options, reads, and the max_chains values to run it with."""
+import os
+import struct
+import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -11,6 +14,7 @@ import numpy as np
 from hit_ref import fuzzy_len
 
 K = 15
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class Chain:
@@ -361,3 +365,102 @@ def hand_family(seed=606):
 
 def families():
     return dict(counts=counts_family(), ties=ties_family(), mask=mask_family(), select=select_family(), join=join_family(), hand=hand_family())
+
+
+# ---- the host check program (scripts/hit_host_check.cpp: csrc/hit_host.cpp + csrc/hits_block.cpp built for the host) ----------------
+BLOCK_FIELDS = ('cnt', 'rid', 'score', 'score0', 'qs', 'qe', 'rs', 're', 'mlen', 'blen', 'rev', 'inv', 'split', 'hash', 'has_p', 'dp_score',
+                'dp_max', 'n_ambi')
+
+
+def build_host_check(out_dir):
+    exe = os.path.join(str(out_dir), 'hit_host_check')
+    csrc = os.path.join(ROOT, 'megapath_nano_amd', 'csrc')
+    base = ['g++', '-std=c++17', '-Wall', '-Werror', '-o', exe, os.path.join(ROOT, 'scripts', 'hit_host_check.cpp'),
+            os.path.join(csrc, 'hit_host.cpp'), os.path.join(csrc, 'hits_block.cpp')]
+    if subprocess.run(base + ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']).returncode != 0:
+        subprocess.run(base + ['-O2'], check=True)
+    return exe
+
+
+def host_hits(exe, tmp, runs):
+    """runs: [(batch, the bytes of its mpn_map_opt)] -> per run, per read (hits as dicts of hit_ref.KEYS, n_a, segments (src, dst, cnt,
+    flag) or None without CIGARs): the host hit path on the chains in pool order"""
+    from hit_ref import KEYS
+    out = [struct.pack('<I', len(runs))]
+    for b, opt in runs:
+        out.append(struct.pack('<I', len(opt)) + opt + struct.pack('<iI', b.k, len(b.reads)))
+        for r in b.reads:
+            name = r.name.encode()
+            out.append(struct.pack('<i', len(name)) + name + struct.pack('<iI', r.qlen, len(r.pool)))
+            for c in r.pool:
+                out.append(struct.pack('<5Q2i', c.score << 32 | len(c.a), c.a[0][0], c.a[0][1], c.a[-1][0], c.a[-1][1], c.mlen, c.blen))
+    src, dst = os.path.join(str(tmp), 'hit_cases.bin'), os.path.join(str(tmp), 'hit_results.bin')
+    with open(src, 'wb') as f:
+        f.write(b''.join(out))
+    subprocess.run([exe, 'hits', src, dst], check=True, timeout=600)
+    blob, p, res = open(dst, 'rb').read(), 0, []
+    unsigned = ('fx', 'fy', 'lx', 'ly', 'hash')
+    for b, opt in runs:
+        reads = []
+        for _ in b.reads:
+            n_regs, n_a, n_segs = struct.unpack_from('<3i', blob, p)
+            p += 12
+            hits = []
+            for _ in range(n_regs):
+                w = struct.unpack_from('<15q', blob, p)
+                p += 120
+                hits.append({key: v & (1 << 64) - 1 if key in unsigned else v for key, v in zip(KEYS, w)})
+            segs = [struct.unpack_from('<q3i', blob, p + 20 * t) for t in range(n_segs)]
+            p += 20 * n_segs
+            reads.append((hits, n_a, segs))
+        res.append(reads)
+    assert p == len(blob)
+    return res
+
+
+def squeezed(read, n_a, segs):
+    """the read's squeezed anchor list as anchor_squeeze_kernel writes it from the segments: every place written exactly once"""
+    pool = [p for c in read.pool for p in c.a]
+    sq = [None] * n_a
+    for src, dst, cnt, flag in segs:
+        assert cnt >= 1 and 0 <= src and src + cnt <= len(pool) and 0 <= dst and dst + cnt <= n_a and flag in (0, 1), (read.name, src, dst, cnt, flag)
+        for j in range(cnt):
+            assert sq[dst + j] is None, (read.name, 'place written twice', dst + j)
+            x, y = pool[src + j]
+            sq[dst + j] = (x, y | 1 << 40) if j == 0 and flag else (x, y)
+    assert None not in sq, (read.name, 'place not written')
+    return sq
+
+
+def host_block(exe, tmp, k, want_text, n_parts, lens, reads, lo, hi):
+    """reads: [(rep_len, [(the BLOCK_FIELDS values, CIGAR words)])] -> (block bytes, the fresh accumulator after two imports of reads
+    [lo, hi) as (k, n_parts, lens, the reads in the same form), the five counts of the refusal loops)"""
+    out = [struct.pack('<4i', k, want_text, n_parts, len(lens)) + struct.pack('<%di' % len(lens), *lens) + struct.pack('<i', len(reads))]
+    for rep_len, hits in reads:
+        out.append(struct.pack('<2i', rep_len, len(hits)))
+        for f, cig in hits:
+            out.append(struct.pack('<18i', *f) + struct.pack('<i%dI' % len(cig), len(cig), *cig))
+    out.append(struct.pack('<2i', lo, hi))
+    src, dst = os.path.join(str(tmp), 'block_cases.bin'), os.path.join(str(tmp), 'block_results.bin')
+    with open(src, 'wb') as f:
+        f.write(b''.join(out))
+    subprocess.run([exe, 'block', src, dst], check=True, timeout=600)
+    blob = open(dst, 'rb').read()
+    size, k2, parts2, n_seq2 = struct.unpack_from('<q3i', blob, 0)
+    p = 20
+    lens2 = list(struct.unpack_from('<%di' % n_seq2, blob, p))
+    p += 4 * n_seq2
+    got = []
+    for _ in range(hi - lo):
+        rep_len, n_hits = struct.unpack_from('<2i', blob, p)
+        p += 8
+        hits = []
+        for _ in range(n_hits):
+            f = struct.unpack_from('<18i', blob, p)
+            nc, = struct.unpack_from('<i', blob, p + 72)
+            hits.append((f, struct.unpack_from('<%dI' % nc, blob, p + 76)))
+            p += 76 + 4 * nc
+        got.append((rep_len, hits))
+    counts = struct.unpack_from('<5q', blob, p)
+    assert p + 40 == len(blob)
+    return size, (k2, parts2, lens2, got), counts

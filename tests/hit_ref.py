@@ -1,7 +1,7 @@
-"""Plain sequential restatement of the hit stage (csrc/hit_kernels.h and gen_regs .. join_long of csrc/align.hip): minimap2's
+"""Plain sequential restatement of the hit stage (csrc/hit_kernels.h and gen_regs .. join_long of csrc/hit_host.cpp): minimap2's
 mm_gen_regs, mm_set_parent, mm_select_sub, mm_squeeze_a and mm_join_long on one read's chains, in Python integers, with numpy
 float32 wherever the C code computes in `float`.  test_hit_ref.py pins it to the oracle's own functions (mmo_hits_from_chains);
-test_hit_select_gpu.py compares the kernel and the host path with it.
+test_hit_select_gpu.py compares the kernel and the host path with it, test_hit_host.py the host path alone on the CPU.
 
 Input as the oracle takes it: u[c] = score << 32 | cnt and the chains' anchors (x, y) back to back, chains in the order of their
 first anchors.  hit_ref() also returns what happened on the way (`ev`), so that the tests can assert that their cases reach the

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of the hit stage (csrc/hit_kernels.h: mm_gen_regs, mm_set_parent, mm_select_sub, mm_squeeze_a, mm_join_long,
-one wave per read; gen_regs .. join_long of csrc/align.hip for the reads left to the host; anchor_squeeze_kernel) through its stage
+one wave per read; gen_regs .. join_long of csrc/hit_host.cpp for the reads left to the host; anchor_squeeze_kernel) through its stage
 entry point mpn_hit_select_batch, which runs the function the mapper runs.  Every per-read and per-hit output and every squeezed
 anchor is compared with the sequential restatement of hit_ref.py, exact integers; test_hit_ref.py pins that restatement to the
 oracle's own functions on the same cases and asserts that the families of hit_cases.py reach the mechanisms these tests are here
